@@ -272,7 +272,7 @@ def run_case(case, L, B, ij, O, dist, comm, rank, world):
         L.hypre_ParCSRMatrixMatvec(2.0, A, dxt, 0.0, dy)
         B.check()
         # the solve with timing events on every exchange (hypre_amd_CommSetTiming): how many there were per AMG level, how long
-        # the transfers took and how much of that the compute stream spent waiting (bench.py --gpus N reports these)
+        # the transfers took and how much of that the compute stream spent waiting (bench.py --full --gpus N reports these)
         L.hypre_amd_CommSetTiming(1)
         if opt.solver == 0:
             L.HYPRE_BoomerAMGSolve(s, A, db, dx)

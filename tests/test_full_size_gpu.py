@@ -16,7 +16,7 @@ that do not need a CPU run of the same size:
   host's cores): 1e-11 relative in the max norm — the full-size counterpart of the small-size cycle tests.
 
 The same hierarchies are compared entry by entry with the CPU oracle at sizes the oracle finishes in seconds
-(test_amg_gpu.py, test_bench_class_gpu.py), and bench.py compares one full-size cycle with the oracle on every run."""
+(test_amg_gpu.py, test_bench_class_gpu.py), and bench.py --full compares one full-size cycle with the oracle."""
 import ctypes as C
 
 import numpy as np

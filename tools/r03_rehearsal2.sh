@@ -3,7 +3,7 @@ out=gpurun_out/${1:-r03_rehearsal2}
 mkdir -p $out
 export HYPRE_AMD_BENCH_TRANSPORT=gloo HYPRE_AMD_SETUP_TIMING=1
 run() { name=$1; ranks=$2; shift 2
-  timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $ranks --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus $ranks --steps 10 --warmup 3 --no-cpu-baseline "$@" > $out/$name.json 2> $out/$name.err
+  timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $ranks --master-addr 127.0.0.1 --master-port 29518 bench.py --full --gpus $ranks --steps 10 --warmup 3 --no-cpu-baseline "$@" > $out/$name.json 2> $out/$name.err
   echo "$name rc=$?"; }
 run c4_4x128 4 --grid 128 --problem 27pt --relax 11
 run c5_4x128 4 --grid 128 --problem difconv --mixed

@@ -5,13 +5,13 @@ for n in 64 128; do
   for sm in "18 -1 l1jacobi" "11 -1 twostage1" "12 -1 twostage2" "21 22 multicolour" "13 14 hybrid_l1gs" "3 4 hybrid_gs"; do
     set -- $sm
     extra=""; [ "$2" != "-1" ] && extra="--relax-up $2"
-    timeout -k 10 300 python bench.py --grid $n --relax $1 $extra --no-cpu-baseline --steps 10 > $out/s_${n}_$3.json 2> $out/s_${n}_$3.err; echo "$n $3 exit $?"
+    timeout -k 10 300 python bench.py --full --grid $n --relax $1 $extra --no-cpu-baseline --steps 10 > $out/s_${n}_$3.json 2> $out/s_${n}_$3.err; echo "$n $3 exit $?"
   done
 done
 for sm in "18 -1 l1jacobi" "11 -1 twostage1" "21 22 multicolour"; do
   set -- $sm
   extra=""; [ "$2" != "-1" ] && extra="--relax-up $2"
-  timeout -k 10 300 python bench.py --grid 256 --relax $1 $extra --no-cpu-baseline --steps 10 > $out/s_256_$3.json 2> $out/s_256_$3.err; echo "256 $3 exit $?"
+  timeout -k 10 300 python bench.py --full --grid 256 --relax $1 $extra --no-cpu-baseline --steps 10 > $out/s_256_$3.json 2> $out/s_256_$3.err; echo "256 $3 exit $?"
 done
 python - <<PY
 import glob, json, os

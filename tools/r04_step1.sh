@@ -10,6 +10,6 @@ HYPRE_AMD_PLAN_VERBOSE=1 timeout -k 10 300 python tools/bench_levels.py 256 20 -
 for w in 2 4 8; do
   HYPRE_AMD_SPMV_RS_W=$w timeout -k 10 300 python tools/bench_levels.py 256 20 --variants 2 --levels 4 --json $out/levels_rsw$w.json > $out/levels_rsw$w.log 2>&1; echo "levels w$w exit $?"
 done
-timeout -k 10 300 python bench.py > $out/bench_c2.json 2> $out/bench_c2.err; echo "c2 exit $?"
+timeout -k 10 300 python bench.py --full > $out/bench_c2.json 2> $out/bench_c2.err; echo "c2 exit $?"
 cat $out/levels_rs0.log | head -40
 cat $out/levels_rs1.log | head -60

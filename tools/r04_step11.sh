@@ -7,8 +7,8 @@ timeout -k 10 600 python -m pytest tests/test_amg_gpu.py -m gpu -x -q > $out/tes
 rc=$?
 tail -15 $out/tests_amg.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py --no-cpu-baseline > $out/bench_on.json 2> $out/bench_on.err && HYPRE_AMD_SMALL_TAIL=0 timeout -k 10 300 python bench.py --no-cpu-baseline > $out/bench_off.json 2> $out/bench_off.err &&
-timeout -k 10 300 python bench.py --no-cpu-baseline > $out/bench_on2.json 2> $out/bench_on2.err && HYPRE_AMD_SMALL_TAIL=0 timeout -k 10 300 python bench.py --no-cpu-baseline > $out/bench_off2.json 2> $out/bench_off2.err
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > $out/bench_on.json 2> $out/bench_on.err && HYPRE_AMD_SMALL_TAIL=0 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $out/bench_off.json 2> $out/bench_off.err &&
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > $out/bench_on2.json 2> $out/bench_on2.err && HYPRE_AMD_SMALL_TAIL=0 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $out/bench_off2.json 2> $out/bench_off2.err
 python - <<'PY'
 import json
 for f in ("on", "off", "on2", "off2"):

@@ -7,7 +7,7 @@ export HYPRE_AMD_BENCH_TRANSPORT=gloo
 for cfg in "dev2 2 --grid 128" "dev4 4 --grid 128" "c4_dev2 2 --grid 96 --problem 27pt --relax 11"; do
   set -- $cfg
   name=$1; np=$2; shift 2
-  timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $np --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus $np --steps 10 --warmup 3 "$@" > $out/bench_rehearsal_$name.json 2> $out/bench_rehearsal_$name.err; echo "$name exit $?"
+  timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $np --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus $np --steps 10 --warmup 3 "$@" > $out/bench_rehearsal_$name.json 2> $out/bench_rehearsal_$name.err; echo "$name exit $?"
 done
 python - <<'PY'
 import json,glob

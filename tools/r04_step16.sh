@@ -7,7 +7,7 @@ timeout -k 10 600 python -m pytest tests/test_multicolor_gpu.py -m gpu -x -q > $
 rc=$?
 tail -12 $out/tests.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py --relax 21 --relax-up 22 --no-cpu-baseline > $out/mc_on.json 2> $out/mc_on.err && HYPRE_AMD_MC_LOOK_AHEAD=0 timeout -k 10 300 python bench.py --relax 21 --relax-up 22 --no-cpu-baseline > $out/mc_off.json 2> $out/mc_off.err
+timeout -k 10 300 python bench.py --full --relax 21 --relax-up 22 --no-cpu-baseline > $out/mc_on.json 2> $out/mc_on.err && HYPRE_AMD_MC_LOOK_AHEAD=0 timeout -k 10 300 python bench.py --full --relax 21 --relax-up 22 --no-cpu-baseline > $out/mc_off.json 2> $out/mc_off.err
 python - <<'PY'
 import json
 for f in ("on", "off"):

@@ -2,7 +2,7 @@ set -x
 out=gpurun_out/r04_step17
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/prof -o b --output-format csv -- python3 bench.py --relax 21 --relax-up 22 --no-cpu-baseline > $out/prof.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/prof -o b --output-format csv -- python3 bench.py --full --relax 21 --relax-up 22 --no-cpu-baseline > $out/prof.log 2>&1
 python - <<'PY'
 import csv, glob
 for f in glob.glob('gpurun_out/r04_step17/prof/**/*kernel_trace.csv', recursive=True):

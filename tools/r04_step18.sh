@@ -7,8 +7,8 @@ timeout -k 10 1100 python -m pytest tests -m gpu -x -q > $out/tests.log 2>&1
 rc=$?
 tail -5 $out/tests.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py --relax 21 --relax-up 22 --cpu-cycles 1 > $out/bench_mc256.json 2> $out/bench_mc256.err; echo "mc256 exit $?"
-timeout -k 10 300 python bench.py --relax 21 --relax-up 22 --grid 128 --no-cpu-baseline > $out/bench_mc128.json 2> $out/bench_mc128.err; echo "mc128 exit $?"
+timeout -k 10 300 python bench.py --full --relax 21 --relax-up 22 --cpu-cycles 1 > $out/bench_mc256.json 2> $out/bench_mc256.err; echo "mc256 exit $?"
+timeout -k 10 300 python bench.py --full --relax 21 --relax-up 22 --grid 128 --no-cpu-baseline > $out/bench_mc128.json 2> $out/bench_mc128.err; echo "mc128 exit $?"
 python - <<'PY'
 import json
 for f in ("mc256", "mc128"):

@@ -5,8 +5,8 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 run() { # name, args...
   name=$1; shift
   for i in 1 2; do
-    timeout -k 10 300 python bench.py --no-cpu-baseline "$@" > $out/${name}_g1_$i.json 2> /dev/null
-    HYPRE_AMD_CYCLE_GRAPH=0 timeout -k 10 300 python bench.py --no-cpu-baseline "$@" > $out/${name}_g0_$i.json 2> /dev/null
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline "$@" > $out/${name}_g1_$i.json 2> /dev/null
+    HYPRE_AMD_CYCLE_GRAPH=0 timeout -k 10 300 python bench.py --full --no-cpu-baseline "$@" > $out/${name}_g0_$i.json 2> /dev/null
   done
 }
 run j128 --grid 128

@@ -3,8 +3,8 @@ out=gpurun_out/r04_step21
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for i in 1 2 3 4 5; do
-  timeout -k 10 300 python bench.py --no-cpu-baseline > $out/base_$i.json 2> /dev/null
-  HYPRE_AMD_LIB=hypre_amd/lib/libhypre_amd_fg4.so timeout -k 10 300 python bench.py --no-cpu-baseline > $out/fg4_$i.json 2> /dev/null
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline > $out/base_$i.json 2> /dev/null
+  HYPRE_AMD_LIB=hypre_amd/lib/libhypre_amd_fg4.so timeout -k 10 300 python bench.py --full --no-cpu-baseline > $out/fg4_$i.json 2> /dev/null
 done
 python - <<'PY'
 import json,glob

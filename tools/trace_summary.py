@@ -1,4 +1,4 @@
-"""Per-launch durations of bench.py's kernel figures out of a rocprofv3 --kernel-trace of bench.py.
+"""Per-launch durations of bench.py's kernel figures out of a rocprofv3 --kernel-trace of bench.py --full.
 
     python tools/trace_summary.py <kernel_trace.csv> <out.json>
 
