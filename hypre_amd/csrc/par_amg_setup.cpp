@@ -1409,6 +1409,34 @@ HYPRE_Int hypre_BoomerAMGBuildDirInterp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_mar
 // ===========================================================================
 
 
+namespace {
+// The flags that route the builders to the device, the twins and the markers belong to ONE run of the setup: set when it
+// starts, cleared on every way out (a standalone call of hypre_BoomerAMGBuildExtPIInterp or ..CoarseOperatorKT afterwards
+// works where its operands are, as the reference's do).
+int g_setup_depth = 0;                       // > 0 while a SetupScope is open
+struct SetupScope
+{
+   int saved_threads;
+   explicit SetupScope(bool device) : saved_threads(omp_get_max_threads())
+   {
+      g_setup_depth++;
+      g_setup_targets_device = device;
+      g_level_on_device = false;
+      g_interp_host_once = false;
+      drop_device_twins();
+   }
+   ~SetupScope()
+   {
+      g_setup_targets_device = false;
+      g_level_on_device = false;
+      g_interp_host_once = false;
+      drop_device_twins();
+      omp_set_num_threads(saved_threads);
+      g_setup_depth--;
+   }
+};
+}  // namespace
+
 static bool device_galerkin_product(hypre_ParCSRMatrix *RT, hypre_ParCSRMatrix *A, hypre_ParCSRMatrix *P,
                                     HYPRE_Int keepTranspose, hypre_ParCSRMatrix **RAP_ptr)
 {
@@ -1471,7 +1499,14 @@ HYPRE_Int hypre_BoomerAMGBuildCoarseOperatorKT(hypre_ParCSRMatrix *RT, hypre_Par
       }
       return dist_build_coarse_operator(RT, A, P, keepTranspose, RAP_ptr);
    }
-   if (device_galerkin_product(RT, A, P, keepTranspose, RAP_ptr)) { return hypre_error_flag; }
+   if (g_device_rap_on == 2 && g_setup_depth == 0)
+   {
+      // test switch: a standalone call takes the device product too; the scope drops the twins of its operands afterwards
+      // (a later call whose matrix reuses a freed address must not find a stale twin)
+      SetupScope scope(true);
+      if (device_galerkin_product(RT, A, P, keepTranspose, RAP_ptr)) { return hypre_error_flag; }
+   }
+   else if (device_galerkin_product(RT, A, P, keepTranspose, RAP_ptr)) { return hypre_error_flag; }
    if (A->diag->memory_location != HYPRE_MEMORY_HOST)
    {
       // the host loop below needs a host copy of A: the caller (the setup loop) fetches it and asks again
@@ -1834,31 +1869,6 @@ static hypre_ParVector *new_vec(MPI_Comm comm, HYPRE_BigInt gsize, HYPRE_BigInt 
    hypre_ParVectorInitialize_v2(v, loc);
    return v;
 }
-
-namespace {
-// The flags that route the builders to the device, the twins and the markers belong to ONE run of the setup: set when it
-// starts, cleared on every way out (a standalone call of hypre_BoomerAMGBuildExtPIInterp or ..CoarseOperatorKT afterwards
-// works where its operands are, as the reference's do).
-struct SetupScope
-{
-   int saved_threads;
-   explicit SetupScope(bool device) : saved_threads(omp_get_max_threads())
-   {
-      g_setup_targets_device = device;
-      g_level_on_device = false;
-      g_interp_host_once = false;
-      drop_device_twins();
-   }
-   ~SetupScope()
-   {
-      g_setup_targets_device = false;
-      g_level_on_device = false;
-      g_interp_host_once = false;
-      drop_device_twins();
-      omp_set_num_threads(saved_threads);
-   }
-};
-}  // namespace
 
 HYPRE_Int hypre_BoomerAMGSetup(void *amg_vdata, hypre_ParCSRMatrix *A, hypre_ParVector *f, hypre_ParVector *u)
 {

@@ -500,6 +500,13 @@ __global__ void rap_bound_kernel(int nc, const int *__restrict__ Ri, const int *
 
 static int pow2_at_least(int v) { int p = 8; while (p < v) { p <<= 1; } return p; }
 
+// Test switches (hypre_amd_SetDeviceRapTables; -1: the default) and how the last product was attempted
+// (hypre_amd_GetDeviceRapPath): tests force the retry ladder and the two-walk form and check which path ran
+static int g_first_RA = -1, g_first_O = -1;
+static long long g_scratch_limit = -1;
+struct RapPath { int pilot, attempts, two_walks, fell_back; };
+static RapPath g_rap_path = {0, 0, 0, 0};
+
 // R (nc x nf), A (nf x nf), P (nf x ncP) as device CSR.  Allocates *Ci / *Cj / *Ca (device) for the product.  Returns false
 // when a row does not fit the LDS budget of a workgroup (the caller then forms this product on the host).
 bool device_rap(int nc, int ncP, int maxP,
@@ -546,13 +553,17 @@ bool device_rap(int nc, int ncP, int maxP,
    // each, their lengths come out of the same pass, a copy packs them.  (With less room: lengths first, then a second
    // walk that writes at the exact offsets.)
    auto table_for = [](int entries) { return pow2_at_least((entries * 29 + 19) / 20); };      // load factor <= 0.69
-   int needRA = std::min(ubA, 384), needO = (int) std::min<long long>(ubO, 192);      // without a pilot (few rows)
+   RapPath path = {0, 0, 0, 0};
+   const bool forced = g_first_RA >= 0 || g_first_O >= 0;            // first tables set by a test: no pilot
+   int needRA = std::min(ubA, g_first_RA >= 0 ? g_first_RA : 384);    // without a pilot (few rows)
+   int needO = (int) std::min<long long>(ubO, g_first_O >= 0 ? g_first_O : 192);
    {
       int pRA = std::min(ubA, 1536), pO = (int) std::min<long long>(ubO, 768);
       pRA = (pRA + 1) & ~1; pO = (pO + 1) & ~1;
       const int pA = table_for(pRA), pP = table_for(pO);
-      if (lds_bytes(pA, pRA, pP, pO) <= budget && nc >= 4096)
+      if (!forced && lds_bytes(pA, pRA, pP, pO) <= budget && nc >= 4096)
       {
+         path.pilot = 1;
          int *d_max = nullptr;
          HIP_CHECK(hipMalloc((void **) &d_max, sizeof(int) * 2));
          HIP_CHECK(hipMemsetAsync(d_max, 0, sizeof(int) * 2, s));
@@ -578,7 +589,7 @@ bool device_rap(int nc, int ncP, int maxP,
    // which needs none
    size_t free_b = 0, total_b = 0;
    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void) hipGetLastError(); free_b = (size_t) 48 << 30; }
-   const size_t scratch_limit = std::min<size_t>((size_t) 24 << 30, free_b / 2);
+   const size_t scratch_limit = g_scratch_limit >= 0 ? (size_t) g_scratch_limit : std::min<size_t>((size_t) 24 << 30, free_b / 2);
    for (int attempt = 0; attempt < 6 && !done; attempt++)
    {
       capRA = (std::min(ubA, needRA) + 1) & ~1;
@@ -586,6 +597,7 @@ bool device_rap(int nc, int ncP, int maxP,
       capO = (int) ((std::min<long long>(ubO, needO) + 1) & ~1LL);
       capP = table_for(capO);
       if (lds_bytes(capA, capRA, capP, capO) > budget) { break; }
+      path.attempts++;
       HIP_CHECK(hipMemsetAsync(d_scr + 1, 0, sizeof(int), s));
       const size_t slots = (size_t) nc * (size_t) capO;
       single = slots * 12 <= scratch_limit;
@@ -622,7 +634,13 @@ bool device_rap(int nc, int ncP, int maxP,
       needRA = std::min(ubA, needRA + needRA / 2 + 16);
       needO = (int) std::min<long long>(ubO, (long long) needO + needO / 2 + 8);
    }
-   auto give_up = [&]() { HIP_CHECK(hipFree(rowlen)); HIP_CHECK(hipFree(d_scr)); if (sj) { HIP_CHECK(hipFree(sj)); } if (sa) { HIP_CHECK(hipFree(sa)); } return false; };
+   path.two_walks = single ? 0 : 1;
+   auto give_up = [&]()
+   {
+      HIP_CHECK(hipFree(rowlen)); HIP_CHECK(hipFree(d_scr)); if (sj) { HIP_CHECK(hipFree(sj)); } if (sa) { HIP_CHECK(hipFree(sa)); }
+      path.fell_back = 1; g_rap_path = path;
+      return false;
+   };
    if (!done) { return give_up(); }
    // row pointers: exclusive scan of the lengths, in place
    launch_scan_exclusive(rowlen, nc, s);
@@ -660,7 +678,12 @@ bool device_rap(int nc, int ncP, int maxP,
       HIP_CHECK(hipMemcpyAsync(h_scr, d_scr, sizeof(int) * 2, hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));
       HIP_CHECK(hipFree(d_scr));
-      if (h_scr[1]) { HIP_CHECK(hipFree(Ci)); HIP_CHECK(hipFree(Cj)); HIP_CHECK(hipFree(Ca)); return false; }
+      if (h_scr[1])
+      {
+         HIP_CHECK(hipFree(Ci)); HIP_CHECK(hipFree(Cj)); HIP_CHECK(hipFree(Ca));
+         path.fell_back = 1; g_rap_path = path;
+         return false;
+      }
    }
    if (timing)
    {
@@ -668,6 +691,7 @@ bool device_rap(int nc, int ncP, int maxP,
               single ? "one walk" : "two walks", t_alloc, t_walk, omp_get_wtime() - t_begin);
    }
    *Ci_out = Ci; *Cj_out = Cj; *Ca_out = Ca; *nnz_out = nnz;
+   g_rap_path = path;
    return true;
 }
 
@@ -746,13 +770,17 @@ bool device_rap_dist(bool direct, int nc, int square, int ncols_out, int maxP, i
    dd.rowlen_d = rowlen_d;
    const int waves = std::min(nc, handle().num_cus * 32);
    auto table_for = [](int entries) { return pow2_at_least((entries * 29 + 19) / 20); };
-   int needRA = std::min(ubA, 384), needO = (int) std::min<long long>(ubO, 192);
+   RapPath path = {0, 0, 0, 0};
+   const bool forced = g_first_RA >= 0 || g_first_O >= 0;
+   int needRA = std::min(ubA, g_first_RA >= 0 ? g_first_RA : 384);
+   int needO = (int) std::min<long long>(ubO, g_first_O >= 0 ? g_first_O : 192);
    {
       int pRA = std::min(ubA, 1536), pO = (int) std::min<long long>(ubO, 768);
       pRA = (pRA + 1) & ~1; pO = (pO + 1) & ~1;
       const int pA = direct ? 8 : table_for(pRA), pP = table_for(pO);
-      if (lds_bytes(pA, pRA, pP, pO) <= budget && nc >= 4096)
+      if (!forced && lds_bytes(pA, pRA, pP, pO) <= budget && nc >= 4096)
       {
+         path.pilot = 1;
          const int step = 61, rows = (nc + step - 1) / step;
          const dim3 g(std::min(rows, handle().num_cus * 8));
          if (direct)
@@ -780,7 +808,7 @@ bool device_rap_dist(bool direct, int nc, int square, int ncols_out, int maxP, i
    double *sa = nullptr;
    size_t free_b = 0, total_b = 0;
    (void) hipMemGetInfo(&free_b, &total_b);
-   const size_t scratch_limit = std::min<size_t>((size_t) 24 << 30, free_b / 2);
+   const size_t scratch_limit = g_scratch_limit >= 0 ? (size_t) g_scratch_limit : std::min<size_t>((size_t) 24 << 30, free_b / 2);
    for (int attempt = 0; attempt < 8 && !done; attempt++)
    {
       capRA = (std::min(ubA, needRA) + 1) & ~1;
@@ -790,6 +818,7 @@ bool device_rap_dist(bool direct, int nc, int square, int ncols_out, int maxP, i
       if (lds_bytes(capA, capRA, capP, capO) > budget) { break; }
       const size_t slots = (size_t) nc * (size_t) capO;
       if (slots * 12 > scratch_limit) { break; }
+      path.attempts++;
       HIP_CHECK(hipMemsetAsync(d_scr + 1, 0, sizeof(int), s));
       if (hipMalloc((void **) &sj, sizeof(int) * slots) != hipSuccess) { sj = nullptr; (void) hipGetLastError(); break; }
       if (hipMalloc((void **) &sa, sizeof(double) * slots) != hipSuccess) { sa = nullptr; (void) hipGetLastError(); break; }
@@ -812,6 +841,8 @@ bool device_rap_dist(bool direct, int nc, int square, int ncols_out, int maxP, i
       needO = (int) std::min<long long>(ubO, (long long) needO + needO / 2 + 8);
    }
    HIP_CHECK(hipFree(d_scr));
+   path.fell_back = done ? 0 : 1;
+   g_rap_path = path;
    if (!done)
    {
       HIP_CHECK(hipFree(rowlen)); HIP_CHECK(hipFree(rowlen_d));
@@ -849,3 +880,21 @@ bool device_rap_dist(bool direct, int nc, int square, int ncols_out, int maxP, i
 void preload_rap_kernels() { hipFuncAttributes at; (void) hipFuncGetAttributes(&at, (const void *) rap_rows_kernel<true>); (void) hipGetLastError(); }
 
 }  // namespace hamd
+
+extern "C" HYPRE_Int hypre_amd_SetDeviceRapTables(HYPRE_Int first_RA, HYPRE_Int first_O, long long scratch_limit)
+{
+   hamd::g_first_RA = first_RA >= 0 ? first_RA : -1;
+   hamd::g_first_O = first_O >= 0 ? first_O : -1;
+   hamd::g_scratch_limit = scratch_limit >= 0 ? scratch_limit : -1;
+   return 0;
+}
+
+extern "C" HYPRE_Int hypre_amd_GetDeviceRapPath(HYPRE_Int *pilot, HYPRE_Int *attempts, HYPRE_Int *two_walks, HYPRE_Int *fell_back)
+{
+   const hamd::RapPath &p = hamd::g_rap_path;
+   if (pilot) { *pilot = p.pilot; }
+   if (attempts) { *attempts = p.attempts; }
+   if (two_walks) { *two_walks = p.two_walks; }
+   if (fell_back) { *fell_back = p.fell_back; }
+   return 0;
+}

@@ -249,8 +249,20 @@ HYPRE_Int hypre_amd_BoomerAMGSetNumThreads(HYPRE_Solver solver, HYPRE_Int num_th
  * one rank: on the device by default (rap_kernels.hip; same columns, order and bits as the host loop), on = 0 keeps the
  * host loop; min_rows: smallest fine level sent to the device (default 20000).  Negative arguments leave a setting
  * unchanged.  Returns the number of products formed on the device since the previous call.  The reference's device setup:
- * parcsr_mv/par_csr_triplemat.c:938-960. */
+ * parcsr_mv/par_csr_triplemat.c:938-960.  Test switch: on = 2 makes a standalone call of
+ * hypre_BoomerAMGBuildCoarseOperatorKT (one rank, RT == P, at least min_rows fine rows) form the product on the device as
+ * well; the result's diagonal block (and the stored transpose) then live in device memory. */
 HYPRE_Int hypre_amd_SetSetupDeviceRAP(HYPRE_Int on, HYPRE_Int min_rows);
+/* Test switches of the device Galerkin product (single-rank and distributed): first_RA / first_O set the table sizes of
+ * its first attempt (entries of the intermediate row R*A and of the output row) instead of the pilot's estimate;
+ * scratch_limit (bytes) replaces the budget of the strided scratch of the one-walk form — 0 sends the single-rank product
+ * to the two-walk form (lengths, then columns and values) and the distributed one, which has no two-walk form, to the
+ * host.  -1 restores the default of an argument. */
+HYPRE_Int hypre_amd_SetDeviceRapTables(HYPRE_Int first_RA, HYPRE_Int first_O, long long scratch_limit);
+/* How the last device Galerkin product was attempted: pilot = 1 if a pilot walk sized the tables, attempts = walks of
+ * the first pass, two_walks = 1 for the two-walk form, fell_back = 1 if the product was left to the host loop.  Any
+ * pointer may be NULL. */
+HYPRE_Int hypre_amd_GetDeviceRapPath(HYPRE_Int *pilot, HYPRE_Int *attempts, HYPRE_Int *two_walks, HYPRE_Int *fell_back);
 /* The same for the extended+i interpolation operators (interp_kernels.hip; scalar problems, levels of at least min_rows
  * rows): on = 0 keeps the host loop; on = 1 + k starts the kernel's ladder of table sizes (64, 128, 256, 1024 entries per
  * row; an overflowing row moves everyone up) at rung k — the results do not depend on it, tests walk the rungs; returns

@@ -59,11 +59,15 @@ def compare_setup(case, L, B, ij, O, dist, comm, rank, world):
     markers, smoother diagonals."""
     opt = ij.IJOptions(**{k: (tuple(v) if isinstance(v, list) else v) for k, v in case["options"].items()})
     hier, counts = [], []
+    rap_path = None
     for on in (0, 1):
         L.hypre_amd_SetSetupDeviceDist(on)
         L.hypre_amd_SetSetupDeviceRAP(1, int(case.get("min_rows", 50)))
         L.hypre_amd_SetSetupDeviceInterp(1 + int(case.get("rung", 0)))
         L.hypre_amd_SetSetupDeviceCoarsen(1)
+        if on and "rap_tables" in case:
+            # the device product's first tables / scratch budget forced: the retry ladder, or the host after the budget
+            L.hypre_amd_SetDeviceRapTables(*[int(v) for v in case["rap_tables"]])
         A = ij.build_matrix(opt, comm=comm, rank=rank, nprocs=world)
         if on and case.get("matrix_on_device"):
             L.hypre_ParCSRMatrixMigrate(A, B.HYPRE_MEMORY_DEVICE)
@@ -73,7 +77,12 @@ def compare_setup(case, L, B, ij, O, dist, comm, rank, world):
             L.hypre_amd_SetupDistTestDecline(int(case["decline"][0]), int(case["decline"][1]), 1)
         L.HYPRE_BoomerAMGSetup(s, A, None, None)
         L.hypre_amd_SetupDistTestDecline(0, -1, 0)
+        L.hypre_amd_SetDeviceRapTables(-1, -1, -1)
         B.check()
+        if on:
+            path = [C.c_int(-1) for _ in range(4)]
+            L.hypre_amd_GetDeviceRapPath(*[C.byref(v) for v in path])
+            rap_path = [v.value for v in path]
         counts.append((L.hypre_amd_SetSetupDeviceCoarsen(-1), L.hypre_amd_SetSetupDeviceInterp(-1), L.hypre_amd_SetSetupDeviceRAP(-1, -1)))
         nl = L.hypre_amd_BoomerAMGGetNumLevels(s)
         lv = []
@@ -115,7 +124,7 @@ def compare_setup(case, L, B, ij, O, dist, comm, rank, world):
                     break
             if mismatch:
                 break
-    mine = dict(mismatch=mismatch, host_counts=counts[0], device_counts=counts[1], pieces=len(hier[1]),
+    mine = dict(mismatch=mismatch, host_counts=counts[0], device_counts=counts[1], pieces=len(hier[1]), rap_path=rap_path,
                 sizes=[int(a[1][0].shape[0]) - 1 for a in hier[1] if a[0].startswith("A")])
     parts = [None] * world if rank == 0 else None
     dist.gather_object(mine, parts, dst=0)
@@ -123,6 +132,7 @@ def compare_setup(case, L, B, ij, O, dist, comm, rank, world):
         bad = [p["mismatch"] for p in parts if p["mismatch"]]
         out = {"name": case.get("name"), "setup_equal": not bad, "mismatch": bad[:3],
                "host_counts": [list(p["host_counts"]) for p in parts], "device_counts": [list(p["device_counts"]) for p in parts],
+               "rap_paths": [p["rap_path"] for p in parts],
                "local_sizes": [p["sizes"] for p in parts]}
         print("RESULT " + json.dumps(out), flush=True)
 

@@ -189,6 +189,11 @@ SETUP_CASES = {
     "decline_product_rank2_3ranks": (3, dict(n=[45, 16, 16], P=[3, 1, 1], relax_type=18, coarsen_type=8), {"decline": [3, 2]}),
     "strong_threshold_4ranks": (4, dict(n=[32, 32, 16], P=[2, 2, 1], relax_type=18, coarsen_type=8, strong_threshold=0.6, max_row_sum=0.8), {}),
 }
+# the device product's retry ladder (first tables forced small) and its budget of strided scratch (0: every product of
+# the distributed levels goes to the host routine) on two of the cases above
+for _base in ("c3_7pt_2ranks", "c4_27pt_2ranks_relax11"):
+    SETUP_CASES[_base + "_rap_small_tables"] = (2, SETUP_CASES[_base][1], {"rap_tables": [16, 8, -1]})
+    SETUP_CASES[_base + "_rap_no_scratch"] = (2, SETUP_CASES[_base][1], {"rap_tables": [-1, -1, 0]})
 _setup = {}
 
 
@@ -222,7 +227,23 @@ def test_distributed_device_setup_is_the_host_setup(name):
     # the host run coarsened nothing on the device, the device run at least two levels on every rank, interpolation and
     # Galerkin product included
     assert all(c[0] == 0 for c in out["host_counts"]), out["host_counts"]
-    assert all(min(c) >= (1 if "decline" in name else 2) for c in out["device_counts"]), out["device_counts"]
+    if name.endswith("_rap_no_scratch"):
+        # no product fits the scratch budget: all of them on the host, coarsening and interpolation still on the device
+        assert all(min(c[:2]) >= 2 and c[2] == 0 for c in out["device_counts"]), out["device_counts"]
+    else:
+        assert all(min(c) >= (1 if "decline" in name else 2) for c in out["device_counts"]), out["device_counts"]
+
+
+@pytest.mark.parametrize("name", sorted(k for k in SETUP_CASES if "_rap_" in k))
+def test_distributed_device_product_takes_the_forced_path(name):
+    """the path report of every rank's last device product: no pilot and a second attempt or more with the small first
+    tables, the host routine without scratch"""
+    paths = _setup_result(name)["rap_paths"]
+    for pilot, attempts, two_walks, fell_back in paths:
+        if name.endswith("_rap_small_tables"):
+            assert pilot == 0 and attempts >= 2 and two_walks == 0 and fell_back == 0, paths
+        else:
+            assert attempts == 0 and fell_back == 1, paths
 
 
 # ... and the solve phase on hierarchies the device built (communication packages, row lists of the ghost blocks, stored
