@@ -70,6 +70,10 @@ struct AmgPrivate
    // mixed precision: fp64 residual and correction of the outer solve loop (a cycle on fp32-rounded operators applied
    // to a non-zero iterate must work on the error equation, or the iteration converges to the rounded system's solution)
    hypre_ParVector *mp_r = nullptr, *mp_e = nullptr;
+   // right-hand sides of several columns (num_vectors > 1): the outer loop's residual of all columns, allocated at the first
+   // such solve and grown with the column count; the single-column Vtemp the cycle (and a recorded tail) uses is untouched
+   hypre_ParVector *mv_resid = nullptr;
+   int              mv_resid_cols = 0;
 
    // Coarse tail of a single-rank V-cycle as one HIP graph.  From level graph_level down and back up every kernel is a
    // few microseconds of work behind a launch that costs as much; the sub-cycle reads F[graph_level], writes U[graph_level]

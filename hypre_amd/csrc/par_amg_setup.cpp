@@ -1872,9 +1872,14 @@ static hypre_ParVector *new_vec(MPI_Comm comm, HYPRE_BigInt gsize, HYPRE_BigInt 
 
 HYPRE_Int hypre_BoomerAMGSetup(void *amg_vdata, hypre_ParCSRMatrix *A, hypre_ParVector *f, hypre_ParVector *u)
 {
-   (void) f; (void) u;
    hypre_ParAMGData *d = (hypre_ParAMGData *) amg_vdata;
    if (!d) { hypre_error_in_arg(1); return hypre_error_flag; }
+   // f and u only shape the solve (par_amg_setup.c:336-339): several columns are taken at solve time, as many in both
+   if (f && u && f->local_vector && u->local_vector && f->local_vector->num_vectors != u->local_vector->num_vectors)
+   {
+      hypre_error_w_msg(HYPRE_ERROR_GENERIC, "Error: num_vectors for RHS and LHS do not match!");
+      return hypre_error_flag;
+   }
    AmgPrivate *pv = (AmgPrivate *) d->amd_private;
    amg_free_hierarchy(d);
    // A (re-)setup is the caller telling the library that the matrix is what it is NOW: whatever earlier products cached for

@@ -22,6 +22,7 @@
 #include "amg_internal.hpp"
 #include <algorithm>
 #include <cmath>
+#include <string>
 
 using namespace hamd;
 
@@ -50,6 +51,7 @@ void AmgPrivate::release_device()
    tail_image_sig = 0; small_tail_level = -2; small_tail_used = -2; tail_outside = -1;
    if (mp_r) { hypre_ParVectorDestroy(mp_r); mp_r = nullptr; }
    if (mp_e) { hypre_ParVectorDestroy(mp_e); mp_e = nullptr; }
+   if (mv_resid) { hypre_ParVectorDestroy(mv_resid); mv_resid = nullptr; }
 }
 
 double *AmgPrivate::level_diag(int level, int n)
@@ -1151,6 +1153,156 @@ HYPRE_Int hypre_BoomerAMGCycle(void *amg_vdata, hypre_ParVector **F_array, hypre
 }
 
 // ===========================================================================
+// several right-hand sides: f and u with num_vectors > 1 (par_amg_solve.c:107-133)
+// ===========================================================================
+// Why a solve of several columns is refused with the solver's options, or "" when it is served: Jacobi-type sweeps 7 / 18
+// and two-stage Gauss-Seidel 11 / 12 over all points, a direct solve on the coarsest level.  The reference refuses hybrid
+// Gauss-Seidel, Jacobi 0 and Chebyshev with multicomponent vectors (par_relax.c:219-224, 751-756; par_cheby.c:423); the
+// other smoothers, C/F-ordered sweeps, grid_relax_points and mixed precision have no multicomponent path.
+static std::string multivector_refusal(const hypre_ParAMGData *d)
+{
+   const AmgPrivate *pv = (const AmgPrivate *) d->amd_private;
+   if (pv && pv->mixed_precision) { return "hypre_BoomerAMGSolve: mixed precision doesn't support multicomponent vectors"; }
+   if (d->grid_relax_points) { return "hypre_BoomerAMGSolve: grid_relax_points don't support multicomponent vectors"; }
+   if (d->relax_order != 0) { return "hypre_BoomerAMGSolve: C/F-ordered relaxation doesn't support multicomponent vectors"; }
+   // the smoothers the cycle takes (par_cycle.c: down, up, coarsest; the user's type on a one-level hierarchy)
+   std::vector<int> types;
+   if (d->num_levels > 1) { types = {d->grid_relax_type[1], d->grid_relax_type[2], d->grid_relax_type[3]}; }
+   else { types = {d->user_relax_type == -1 ? 6 : d->user_relax_type}; }
+   for (size_t k = 0; k < types.size(); k++)
+   {
+      const int t = types[k];
+      const bool coarsest = k == 2 || d->num_levels == 1;
+      if (t == 7 || t == 18 || t == 11 || t == 12 || (coarsest && is_ge_type(t))) { continue; }
+      if (t == 3 || t == 4 || t == 6 || t == 8 || t == 13 || t == 14 || t == 88 || t == 89)
+      {
+         return "Hybrid GS relaxation doesn't support multicomponent vectors";
+      }
+      if (t == 0) { return "Jacobi relaxation doesn't support multicomponent vectors"; }
+      return "Requested relaxation type " + std::to_string(t) + " doesn't support multicomponent vectors";
+   }
+   return "";
+}
+
+// The solve of num_vectors = NV columns stored one after the other.  Every cycle runs column by column on the solver's
+// single-column level vectors, with each column a view of the caller's storage: column v of an NV-column cycle is the
+// single-vector cycle on column v, bit for bit, launch for launch (coarse-tail graph and one-workgroup tail included).
+// The convergence test is the reference's: one residual norm and one right-hand-side norm over all columns, one
+// iteration count.  A refused solve sets the error flag before anything is written.
+static HYPRE_Int amg_solve_columns(hypre_ParAMGData *d, hypre_ParCSRMatrix *A, hypre_ParVector *f, hypre_ParVector *u)
+{
+   hypre_Vector *fl = f->local_vector, *ul = u->local_vector;
+   const int nv = ul->num_vectors;
+   if (fl->num_vectors != nv)
+   {
+      hypre_error_w_msg(HYPRE_ERROR_GENERIC, "Error: num_vectors for RHS and LHS do not match!");
+      return hypre_error_flag;
+   }
+   const int n = A->diag->num_rows;
+   if (fl->size != n || ul->size != n || fl->idxstride != 1 || ul->idxstride != 1 || fl->vecstride != n || ul->vecstride != n)
+   {
+      hypre_error_w_msg(HYPRE_ERROR_GENERIC, "hypre_BoomerAMGSolve: multicomponent f and u must store their columns one after the "
+                                             "other (vecstride = local size, idxstride = 1)");
+      return hypre_error_flag;
+   }
+   const std::string why = multivector_refusal(d);
+   if (!why.empty()) { hypre_error_w_msg(HYPRE_ERROR_GENERIC, why.c_str()); return hypre_error_flag; }
+
+   AmgPrivate *pv = (AmgPrivate *) d->amd_private;
+   const HYPRE_Real tol = d->tol;
+   const int saved_sync = handle().sync_compute;
+   handle().sync_compute = 0;
+   if (d->max_iter > 1) { verify_par_plans(A); }
+   d->A_array[0] = A;
+   hypre_ParVectorSetLocalSize(d->Vtemp, n);
+   std::vector<hypre_Vector> fc((size_t) nv), uc((size_t) nv);
+   std::vector<hypre_ParVector> fp((size_t) nv), up((size_t) nv);
+   for (int v = 0; v < nv; v++)
+   {
+      fc[(size_t) v] = *fl; fc[(size_t) v].data = fl->data + (size_t) v * n; fc[(size_t) v].num_vectors = 1; fc[(size_t) v].owns_data = 0;
+      uc[(size_t) v] = *ul; uc[(size_t) v].data = ul->data + (size_t) v * n; uc[(size_t) v].num_vectors = 1; uc[(size_t) v].owns_data = 0;
+      fp[(size_t) v] = *f; fp[(size_t) v].local_vector = &fc[(size_t) v]; fp[(size_t) v].owns_data = 0;
+      up[(size_t) v] = *u; up[(size_t) v].local_vector = &uc[(size_t) v]; up[(size_t) v].owns_data = 0;
+   }
+
+   const bool track = d->print_level > 1 || d->logging > 1 || tol > 0.;
+   hypre_ParVector *R = nullptr;
+   if (track)
+   {
+      if (pv->mv_resid && (pv->mv_resid_cols < nv || pv->mv_resid->actual_local_size < n))
+      {
+         hypre_ParVectorDestroy(pv->mv_resid);
+         pv->mv_resid = nullptr;
+      }
+      if (!pv->mv_resid)
+      {
+         pv->mv_resid = hypre_ParMultiVectorCreate(A->comm, A->global_num_rows, A->row_starts, nv);
+         hypre_ParVectorInitialize_v2(pv->mv_resid, HYPRE_MEMORY_DEVICE);
+         pv->mv_resid_cols = nv;
+      }
+      R = pv->mv_resid;
+      R->local_vector->num_vectors = nv;
+      hypre_ParVectorSetLocalSize(R, n);
+   }
+   HYPRE_Real resid_nrm = 1.0, resid_nrm_init = 1.0, rhs_norm = 0.0, relative_resid = 1.0, old_resid, conv_factor = 0.0;
+   if (track)
+   {
+      hypre_ParVectorCopy(f, R);
+      if (tol > 0) { hypre_ParCSRMatrixMatvec(1.0, A, u, -1.0, R); }
+      resid_nrm = std::sqrt(hypre_ParVectorInnerProd(R, R));
+      HYPRE_Real ieee_check = 0.;
+      if (resid_nrm != 0.) { ieee_check = resid_nrm / resid_nrm; }
+      if (ieee_check != ieee_check)
+      {
+         if (d->print_level > 0) { fprintf(stderr, "ERROR -- hypre_BoomerAMGSolve: INFs and/or NaNs detected in input.\n"); }
+         handle().sync_compute = saved_sync;
+         d->F_array[0] = f; d->U_array[0] = u;
+         hypre_error(HYPRE_ERROR_GENERIC);
+         return hypre_error_flag;
+      }
+      resid_nrm_init = resid_nrm;
+      if (d->converge_type == 0)
+      {
+         rhs_norm = std::sqrt(hypre_ParVectorInnerProd(f, f));
+         relative_resid = rhs_norm ? resid_nrm_init / rhs_norm : resid_nrm_init;
+      }
+   }
+   HYPRE_Int cycle_count = 0;
+   while ((relative_resid >= tol || cycle_count < d->min_iter) && cycle_count < d->max_iter)
+   {
+      for (int v = 0; v < nv; v++)
+      {
+         d->cycle_op_count = 0;          // (one cycle's count, as with one column)
+         d->F_array[0] = &fp[(size_t) v]; d->U_array[0] = &up[(size_t) v];
+         hypre_BoomerAMGCycle(d, d->F_array, d->U_array);
+      }
+      u->all_zeros = 0;
+      if (track)
+      {
+         old_resid = resid_nrm;
+         hypre_ParCSRMatrixMatvecOutOfPlace(1.0, A, u, -1.0, f, R);
+         resid_nrm = std::sqrt(hypre_ParVectorInnerProd(R, R));
+         conv_factor = old_resid ? resid_nrm / old_resid : resid_nrm;
+         if (d->converge_type == 0) { relative_resid = rhs_norm ? resid_nrm / rhs_norm : resid_nrm; }
+         else { relative_resid = resid_nrm / resid_nrm_init; }
+         d->rel_resid_norm = relative_resid;
+      }
+      ++cycle_count;
+      d->num_iterations = cycle_count;
+      if (d->print_level > 1)
+      {
+         HYPRE_Int rank; hypre_MPI_Comm_rank(A->comm, &rank);
+         if (rank == 0) { printf("    Cycle %2d   %e    %f     %e \n", cycle_count, resid_nrm, conv_factor, relative_resid); }
+      }
+   }
+   d->F_array[0] = f; d->U_array[0] = u;        // (no view of a column outlives the call)
+   if (cycle_count == d->max_iter && tol > 0.) { hypre_error(HYPRE_ERROR_CONV); }
+   handle().sync_compute = saved_sync;
+   maybe_sync();
+   return hypre_error_flag;
+}
+
+// ===========================================================================
 // outer solve loop (par_amg_solve.c:22-424)
 // ===========================================================================
 HYPRE_Int hypre_BoomerAMGSolve(void *amg_vdata, hypre_ParCSRMatrix *A, hypre_ParVector *f, hypre_ParVector *u)
@@ -1165,6 +1317,7 @@ HYPRE_Int hypre_BoomerAMGSolve(void *amg_vdata, hypre_ParCSRMatrix *A, hypre_Par
    HYPRE_AMD_REQUIRE_DEVICE(A->diag->memory_location, "hypre_BoomerAMGSolve(A)");
    HYPRE_AMD_REQUIRE_DEVICE(f->local_vector->memory_location, "hypre_BoomerAMGSolve(f)");
    HYPRE_AMD_REQUIRE_DEVICE(u->local_vector->memory_location, "hypre_BoomerAMGSolve(u)");
+   if (f->local_vector->num_vectors != 1 || u->local_vector->num_vectors != 1) { return amg_solve_columns(d, A, f, u); }
    const HYPRE_Real tol = d->tol;
    const int saved_sync = handle().sync_compute;
    handle().sync_compute = 0;

@@ -360,10 +360,16 @@ def parse_cli(argv):
             raise SystemExit("ij: option %s is outside the scope of this driver" % flag)
     if opt.solver not in (0, 1, 2, 3, 4):
         raise SystemExit("ij: -solver %d is outside the scope of this driver (0 AMG, 1 AMG-PCG, 2 DS-PCG, 3 AMG-GMRES, 4 DS-GMRES)" % opt.solver)
-    if opt.num_components < 1 or (opt.num_components > 1 and (opt.solver not in (2, 4) or opt.rhs != "one" or opt.rhsfromfile)):
-        # test/ij.c:3400-3404 takes several components with the constant right-hand sides only; of the solvers that accept
-        # multivectors (test/TEST_ij/vector.jobs) this driver has the diagonally scaled PCG
-        raise SystemExit("ij: -nc %d needs -solver 2 or 4 and -rhsisone in this driver" % opt.num_components)
+    if opt.num_components < 1 or (opt.num_components > 1 and (opt.rhs != "one" or opt.rhsfromfile)):
+        # test/ij.c:3400-3404 takes several components with the constant right-hand sides only
+        raise SystemExit("ij: -nc %d needs -rhsisone in this driver" % opt.num_components)
+    if opt.num_components > 1 and opt.solver in (0, 1, 3):
+        # BoomerAMG on multivectors (hypre_BoomerAMGSolve with num_vectors > 1) serves l1-Jacobi / Jacobi 7 / 18 and two-stage
+        # Gauss-Seidel 11 / 12 over all points with a direct coarsest-level solve; the reference refuses hybrid Gauss-Seidel
+        # (the defaults 13 / 14) with multicomponent vectors as well
+        why = multivector_amg_refusal(opt)
+        if why:
+            raise SystemExit("ij: -nc %d with -solver %d: %s" % (opt.num_components, opt.solver, why))
     if opt.interp_type not in (6, 3):
         raise SystemExit("ij: -interptype %d is outside the scope of this driver (6 ext+i, 3 direct)" % opt.interp_type)
     smoothers = (-1, 0, 3, 4, 6, 7, 8, 11, 12, 13, 14, 15, 16, 17, 18, 88, 89)
@@ -376,6 +382,31 @@ def parse_cli(argv):
     if any(w < 0 for w in weights):
         raise SystemExit("ij: negative (automatically estimated) relaxation weights are outside the scope of this driver")
     return opt
+
+
+def resolved_smoothers(opt):
+    """The smoothers (down, up, coarsest) the options give a hierarchy: HYPRE_BoomerAMGSetRelaxType sets the first two and the
+    direct solve 9 on the coarsest level, -rlx_down / -rlx_up / -rlx_coarse override them (defaults 13 / 14 / 9)."""
+    down = opt.relax_down if opt.relax_down > -1 else (opt.relax_type if opt.relax_type > -1 else 13)
+    up = opt.relax_up if opt.relax_up > -1 else (opt.relax_type if opt.relax_type > -1 else 14)
+    coarse = opt.relax_coarse if opt.relax_coarse > -1 else 9
+    return down, up, coarse
+
+
+def multivector_amg_refusal(opt):
+    """Why BoomerAMG cannot take -nc N columns with these options ("" when it can): the smoothers and switches that
+    hypre_BoomerAMGSolve serves on multivectors."""
+    down, up, coarse = resolved_smoothers(opt)
+    for where, t in (("down", down), ("up", up), ("coarse", coarse)):
+        if t in (7, 18, 11, 12) or (where == "coarse" and t in (9, 19, 98, 99)):
+            continue
+        kind = {0: "Jacobi 0", 16: "Chebyshev 16"}.get(t, "hybrid Gauss-Seidel %d" % t if t in (3, 4, 6, 8, 13, 14, 88, 89) else "%d" % t)
+        return "smoother %s (%s) doesn't support multicomponent vectors (served: 7, 18, 11, 12; direct coarse solve)" % (kind, where)
+    if opt.relax_order != 0:
+        return "C/F-ordered relaxation (-CF %d) doesn't support multicomponent vectors" % opt.relax_order
+    if opt.mixed:
+        return "mixed precision doesn't support multicomponent vectors"
+    return ""
 
 
 def run(opt, comm=0, rank=0, nprocs=1, allreduce=None, out=None):
@@ -393,18 +424,31 @@ def run(opt, comm=0, rank=0, nprocs=1, allreduce=None, out=None):
     Am = A.contents
     first, nglob = int(Am.row_starts[0]), int(Am.global_num_rows)
     b, x0 = build_rhs_host(opt, A, rank=rank, allreduce=allreduce)
-    dx = B.parvec_from_numpy(x0, comm=comm, global_size=nglob, first=first)
+    nv = opt.num_components
     if b is None:
         ones = B.parvec_from_numpy(np.ones(len(x0)), comm=comm, global_size=nglob, first=first)
         db = B.parvec_from_numpy(np.zeros(len(x0)), comm=comm, global_size=nglob, first=first)
         L.hypre_ParCSRMatrixMatvec(1.0, A, ones, 0.0, db)
+        if nv > 1:
+            b = B.parvec_to_numpy(db)
+            L.hypre_ParVectorDestroy(db)
+        L.hypre_ParVectorDestroy(ones)
+    if nv > 1:
+        # -nc N: the same values in every column of b and of the initial guess (test/ij.c:3483-3512)
+        db = B.parmultivec_from_numpy(np.repeat(b[:, None], nv, axis=1), comm=comm, global_size=nglob, first=first)
+        dx = B.parmultivec_from_numpy(np.repeat(x0[:, None], nv, axis=1), comm=comm, global_size=nglob, first=first)
     else:
-        db = B.parvec_from_numpy(b, comm=comm, global_size=nglob, first=first)
+        if b is not None:
+            db = B.parvec_from_numpy(b, comm=comm, global_size=nglob, first=first)
+        dx = B.parvec_from_numpy(x0, comm=comm, global_size=nglob, first=first)
     its, rel = C.c_int(), C.c_double()
     lines = []
     if opt.solver == 0:
         # ||b - A x0|| for the average convergence factor (par_amg_solve.c:237-256, 347-355)
-        r0 = B.parvec_from_numpy(np.zeros(len(x0)), comm=comm, global_size=nglob, first=first)
+        if nv > 1:
+            r0 = B.parmultivec_from_numpy(np.zeros((len(x0), nv)), comm=comm, global_size=nglob, first=first)
+        else:
+            r0 = B.parvec_from_numpy(np.zeros(len(x0)), comm=comm, global_size=nglob, first=first)
         L.hypre_ParCSRMatrixMatvecOutOfPlace(-1.0, A, dx, 1.0, db, r0)
         L.hypre_ParVectorInnerProd.restype = C.c_double
         nrm0 = float(np.sqrt(L.hypre_ParVectorInnerProd(r0, r0)))
