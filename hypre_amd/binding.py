@@ -208,6 +208,9 @@ PROTOTYPES = {
     "hypre_amd_SpmvSetValueCodes": (Int, [Int]),
     "hypre_amd_SpmvSetSliceForm": (Int, [Int]),
     "hypre_amd_CSRMatrixPlanSliceForm": (Int, [CSRp]),
+    "hypre_amd_SpmvSetSliceClasses": (Int, [Int]),
+    "hypre_amd_CSRMatrixPlanSliceClasses": (Int, [CSRp]),
+    "hypre_amd_CSRMatrixPlanSliceClassHistogram": (Int, [CSRp, C.POINTER(Int), C.POINTER(Int), C.POINTER(BigInt)]),
     "hypre_amd_CSRMatrixPlanValueCodes": (Int, [CSRp]),
     "hypre_SeqVectorSetConstantValues": (Int, [Vecp, Real]),
     "hypre_SeqVectorCopy": (Int, [Vecp, Vecp]),

@@ -139,7 +139,16 @@ struct SpmvPlan
    int      *d_sl_cnt = nullptr, *d_sl_desc = nullptr;    // per block, as d_xs_cnt / d_xs_desc per tile
    int      *d_sl_k0 = nullptr, *d_sl_fp = nullptr;       // per block: position of its first entry; fingerprint of two of its columns
    int      *d_sl_perm = nullptr;                          // workgroup -> block (band-aware placement), or null
-   unsigned *d_sl_data = nullptr;                          // [sl_blocks][4 waves][sl_wc + sl_wl][64 lanes]
+   unsigned *d_sl_data = nullptr;                          // [sl_blocks][4 waves][sl_wc + sl_wl][64 lanes]; null when the classes below hold the words
+   // Class storage of the slice form (spmv_sl_kernel_cls): inside a block the words of lane-row t are those of a few CLASSES
+   // with t added to every local index, so a lane streams one byte (its class) and the block's table rides into LDS with
+   // the x pieces.  Adopted for the whole matrix or not at all (device_build_slice_classes); d_sl_data is then freed.
+   unsigned char *d_sl_cls = nullptr;                      // [sl_blocks][256] class of every lane
+   unsigned      *d_sl_tab = nullptr;                      // [sl_class_total][sl_k]: entries of the lane, code words, index words less the lane-row
+   int           *d_sl_toff = nullptr;                     // [sl_blocks + 1] first class of every block
+   int            sl_classes = 0;                          // most classes of any block (0: packed words)
+   long long      sl_class_total = 0;                      // classes of all blocks
+   bool has_slice_form() const { return d_sl_data != nullptr || d_sl_cls != nullptr; }
    // Row-slice form (spmv_rs_kernel): matrices that cannot change behind their plans (owned) and are not coded — the Galerkin
    // operators of the coarse levels, 30 - 90 entries per row, every value distinct — are stored once more as JAGGED SLICES:
    // a workgroup takes rs_rows = 256 / rs_w consecutive rows, rs_w lanes per row (lane `sub` takes entries sub, sub + rs_w,
@@ -201,7 +210,7 @@ bool is_owned(const hypre_CSRMatrix *A);
 bool plan_verify(hypre_CSRMatrix *A);
 // checked device allocation of the plan builders (seq_mv.cpp): false — nothing allocated, no HIP error left behind — when the
 // memory is not to be had, when the request exceeds half of what is free, or when a test armed this site
-enum PlanAllocSite { PLAN_SITE_TILES = 1, PLAN_SITE_XS = 2, PLAN_SITE_CODES = 3, PLAN_SITE_SLICE = 4, PLAN_SITE_ROWSLICE = 5 };
+enum PlanAllocSite { PLAN_SITE_TILES = 1, PLAN_SITE_XS = 2, PLAN_SITE_CODES = 3, PLAN_SITE_SLICE = 4, PLAN_SITE_ROWSLICE = 5, PLAN_SITE_SLICE_CLASSES = 6 };
 bool plan_alloc(void **ptr, size_t bytes, int site);
 void plan_free(void *ptr);
 // where a solve begins: the plans of the caller's matrix are verified against its arrays (plan_verify) — a plan that
@@ -312,6 +321,7 @@ bool device_build_slice_form(SpmvPlan *p, const hypre_CSRMatrix *A, hipStream_t 
 // row-slice form of an owned, uncoded matrix (false: not applicable, or a table was not to be had: the tiles serve)
 bool device_build_row_slices(SpmvPlan *p, const hypre_CSRMatrix *A, hipStream_t s);
 int  &spmv_row_slices();              // 0 off, 1 matrices the library owns (default), 2 every matrix (tests); HYPRE_AMD_SPMV_ROW_SLICES
+bool &spmv_slice_classes();            // slice forms built from now on store class bytes where the blocks repeat (default: on; HYPRE_AMD_SPMV_SLICE_CLASSES=0)
 bool &spmv_slice_form();               // plans built from now on get the slice form where it applies (default: on; HYPRE_AMD_SPMV_SLICE_FORM=0)
 bool &spmv_value_codes();              // plans built from now on look for value codes (default: on; HYPRE_AMD_SPMV_VALUE_CODES=0)
 void launch_build_tiles(const HYPRE_Int *Ai, int num_rows, int nnz, int num_tiles, int *d_tile_row,

@@ -251,6 +251,9 @@ static void free_plan(SpmvPlan *p)
    if (p->d_sl_fp) { HIP_CHECK(hipFree(p->d_sl_fp)); }
    if (p->d_sl_perm) { HIP_CHECK(hipFree(p->d_sl_perm)); }
    if (p->d_sl_data) { HIP_CHECK(hipFree(p->d_sl_data)); }
+   if (p->d_sl_cls) { HIP_CHECK(hipFree(p->d_sl_cls)); }
+   if (p->d_sl_tab) { HIP_CHECK(hipFree(p->d_sl_tab)); }
+   if (p->d_sl_toff) { HIP_CHECK(hipFree(p->d_sl_toff)); }
    for (void *q : {(void *) p->d_rs_desc, (void *) p->d_rs_perm, (void *) p->d_rs_hdr, (void *) p->d_rs_meta, (void *) p->d_rs_val,
                    (void *) p->d_rs_val32, (void *) p->d_rs_idx}) { plan_free(q); }
    if (p->AT) { hypre_CSRMatrixDestroy(p->AT); }
@@ -445,6 +448,12 @@ bool &spmv_slice_form()
    return on;
 }
 
+bool &spmv_slice_classes()
+{
+   static bool on = [] { const char *e = getenv("HYPRE_AMD_SPMV_SLICE_CLASSES"); return !(e && atoi(e) == 0); }();
+   return on;
+}
+
 bool &spmv_fused_multivectors()
 {
    static bool on = [] { const char *e = getenv("HYPRE_AMD_SPMV_FUSED_MV"); return !(e && atoi(e) == 0); }();
@@ -561,6 +570,42 @@ extern "C" HYPRE_Int hypre_amd_SpmvSetSliceForm(HYPRE_Int on)
    return hypre_error_flag;
 }
 
+// Class storage of the slice form for the plans built from now on: a lane streams one class byte instead of its packed
+// words where the blocks of the matrix repeat themselves.  Speed only: same words, same products, bit for bit.
+extern "C" HYPRE_Int hypre_amd_SpmvSetSliceClasses(HYPRE_Int on)
+{
+   if (on >= 0) { hamd::spmv_slice_classes() = on != 0; }
+   return hypre_error_flag;
+}
+// most classes of any block of the slice form in A's plan (built on demand); 0: the matrix streams packed words, or has no slice form
+extern "C" HYPRE_Int hypre_amd_CSRMatrixPlanSliceClasses(hypre_CSRMatrix *A)
+{
+   if (!A || A->memory_location != HYPRE_MEMORY_DEVICE) { return 0; }
+   hamd::SpmvPlan *p = hamd::get_plan(A);
+   return p->d_sl_cls ? p->sl_classes : 0;
+}
+
+// classes per block of the slice form in A's plan: hist[c] (c = 0 .. 255) = number of blocks that hold c classes; fills the
+// number of blocks and the classes of all blocks (the rows of d_sl_tab); returns the most classes of a block, 0 (nothing
+// filled) when the plan streams packed words
+extern "C" HYPRE_Int hypre_amd_CSRMatrixPlanSliceClassHistogram(hypre_CSRMatrix *A, HYPRE_Int *hist, HYPRE_Int *blocks, HYPRE_BigInt *total)
+{
+   if (!A || A->memory_location != HYPRE_MEMORY_DEVICE) { return 0; }
+   hamd::SpmvPlan *p = hamd::get_plan(A);
+   if (!p->d_sl_cls) { return 0; }
+   std::vector<int> toff((size_t) p->sl_blocks + 1);
+   HIP_CHECK(hipStreamSynchronize(hamd::stream()));
+   HIP_CHECK(hipMemcpy(toff.data(), p->d_sl_toff, sizeof(int) * toff.size(), hipMemcpyDeviceToHost));
+   if (hist)
+   {
+      for (int c = 0; c < 256; c++) { hist[c] = 0; }
+      for (int b = 0; b < p->sl_blocks; b++) { hist[std::min(std::max(toff[(size_t) b + 1] - toff[(size_t) b], 0), 255)]++; }
+   }
+   if (blocks) { *blocks = p->sl_blocks; }
+   if (total) { *total = (HYPRE_BigInt) p->sl_class_total; }
+   return p->sl_classes;
+}
+
 // Row-slice form for the plans built from now on: 0 off, 1 matrices the library owns or the caller declared immutable
 // (default), 2 every matrix (tests: the caller then owes hypre_amd_CSRMatrixInvalidatePlan after any change).  Speed only.
 extern "C" HYPRE_Int hypre_amd_SpmvSetRowSlices(HYPRE_Int mode)
@@ -587,7 +632,7 @@ extern "C" HYPRE_Int hypre_amd_CSRMatrixPlanSliceForm(hypre_CSRMatrix *A)
 {
    if (A->memory_location != HYPRE_MEMORY_DEVICE) { return 0; }
    hamd::SpmvPlan *p = hamd::get_plan(A);
-   return p->d_sl_data ? p->sl_w : 0;
+   return p->has_slice_form() ? p->sl_w : 0;
 }
 
 // number of distinct values in the value table of A's plan (built on demand); 0: the matrix is not coded
@@ -665,7 +710,7 @@ extern "C" HYPRE_Int hypre_amd_CSRMatrixSetImmutable(hypre_CSRMatrix *A, HYPRE_I
 }
 
 // Test hook: the nth allocation (1 = the next) that a plan builder makes at `site` fails, once — 1 tile tables, 2 x-staging
-// tables, 3 value codes, 4 slice form, 5 row-slice form.  nth <= 0 disarms.  Returns what was still pending of the request
+// tables, 3 value codes, 4 slice form, 5 row-slice form, 6 class storage of the slice form.  nth <= 0 disarms.  Returns what was still pending of the request
 // before (0: it happened, or nothing was armed).
 extern "C" HYPRE_Int hypre_amd_PlanTestFailAlloc(HYPRE_Int site, HYPRE_Int nth)
 {
@@ -692,7 +737,7 @@ extern "C" HYPRE_Int hypre_amd_CSRMatrixPlanForm(hypre_CSRMatrix *A)
    if (!p->tiled) { return 0; }
    if (p->d_rs_val) { return 5; }
    if (!p->d_lidx) { return 1; }
-   if (p->d_sl_data) { return 4; }
+   if (p->has_slice_form()) { return 4; }
    if (p->d_codes) { return 3; }
    return 2;
 }

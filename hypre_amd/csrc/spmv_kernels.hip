@@ -1396,18 +1396,106 @@ void launch_build_xs(const HYPRE_Int *Aj, const int *d_tile_k, int num_tiles, in
 // which it takes for tiles of 65 to 128 rows).
 // The kernel reads neither the column array nor the values: the staleness watch samples both per block.
 // ---------------------------------------------------------------------------
-// KP, the entries a lane holds: 8 or 16 (a compile-time count: every load of the stream is then unconditional and the
-// sum a straight line; with run-time word counts the compiler put a wait behind every load)
-template <int OP, int W, int KP>
-__global__ __launch_bounds__(SPMV_THREADS)
-void spmv_sl_kernel(SpmvArgs p, const int *__restrict__ sl_cnt, const int *__restrict__ sl_desc, const int *__restrict__ sl_k0,
-                    const int *__restrict__ sl_fp, const int *__restrict__ sl_perm, const unsigned *__restrict__ sl_data,
-                    int blocks, int num_rows, int nnz, int stage_elems)
+// Where a lane's words come from (one mode per matrix, chosen when the plan is built):
+//  - the packed stream (`data`): wc + wl words per lane, read as they are;
+//  - CLASSES: inside a block, lane-row t's words are those of a few classes (interior, left end, right end of a grid line ...)
+//    with t added to every local index — a column one further is staged one further.  The lane reads ONE BYTE (`cls`: its
+//    class), the block's table (`tab`: KP words per class — [0] the entries the lane holds, [1 .. wc] the code words,
+//    [1 + wc .. wc + wl] the index words less t in both 16-bit halves, modulo 2^16; `toff`: the first class of every block)
+//    rides into LDS with the x pieces, and after the barrier the lane reads its class's words there and adds t back.  The
+//    words are those of the packed stream except that the halves of entries the lane does not hold read t instead of 0:
+//    their products are computed and dropped, as before (the staged copy holds at least 256 doubles in this mode).
+struct SlStream
+{
+   const unsigned      *data;
+   const unsigned char *cls;     // [blocks][SPMV_THREADS]
+   const unsigned      *tab;     // [toff[blocks]][KP]
+   const int           *toff;    // [blocks + 1]
+};
+template <bool CLS, int KP>
+struct SlLane
+{
+   unsigned cw[KP / 4], lw[KP / 2];
+   int rs, re;                   // packed: the row's bounds.  Classes: rs the block's first row pointer (wave-uniform), re the class byte
+   int t0, t1;                   // classes: the block's first class, the one behind its last (wave-uniform)
+};
+// issued first, before anything about the block is known: the lane's vector loads (and the scalar ones that go with them)
+template <bool CLS, int W, int KP>
+__device__ __forceinline__ void sl_lane_load(SlLane<CLS, KP> &me, const SlStream &st, const int *__restrict__ Ai, int block, int wave,
+                                             int lane, int tid, int r, int num_rows)
+{
+   constexpr int wc = KP / 4, wl = KP / 2, R = SPMV_THREADS / W;
+   if constexpr (CLS)
+   {
+      me.re = st.cls[(size_t) block * SPMV_THREADS + tid];
+      me.rs = Ai[min(block * R, num_rows)];
+      me.t0 = st.toff[block]; me.t1 = st.toff[block + 1];
+   }
+   else
+   {
+      const unsigned *sd = st.data + ((size_t) (block * 4 + wave) * (size_t) (wc + wl)) * 64 + lane;
+#pragma unroll
+      for (int w = 0; w < wc; w++) { me.cw[w] = sd[w * 64]; }
+#pragma unroll
+      for (int w = 0; w < wl; w++) { me.lw[w] = sd[(wc + w) * 64]; }
+      me.rs = Ai[min(r, num_rows)]; me.re = Ai[min(r + 1, num_rows)];
+      me.t0 = me.t1 = 0;
+   }
+}
+// with the x pieces: the block's class table into LDS (16 bytes a lane; a table of up to 64 (KP = 16) or 128 classes is one trip
+// of the four waves)
+template <bool CLS, int KP>
+__device__ __forceinline__ void sl_lane_stage(const SlLane<CLS, KP> &me, const SlStream &st, int wave, int lane, unsigned *tabl)
+{
+   if constexpr (CLS)
+   {
+      const unsigned *src = st.tab + (size_t) me.t0 * KP;
+      const int nw = (me.t1 - me.t0) * KP;
+      for (int base = 256 * wave; base < nw; base += 4 * SPMV_THREADS)
+      {
+         if (4 * lane < nw - base)
+         {
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) (src + base + 4 * lane),
+                                             (__attribute__((address_space(3))) void *) (tabl + base), 16, 0, 0);
+         }
+      }
+   }
+}
+// after the barrier: the words in me.cw / me.lw; returns the number of entries the lane holds
+template <bool CLS, int W, int KP>
+__device__ __forceinline__ int sl_lane_words(SlLane<CLS, KP> &me, int tid, const unsigned *tabl)
 {
    constexpr int wc = KP / 4, wl = KP / 2;
+   if constexpr (CLS)
+   {
+      typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+      const uint4 *e = reinterpret_cast<const uint4 *>(tabl + (unsigned) me.re * KP);
+      unsigned w[KP];
+#pragma unroll
+      for (int q = 0; q < KP / 4; q++) { const uint4 v = e[q]; w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w; }
+      const unsigned short t = (unsigned short) (tid / W);
+      const us2 tt = {t, t};
+#pragma unroll
+      for (int i = 0; i < wc; i++) { me.cw[i] = w[1 + i]; }
+#pragma unroll
+      for (int i = 0; i < wl; i++) { me.lw[i] = __builtin_bit_cast(unsigned, (us2) (__builtin_bit_cast(us2, w[1 + wc + i]) + tt)); }
+      return (int) w[0];
+   }
+   else { return (me.re - me.rs - tid % W + W - 1) / W; }
+}
+
+// KP, the entries a lane holds: 8 or 16 (a compile-time count: every load of the stream is then unconditional and the
+// sum a straight line; with run-time word counts the compiler put a wait behind every load)
+template <int OP, int W, int KP, bool CLS>
+__device__ __forceinline__
+void spmv_sl_body(const SpmvArgs &p, const int *__restrict__ sl_desc, const int *__restrict__ sl_k0,
+                  const int *__restrict__ sl_fp, const int *__restrict__ sl_perm, const SlStream &st,
+                  int blocks, int num_rows, int nnz, int stage_elems)
+{
    extern __shared__ __align__(16) unsigned char smem_raw[];
    double *xs = reinterpret_cast<double *>(smem_raw);
    const double *dictl = xs + stage_elems;
+   unsigned *tabl = reinterpret_cast<unsigned *>(xs + stage_elems + ((p.ndict + 1) & ~1));      // class table (CLS), behind the value table
 
    int block = (int) blockIdx.x;
    if (sl_perm)
@@ -1421,15 +1509,10 @@ void spmv_sl_kernel(SpmvArgs p, const int *__restrict__ sl_cnt, const int *__res
    const int tid = threadIdx.x, lane = tid & 63;
    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
    constexpr int R = SPMV_THREADS / W;
-   // this lane's words of the slice: one trip, issued before anything about the block is known
-   const unsigned *sd = sl_data + ((size_t) (block * 4 + wave) * (size_t) (wc + wl)) * 64 + lane;
-   unsigned cw[wc], lw[wl];
-#pragma unroll
-   for (int w = 0; w < wc; w++) { cw[w] = sd[w * 64]; }
-#pragma unroll
-   for (int w = 0; w < wl; w++) { lw[w] = sd[(wc + w) * 64]; }
+   // this lane's words of the slice (or its class byte): one trip, issued before anything about the block is known
    const int r = block * R + tid / W, sub = tid % W;
-   const int rs = p.Ai[min(r, num_rows)], re = p.Ai[min(r + 1, num_rows)];
+   SlLane<CLS, KP> me;
+   sl_lane_load<CLS, W, KP>(me, st, p.Ai, block, wave, lane, tid, r, num_rows);
    const RowOps ops = load_row_ops<OP>(p, max(min(r, num_rows - 1), 0));
    // wave-uniform, through the scalar cache: this wave's piece descriptors, the block's first entry and fingerprint
    const int *dsc = sl_desc + (size_t) block * XS_DESC + XS_WSEG * wave;
@@ -1437,7 +1520,7 @@ void spmv_sl_kernel(SpmvArgs p, const int *__restrict__ sl_cnt, const int *__res
 #pragma unroll
    for (int j = 0; j < XS_WSEG; j++) { seg_start[j] = dsc[j]; seg_ol[j] = dsc[XS_SEGS + j]; }
    const int k0 = sl_k0[block], k1b = sl_k0[block + 1], fp_plan = sl_fp[block];
-   asm volatile("" :: "s"(sl_desc), "s"(sl_k0), "s"(sl_fp), "s"(sl_data), "s"(p.Ai) : "memory");
+   asm volatile("" :: "s"(sl_desc), "s"(sl_k0), "s"(sl_fp), "s"(CLS ? (const void *) st.toff : (const void *) st.data), "s"(st.tab), "s"(p.Ai) : "memory");
 #pragma unroll
    for (int j = 0; j < XS_WSEG; j++)
    {
@@ -1448,6 +1531,7 @@ void spmv_sl_kernel(SpmvArgs p, const int *__restrict__ sl_cnt, const int *__res
                                           (__attribute__((address_space(3))) void *) (reinterpret_cast<char *>(xs) + offb), 16, 0, 0);
       }
    }
+   sl_lane_stage<CLS, KP>(me, st, wave, lane, tabl);
    {
       const int dl = (p.ndict + 1) >> 1;
       if (lane < dl - 64 * wave)
@@ -1467,13 +1551,13 @@ void spmv_sl_kernel(SpmvArgs p, const int *__restrict__ sl_cnt, const int *__res
    const unsigned ckc = p.Ac8[ck];
    __syncthreads();
 
-   const int mylen = (re - rs - sub + W - 1) / W;
+   const int mylen = sl_lane_words<CLS, W, KP>(me, tid, tabl);
    double sum = 0.0;
 #pragma unroll
    for (int j = 0; j < KP; j++)
    {
-      const unsigned code = (cw[j >> 2] >> (8 * (j & 3))) & 0xffu;
-      const unsigned li = (lw[j >> 1] >> (16 * (j & 1))) & 0xffffu;
+      const unsigned code = (me.cw[j >> 2] >> (8 * (j & 3))) & 0xffu;
+      const unsigned li = (me.lw[j >> 1] >> (16 * (j & 1))) & 0xffffu;
       {
 #pragma clang fp contract(off)                                  // no fused multiply-add: the tiled kernel rounds every product
          const double pr = dictl[code] * xs[li];
@@ -1483,25 +1567,44 @@ void spmv_sl_kernel(SpmvArgs p, const int *__restrict__ sl_cnt, const int *__res
    if (W == 2) { sum += __shfl_xor(sum, 1, 64); }
    {
       bool off = __double_as_longlong(dictl[ckc]) != __double_as_longlong(p.dict_rounded ? (double) (float) ckv : ckv);
-      if (tid == 0) { off = off || fp_plan != (int) ((unsigned) fc0 * 2654435761u + (unsigned) fc1) || rs != k0; }
+      if (tid == 0) { off = off || fp_plan != (int) ((unsigned) fc0 * 2654435761u + (unsigned) fc1) || me.rs != k0; }
       if (off) { __hip_atomic_fetch_or(p.stale, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
    }
    if (r < num_rows && sub == 0) { row_epilogue<OP>(p, r, sum, ops); }
+}
+template <int OP, int W, int KP>
+__global__ __launch_bounds__(SPMV_THREADS)
+void spmv_sl_kernel(SpmvArgs p, const int *__restrict__ sl_cnt, const int *__restrict__ sl_desc, const int *__restrict__ sl_k0,
+                    const int *__restrict__ sl_fp, const int *__restrict__ sl_perm, const unsigned *__restrict__ sl_data,
+                    int blocks, int num_rows, int nnz, int stage_elems)
+{
+   const SlStream st = {sl_data, nullptr, nullptr, nullptr};
+   spmv_sl_body<OP, W, KP, false>(p, sl_desc, sl_k0, sl_fp, sl_perm, st, blocks, num_rows, nnz, stage_elems);
+}
+// the same with the lanes' words named by class bytes (SlStream)
+template <int OP, int W, int KP>
+__global__ __launch_bounds__(SPMV_THREADS)
+void spmv_sl_kernel_cls(SpmvArgs p, const int *__restrict__ sl_desc, const int *__restrict__ sl_k0, const int *__restrict__ sl_fp,
+                        const int *__restrict__ sl_perm, const unsigned char *__restrict__ sl_cls, const unsigned *__restrict__ sl_tab,
+                        const int *__restrict__ sl_toff, int blocks, int num_rows, int nnz, int stage_elems)
+{
+   const SlStream st = {nullptr, sl_cls, sl_tab, sl_toff};
+   spmv_sl_body<OP, W, KP, true>(p, sl_desc, sl_k0, sl_fp, sl_perm, st, blocks, num_rows, nnz, stage_elems);
 }
 
 // The slice form with a multivector: a lane's codes and local indices are in registers, so the columns cost their x pieces
 // (NV staged copies), NV reads per entry and NV sums — the matrix words are read once.  Same bits as spmv_sl_kernel column
 // by column (and so as every other form).  y = alpha A x + beta b only.
-template <int NV, int W, int KP>
-__global__ __launch_bounds__(SPMV_THREADS)
-void spmv_sl_mv_kernel(SpmvArgs p, const int *__restrict__ sl_desc, const int *__restrict__ sl_k0,
-                       const int *__restrict__ sl_fp, const int *__restrict__ sl_perm, const unsigned *__restrict__ sl_data,
-                       int blocks, int num_rows, int nnz, int stage_elems, long xstride, long bstride, long ystride)
+template <int NV, int W, int KP, bool CLS>
+__device__ __forceinline__
+void spmv_sl_mv_body(const SpmvArgs &p, const int *__restrict__ sl_desc, const int *__restrict__ sl_k0,
+                     const int *__restrict__ sl_fp, const int *__restrict__ sl_perm, const SlStream &st,
+                     int blocks, int num_rows, int nnz, int stage_elems, long xstride, long bstride, long ystride)
 {
-   constexpr int wc = KP / 4, wl = KP / 2;
    extern __shared__ __align__(16) unsigned char smem_raw[];
    double *xs = reinterpret_cast<double *>(smem_raw);
    const double *dictl = xs + (size_t) NV * stage_elems;
+   unsigned *tabl = reinterpret_cast<unsigned *>(xs + (size_t) NV * stage_elems + ((p.ndict + 1) & ~1));
 
    int block = (int) blockIdx.x;
    if (sl_perm)
@@ -1515,14 +1618,9 @@ void spmv_sl_mv_kernel(SpmvArgs p, const int *__restrict__ sl_desc, const int *_
    const int tid = threadIdx.x, lane = tid & 63;
    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
    constexpr int R = SPMV_THREADS / W;
-   const unsigned *sd = sl_data + ((size_t) (block * 4 + wave) * (size_t) (wc + wl)) * 64 + lane;
-   unsigned cw[wc], lw[wl];
-#pragma unroll
-   for (int w = 0; w < wc; w++) { cw[w] = sd[w * 64]; }
-#pragma unroll
-   for (int w = 0; w < wl; w++) { lw[w] = sd[(wc + w) * 64]; }
    const int r = block * R + tid / W, sub = tid % W;
-   const int rs = p.Ai[min(r, num_rows)], re = p.Ai[min(r + 1, num_rows)];
+   SlLane<CLS, KP> me;
+   sl_lane_load<CLS, W, KP>(me, st, p.Ai, block, wave, lane, tid, r, num_rows);
    const int rc = max(min(r, num_rows - 1), 0);
    double bv[NV];
 #pragma unroll
@@ -1537,7 +1635,8 @@ void spmv_sl_mv_kernel(SpmvArgs p, const int *__restrict__ sl_desc, const int *_
 #pragma unroll
    for (int j = 0; j < XS_WSEG; j++) { seg_start[j] = dsc[j]; seg_ol[j] = dsc[XS_SEGS + j]; }
    const int k0 = sl_k0[block], k1b = sl_k0[block + 1], fp_plan = sl_fp[block];
-   asm volatile("" :: "s"(sl_desc), "s"(sl_k0), "s"(sl_fp), "s"(sl_data), "s"(p.Ai) : "memory");
+   asm volatile("" :: "s"(sl_desc), "s"(sl_k0), "s"(sl_fp), "s"(CLS ? (const void *) st.toff : (const void *) st.data), "s"(st.tab), "s"(p.Ai) : "memory");
+   sl_lane_stage<CLS, KP>(me, st, wave, lane, tabl);
 #pragma unroll
    for (int v = 0; v < NV; v++)
    {
@@ -1568,15 +1667,15 @@ void spmv_sl_mv_kernel(SpmvArgs p, const int *__restrict__ sl_desc, const int *_
    const unsigned ckc = p.Ac8[ck];
    __syncthreads();
 
-   const int mylen = (re - rs - sub + W - 1) / W;
+   const int mylen = sl_lane_words<CLS, W, KP>(me, tid, tabl);
    double sum[NV];
 #pragma unroll
    for (int v = 0; v < NV; v++) { sum[v] = 0.0; }
 #pragma unroll
    for (int j = 0; j < KP; j++)
    {
-      const unsigned code = (cw[j >> 2] >> (8 * (j & 3))) & 0xffu;
-      const unsigned li = (lw[j >> 1] >> (16 * (j & 1))) & 0xffffu;
+      const unsigned code = (me.cw[j >> 2] >> (8 * (j & 3))) & 0xffu;
+      const unsigned li = (me.lw[j >> 1] >> (16 * (j & 1))) & 0xffffu;
       const double a = dictl[code];
 #pragma unroll
       for (int v = 0; v < NV; v++)
@@ -1593,7 +1692,7 @@ void spmv_sl_mv_kernel(SpmvArgs p, const int *__restrict__ sl_desc, const int *_
    }
    {
       bool off = __double_as_longlong(dictl[ckc]) != __double_as_longlong(ckv);
-      if (tid == 0) { off = off || fp_plan != (int) ((unsigned) fc0 * 2654435761u + (unsigned) fc1) || rs != k0; }
+      if (tid == 0) { off = off || fp_plan != (int) ((unsigned) fc0 * 2654435761u + (unsigned) fc1) || me.rs != k0; }
       if (off) { __hip_atomic_fetch_or(p.stale, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
    }
    if (r < num_rows && sub == 0)
@@ -1606,6 +1705,25 @@ void spmv_sl_mv_kernel(SpmvArgs p, const int *__restrict__ sl_desc, const int *_
          p.y[(size_t) v * ystride + r] = t;
       }
    }
+}
+template <int NV, int W, int KP>
+__global__ __launch_bounds__(SPMV_THREADS)
+void spmv_sl_mv_kernel(SpmvArgs p, const int *__restrict__ sl_desc, const int *__restrict__ sl_k0,
+                       const int *__restrict__ sl_fp, const int *__restrict__ sl_perm, const unsigned *__restrict__ sl_data,
+                       int blocks, int num_rows, int nnz, int stage_elems, long xstride, long bstride, long ystride)
+{
+   const SlStream st = {sl_data, nullptr, nullptr, nullptr};
+   spmv_sl_mv_body<NV, W, KP, false>(p, sl_desc, sl_k0, sl_fp, sl_perm, st, blocks, num_rows, nnz, stage_elems, xstride, bstride, ystride);
+}
+template <int NV, int W, int KP>
+__global__ __launch_bounds__(SPMV_THREADS)
+void spmv_sl_mv_kernel_cls(SpmvArgs p, const int *__restrict__ sl_desc, const int *__restrict__ sl_k0, const int *__restrict__ sl_fp,
+                           const int *__restrict__ sl_perm, const unsigned char *__restrict__ sl_cls, const unsigned *__restrict__ sl_tab,
+                           const int *__restrict__ sl_toff, int blocks, int num_rows, int nnz, int stage_elems, long xstride, long bstride,
+                           long ystride)
+{
+   const SlStream st = {nullptr, sl_cls, sl_tab, sl_toff};
+   spmv_sl_mv_body<NV, W, KP, true>(p, sl_desc, sl_k0, sl_fp, sl_perm, st, blocks, num_rows, nnz, stage_elems, xstride, bstride, ystride);
 }
 
 // ---- slice form construction
@@ -1651,6 +1769,140 @@ void sl_pack_kernel(const int *__restrict__ Ai, const unsigned char *__restrict_
       }
       out[(wc + w) * 64] = word;
    }
+}
+
+// ---- classes of the slice form (SlStream): built from the packed words, which are the ground truth.
+// A lane's tuple: the entries it holds, its code words, its index words less its lane-row t in both 16-bit halves (modulo
+// 2^16; halves of entries it does not hold are zero, so that padding cannot split classes), zero up to kper words.
+constexpr int SL_CLASS_CAP = 255;            // a class is named by a byte
+// doubles of the staged copy of x a slice launch reserves; with classes at least 256 (the index halves of entries a lane does
+// not hold read its lane-row: inside the copy, the product dropped).  Shared by the launch and by the builder's LDS test.
+static inline int sl_stage_elems_of(int units, bool classes) { return classes ? std::max(2 * units + 8, SPMV_THREADS) : 2 * units + 8; }
+template <int W>
+__device__ inline void sl_lane_tuple(const int *__restrict__ Ai, const unsigned *__restrict__ data, int num_rows, int wc, int wl,
+                                     int block, int tid, unsigned *tup)
+{
+   constexpr int R = SPMV_THREADS / W;
+   const int lane = tid & 63, wave = tid >> 6, t = tid / W, sub = tid % W;
+   const int r = block * R + t;
+   const int rs = r < num_rows ? Ai[r] : 0, re = r < num_rows ? Ai[r + 1] : 0;
+   const int mylen = max((re - rs - sub + W - 1) / W, 0);
+   const unsigned *sd = data + ((size_t) (block * 4 + wave) * (size_t) (wc + wl)) * 64 + lane;
+   tup[0] = (unsigned) mylen;
+   for (int w = 0; w < wc; w++) { tup[1 + w] = sd[w * 64]; }
+   for (int w = 0; w < wl; w++)
+   {
+      const unsigned v = sd[(wc + w) * 64];
+      const unsigned lo = 2 * w < mylen ? ((v & 0xffffu) - (unsigned) t) & 0xffffu : 0u;
+      const unsigned hi = 2 * w + 1 < mylen ? ((v >> 16) - (unsigned) t) & 0xffffu : 0u;
+      tup[1 + wc + w] = lo | (hi << 16);
+   }
+   for (int w = 1 + wc + wl; w < 16; w++) { tup[w] = 0u; }
+}
+// One workgroup per block.  Round c: the first lane without a class leads class c, every lane whose tuple equals the leader's
+// joins it — classes are numbered in order of first appearance.  ncls[block]: the count, SL_CLASS_CAP + 1 when it exceeds the cap.
+template <int W>
+__global__ __launch_bounds__(SPMV_THREADS)
+void sl_classify_kernel(const int *__restrict__ Ai, const unsigned *__restrict__ data, int num_rows, int wc, int wl,
+                        unsigned char *__restrict__ cls, int *__restrict__ ncls)
+{
+   __shared__ unsigned tupS[SPMV_THREADS][17];
+   __shared__ int leader;
+   const int block = blockIdx.x, tid = threadIdx.x;
+   unsigned tup[16];
+   sl_lane_tuple<W>(Ai, data, num_rows, wc, wl, block, tid, tup);
+   for (int w = 0; w < 16; w++) { tupS[tid][w] = tup[w]; }
+   int mine = -1, round = 0;
+   while (true)
+   {
+      if (tid == 0) { leader = SPMV_THREADS; }
+      __syncthreads();
+      if (mine < 0) { atomicMin(&leader, tid); }
+      __syncthreads();
+      const int L = leader;
+      if (L == SPMV_THREADS || round == SL_CLASS_CAP) { if (L != SPMV_THREADS) { round = SL_CLASS_CAP + 1; } break; }
+      if (mine < 0)
+      {
+         bool eq = true;
+         for (int w = 0; w < 16; w++) { eq = eq && tupS[L][w] == tup[w]; }
+         if (eq) { mine = round; }
+      }
+      round++;
+      __syncthreads();
+   }
+   cls[(size_t) block * SPMV_THREADS + tid] = (unsigned char) max(mine, 0);
+   if (tid == 0) { ncls[block] = round; }
+}
+// the tables: the first lane of every class writes its tuple (kper words) at the class's place
+template <int W>
+__global__ __launch_bounds__(SPMV_THREADS)
+void sl_class_table_kernel(const int *__restrict__ Ai, const unsigned *__restrict__ data, int num_rows, int wc, int wl, int kper,
+                           const unsigned char *__restrict__ cls, const int *__restrict__ toff, unsigned *__restrict__ tab)
+{
+   __shared__ int first[256];
+   const int block = blockIdx.x, tid = threadIdx.x;
+   first[tid] = SPMV_THREADS;
+   __syncthreads();
+   const int c = cls[(size_t) block * SPMV_THREADS + tid];
+   atomicMin(&first[c], tid);
+   __syncthreads();
+   if (first[c] != tid) { return; }
+   unsigned tup[16];
+   sl_lane_tuple<W>(Ai, data, num_rows, wc, wl, block, tid, tup);
+   unsigned *out = tab + ((size_t) toff[block] + (size_t) c) * (size_t) kper;
+   for (int w = 0; w < kper; w++) { out[w] = tup[w]; }
+}
+static_assert(SPMV_THREADS == 256, "a class byte per lane of a 256-lane block; sl_class_table_kernel's first[]");
+
+// Adopt the class storage for a slice form just built (p->d_sl_data holds the packed words): false — the matrix keeps the
+// packed stream — when a block has more classes than a byte names, when the largest table does not fit the launch's LDS
+// beside the staged copy, when the class form is not at most half the packed one, or when a table is not to be had.
+static bool device_build_slice_classes(SpmvPlan *p, const hypre_CSRMatrix *A, hipStream_t s)
+{
+   const int blocks = p->sl_blocks, kper = p->sl_k, wc = p->sl_wc, wl = p->sl_wl, n = A->num_rows;
+   unsigned char *d_cls = nullptr;
+   int *d_ncls = nullptr, *d_toff = nullptr;
+   unsigned *d_tab = nullptr;
+   auto fail = [&]() -> bool
+   {
+      HIP_CHECK(hipStreamSynchronize(s));
+      for (void *q : {(void *) d_cls, (void *) d_ncls, (void *) d_toff, (void *) d_tab}) { plan_free(q); }
+      return false;
+   };
+   if (!plan_alloc((void **) &d_cls, (size_t) blocks * SPMV_THREADS, PLAN_SITE_SLICE_CLASSES) ||
+       !plan_alloc((void **) &d_ncls, sizeof(int) * (size_t) blocks, PLAN_SITE_SLICE_CLASSES) ||
+       !plan_alloc((void **) &d_toff, sizeof(int) * ((size_t) blocks + 1), PLAN_SITE_SLICE_CLASSES)) { return fail(); }
+   if (p->sl_w == 1) { hipLaunchKernelGGL((sl_classify_kernel<1>), dim3(blocks), dim3(SPMV_THREADS), 0, s, A->i, p->d_sl_data, n, wc, wl, d_cls, d_ncls); }
+   else              { hipLaunchKernelGGL((sl_classify_kernel<2>), dim3(blocks), dim3(SPMV_THREADS), 0, s, A->i, p->d_sl_data, n, wc, wl, d_cls, d_ncls); }
+   std::vector<int> ncls((size_t) blocks), toff((size_t) blocks + 1, 0);
+   HIP_CHECK(hipMemcpyAsync(ncls.data(), d_ncls, sizeof(int) * (size_t) blocks, hipMemcpyDeviceToHost, s));
+   HIP_CHECK(hipStreamSynchronize(s));
+   int most = 0;
+   long long total = 0;
+   for (int b = 0; b < blocks; b++)
+   {
+      most = std::max(most, ncls[(size_t) b]);
+      total += ncls[(size_t) b];
+      if (total > 0x7fffffffLL / 16) { return fail(); }
+      toff[(size_t) b + 1] = (int) total;
+   }
+   if (most < 1 || most > SL_CLASS_CAP) { return fail(); }
+   // LDS of a launch: the staged copy (at least 256 doubles in this mode), the value table, the largest class table
+   if (8 * ((size_t) sl_stage_elems_of(p->sl_launch_units, true) + DICT_CAP) + 4 * (size_t) most * kper > 40 * 1024) { return fail(); }
+   const double packed_bytes = 4.0 * (double) blocks * 4.0 * (wc + wl) * 64.0;
+   const double class_bytes = (double) blocks * SPMV_THREADS + 4.0 * (double) total * kper + 4.0 * ((double) blocks + 1.0);
+   if (class_bytes > 0.5 * packed_bytes) { return fail(); }
+   if (!plan_alloc((void **) &d_tab, sizeof(unsigned) * (size_t) total * (size_t) kper, PLAN_SITE_SLICE_CLASSES)) { return fail(); }
+   HIP_CHECK(hipMemcpyAsync(d_toff, toff.data(), sizeof(int) * ((size_t) blocks + 1), hipMemcpyHostToDevice, s));
+   if (p->sl_w == 1) { hipLaunchKernelGGL((sl_class_table_kernel<1>), dim3(blocks), dim3(SPMV_THREADS), 0, s, A->i, p->d_sl_data, n, wc, wl, kper, d_cls, d_toff, d_tab); }
+   else              { hipLaunchKernelGGL((sl_class_table_kernel<2>), dim3(blocks), dim3(SPMV_THREADS), 0, s, A->i, p->d_sl_data, n, wc, wl, kper, d_cls, d_toff, d_tab); }
+   HIP_CHECK(hipStreamSynchronize(s));
+   plan_free(d_ncls);
+   plan_free(p->d_sl_data);
+   p->d_sl_data = nullptr;
+   p->d_sl_cls = d_cls; p->d_sl_tab = d_tab; p->d_sl_toff = d_toff;
+   p->sl_classes = most; p->sl_class_total = total;
+   return true;
 }
 
 bool device_build_slice_form(SpmvPlan *p, const hypre_CSRMatrix *A, hipStream_t s)
@@ -1723,6 +1975,7 @@ bool device_build_slice_form(SpmvPlan *p, const hypre_CSRMatrix *A, hipStream_t 
    p->sl_w = W; p->sl_rows = R; p->sl_k = kper; p->sl_wc = wc; p->sl_wl = wl;
    p->sl_blocks = blocks; p->sl_launch_units = units;
    p->d_sl_cnt = d_cnt; p->d_sl_desc = d_desc; p->d_sl_k0 = d_k0; p->d_sl_fp = d_fp; p->d_sl_perm = d_perm; p->d_sl_data = d_data;
+   if (spmv_slice_classes()) { (void) device_build_slice_classes(p, A, s); }      // one byte per lane-row where the blocks repeat themselves
    return true;
 }
 
@@ -2386,12 +2639,31 @@ static void launch_xs(const SpmvPlan *plan, const SpmvArgs &a, hipStream_t s)
                       plan->num_tiles, plan->prod_elems, rowsum_elems, rp_cap, plan->xs_launch_units);
 }
 
+static inline int sl_stage_elems(const SpmvPlan *plan) { return sl_stage_elems_of(plan->sl_launch_units, plan->d_sl_cls != nullptr); }
+// bytes of the largest class table of the matrix (0: packed stream)
+static inline size_t sl_table_bytes(const SpmvPlan *plan) { return plan->d_sl_cls ? sizeof(unsigned) * (size_t) plan->sl_classes * plan->sl_k : 0; }
+// What a slice launch reads of the matrix (hypre_amd_ByteCounters, streamed): per block the descriptors and k0 / fingerprint
+// words, the value table, the rotating value check; the packed words and a row pointer per row — or a class byte per lane,
+// the class tables, two table offsets and one row pointer per block
+static inline double sl_matrix_bytes(const SpmvPlan *plan, int ndict)
+{
+   const double blocks = (double) plan->sl_blocks, per_block = 4.0 * (XS_DESC + 4) + 8.0 * ndict + 4.0 * 72.0;
+   if (plan->d_sl_cls) { return blocks * (per_block + (double) SPMV_THREADS + 4.0 * 3.0) + 4.0 * (double) plan->sl_class_total * plan->sl_k; }
+   return blocks * (per_block + (double) SPMV_THREADS * plan->sl_k * 3.0) + 4.0 * ((double) plan->num_rows + 1.0);
+}
+
 template <int OP, int W, int KP>
 static void launch_sl_form(const SpmvPlan *plan, const SpmvArgs &a, hipStream_t s)
 {
-   const int stage_elems = 2 * plan->sl_launch_units + 8;
-   const size_t lds = sizeof(double) * (size_t) (stage_elems + ((a.ndict + 1) & ~1));
+   const int stage_elems = sl_stage_elems(plan);
+   const size_t lds = sizeof(double) * (size_t) (stage_elems + ((a.ndict + 1) & ~1)) + sl_table_bytes(plan);
    const int grid = plan->d_sl_perm ? plan->sl_blocks : ((plan->sl_blocks + 63) / 64) * 64;
+   if (plan->d_sl_cls)
+   {
+      hipLaunchKernelGGL((spmv_sl_kernel_cls<OP, W, KP>), dim3(grid), dim3(SPMV_THREADS), lds, s, a, plan->d_sl_desc, plan->d_sl_k0, plan->d_sl_fp,
+                         plan->d_sl_perm, plan->d_sl_cls, plan->d_sl_tab, plan->d_sl_toff, plan->sl_blocks, plan->num_rows, plan->nnz, stage_elems);
+      return;
+   }
    hipLaunchKernelGGL((spmv_sl_kernel<OP, W, KP>), dim3(grid), dim3(SPMV_THREADS), lds, s, a, plan->d_sl_cnt, plan->d_sl_desc, plan->d_sl_k0,
                       plan->d_sl_fp, plan->d_sl_perm, plan->d_sl_data, plan->sl_blocks, plan->num_rows, plan->nnz, stage_elems);
 }
@@ -2443,7 +2715,7 @@ static void launch_tiled(const SpmvPlan *plan, const SpmvArgs &a, hipStream_t s)
    // x staged through LDS (variant 2, the default)
    if (takes_xs(plan, a))
    {
-      if (a.Ac8 && !FILL && plan->d_sl_data) { launch_sl<OP>(plan, a, s); }      // slice form: a lane per row (or half row)
+      if (a.Ac8 && !FILL && plan->has_slice_form()) { launch_sl<OP>(plan, a, s); }      // slice form: a lane per row (or half row)
       else if (a.Ac8) { launch_xs<OP, VF_CODE, FILL>(plan, a, s); }
       else { launch_xs<OP, F32 ? VF_F32 : VF_F64, FILL>(plan, a, s); }
       return;
@@ -2547,7 +2819,7 @@ void launch_spmv(const SpmvPlan *plan, const SpmvArgs &args, SpmvOp op, hipStrea
       // what the format of the kernel that serves this launch requires: the matrix stream, the per-tile (per-block) tables
       // — bounds, piece descriptors, fingerprint —, the value table and the rotating value check of a coded matrix
       const bool staged = takes_xs(plan, a);
-      const bool slice = staged && a.Ac8 && a.fill == HYPRE_SPMV_FILL_WHOLE && plan->d_sl_data != nullptr;
+      const bool slice = staged && a.Ac8 && a.fill == HYPRE_SPMV_FILL_WHOLE && plan->has_slice_form();
       double streamed;
       if (a.use_rs)
       {
@@ -2556,7 +2828,7 @@ void launch_spmv(const SpmvPlan *plan, const SpmvArgs &args, SpmvOp op, hipStrea
       }
       else if (slice)
       {
-         streamed = (double) plan->sl_blocks * ((double) SPMV_THREADS * plan->sl_k * 3.0 + 4.0 * (XS_DESC + 4) + 8.0 * a.ndict + 4.0 * 72.0) + rows_b;
+         streamed = sl_matrix_bytes(plan, a.ndict) + rowb * nr + xcols;
       }
       else if (staged)
       {
@@ -2613,6 +2885,20 @@ static void launch_sl_mv(const SpmvPlan *plan, const SpmvArgs &a, int stage_elem
       raised = true;
    }
    const int grid = plan->d_sl_perm ? plan->sl_blocks : ((plan->sl_blocks + 63) / 64) * 64;
+   if (plan->d_sl_cls)
+   {
+      static bool raised_cls = false;
+      if (!raised_cls)
+      {
+         (void) hipFuncSetAttribute((const void *) (spmv_sl_mv_kernel_cls<NV, W, KP>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+         (void) hipGetLastError();
+         raised_cls = true;
+      }
+      hipLaunchKernelGGL((spmv_sl_mv_kernel_cls<NV, W, KP>), dim3(grid), dim3(SPMV_THREADS), lds, s, a, plan->d_sl_desc, plan->d_sl_k0, plan->d_sl_fp,
+                         plan->d_sl_perm, plan->d_sl_cls, plan->d_sl_tab, plan->d_sl_toff, plan->sl_blocks, plan->num_rows, plan->nnz, stage_elems,
+                         xstride, bstride, ystride);
+      return;
+   }
    hipLaunchKernelGGL((spmv_sl_mv_kernel<NV, W, KP>), dim3(grid), dim3(SPMV_THREADS), lds, s, a, plan->d_sl_desc, plan->d_sl_k0,
                       plan->d_sl_fp, plan->d_sl_perm, plan->d_sl_data, plan->sl_blocks, plan->num_rows, plan->nnz, stage_elems, xstride, bstride, ystride);
 }
@@ -2625,8 +2911,8 @@ static void launch_sl_mv_nv(const SpmvPlan *plan, const SpmvArgs &a, int stage_e
 }
 static inline size_t sl_mv_lds_bytes(const SpmvPlan *plan, int nv, int ndict, int &stage_elems)
 {
-   stage_elems = 2 * plan->sl_launch_units + 8;
-   return sizeof(double) * ((size_t) nv * stage_elems + (size_t) ((ndict + 1) & ~1));
+   stage_elems = sl_stage_elems(plan);
+   return sizeof(double) * ((size_t) nv * stage_elems + (size_t) ((ndict + 1) & ~1)) + sl_table_bytes(plan);
 }
 
 constexpr int MV_WIN = 2320;        // SPMV_TILE + SPMV_THREADS entries of a window and its spill, a multiple of 16
@@ -2667,7 +2953,7 @@ bool launch_spmv_mv(const SpmvPlan *plan, const SpmvArgs &args, int nv, long xst
    const double vecs = (8.0 + ((a.beta != 0.0) ? 8.0 : 0.0)) * nr + 8.0 * std::min((double) plan->num_cols, nz);     // per column: y (+ b), x
    for (int v0 = 0; v0 < nv; )
    {
-      const bool slice = coded && plan->d_sl_data != nullptr;      // a lane per row (or half row), the matrix words in registers
+      const bool slice = coded && plan->has_slice_form();          // a lane per row (or half row), the matrix words in registers
       // columns per pass: four over the tiles (the matrix stream is what the pass saves); the slice form's matrix words are
       // few, its passes are bound by the x pieces, and a fourth staged copy costs a resident workgroup per CU: threes and twos
       // (measured per column on the 256^3 7-point operator: 0.108 / 0.104 / 0.118 ms at 2 / 3 / 4 columns, 0.150 alone)
@@ -2688,8 +2974,7 @@ bool launch_spmv_mv(const SpmvPlan *plan, const SpmvArgs &args, int nv, long xst
       if (slice)
       {
          account_bytes(nz * 12.0 + 4.0 * (nr + 1.0) + g * vecs,
-                       (double) plan->sl_blocks * ((double) SPMV_THREADS * plan->sl_k * 3.0 + 4.0 * (XS_DESC + 4) + 8.0 * a.ndict + 4.0 * 72.0) +
-                       4.0 * (nr + 1.0) + g * vecs);
+                       sl_matrix_bytes(plan, a.ndict) + g * vecs);
          switch (g)
          {
             case 2:  launch_sl_mv_nv<2>(plan, c, stage_elems, lds, xstride, bstride, ystride, s); break;

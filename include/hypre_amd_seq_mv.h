@@ -163,7 +163,7 @@ HYPRE_Int hypre_amd_SetMixedPrecisionValues(HYPRE_Int on);
  * form; -1: not a device matrix. */
 HYPRE_Int hypre_amd_CSRMatrixPlanForm(hypre_CSRMatrix *A);
 /* Test hook: the nth allocation (1 = the next one) a plan builder makes at `site` fails, once — 1 tile tables, 2 x-staging
- * tables, 3 value codes, 4 slice form, 5 row-slice form; nth <= 0 disarms.  A plan is an accelerator: the builder frees
+ * tables, 3 value codes, 4 slice form, 5 row-slice form, 6 class storage of the slice form; nth <= 0 disarms.  The builder frees
  * what the step had obtained, leaves no error behind and the matrix is multiplied one form lower.  Returns what was still
  * pending of the request before (0: that failure happened, or nothing was armed). */
 HYPRE_Int hypre_amd_PlanTestFailAlloc(HYPRE_Int site, HYPRE_Int nth);
@@ -195,6 +195,13 @@ HYPRE_Int hypre_amd_SpmvSetValueCodes(HYPRE_Int on);
  * kernel does where a tile holds 65 to 128 rows), within an ulp or two of the row's absolute sum.  On by default (environment:
  * HYPRE_AMD_SPMV_SLICE_FORM=0); on < 0: unchanged; takes effect for plans built afterwards. */
 HYPRE_Int hypre_amd_SpmvSetSliceForm(HYPRE_Int on);
+/* Class storage of the slice form (speed only; no reference counterpart): inside a block of 256 lanes a stencil's packed words
+ * repeat — lane-row t holds the words of one of a few classes with t added to every local index — so a lane streams one byte
+ * that names its class and the block's table of classes rides into LDS with the x pieces; the lane rebuilds the very words of
+ * the packed stream and runs the same sum: the same bits.  Adopted for a whole matrix or not at all: every block within 255
+ * classes, the largest table within the launch's LDS, the class storage at most half the packed words; the packed words are
+ * then freed.  On by default (environment: HYPRE_AMD_SPMV_SLICE_CLASSES=0); on < 0: unchanged; plans built afterwards. */
+HYPRE_Int hypre_amd_SpmvSetSliceClasses(HYPRE_Int on);
 /* Row-slice form (speed only; no reference counterpart — the reference multiplies every matrix with K lanes per row and a
  * shuffle tree, seq_mv/csr_spmv_device.c:149-260): a matrix that cannot change behind its plan (made by the library, or
  * declared by hypre_amd_CSRMatrixSetImmutable) and is not coded is stored in the plan as jagged slices — 256 / W rows per
@@ -216,6 +223,12 @@ HYPRE_Int hypre_amd_SpmvFusedMultivectorLaunches(void);
 HYPRE_Int hypre_amd_CSRMatrixPlanRowSlices(hypre_CSRMatrix *A, HYPRE_Int *rows_per_block, HYPRE_Int *entries_per_lane);
 /* Lanes per row (1 or 2) of the slice form in the plan of the device matrix A; 0 when it has none. */
 HYPRE_Int hypre_amd_CSRMatrixPlanSliceForm(hypre_CSRMatrix *A);
+/* Most classes any block of the slice form in the plan of the device matrix A holds; 0 when the plan streams packed words
+ * (or has no slice form). */
+HYPRE_Int hypre_amd_CSRMatrixPlanSliceClasses(hypre_CSRMatrix *A);
+/* Classes per block of the same plan: hist[c], c = 0 .. 255, = blocks that hold c classes (hist may be NULL); fills the number
+ * of blocks and the classes of all blocks.  Returns the most classes of a block; 0, nothing filled, for packed words. */
+HYPRE_Int hypre_amd_CSRMatrixPlanSliceClassHistogram(hypre_CSRMatrix *A, HYPRE_Int *hist, HYPRE_Int *blocks, HYPRE_BigInt *total);
 /* Number of distinct values in the value table of the plan of the device matrix A; 0 when A is not coded. */
 HYPRE_Int hypre_amd_CSRMatrixPlanValueCodes(hypre_CSRMatrix *A);
 /* x staging of the plan of the device matrix A: returns the number of tiles that take the LDS-staged path of the tiled

@@ -1,5 +1,7 @@
-"""A/B of the V(1,1) cycle with and without the row-slice form (or the cycle's fusions: --toggle fusion; or the one-workgroup tail: --toggle smalltail) in ONE process on ONE box (the HBM-bound launches move by
-4-7 % from box to box and drift with the clocks inside a run: the two forms are measured alternately, four times each).
+"""A/B of the V(1,1) cycle with one switch on and off in ONE process on ONE box: the row-slice form (default), the
+cycle's fusions (--toggle fusion), the one-workgroup tail (--toggle smalltail) or the class storage of the slice form
+(--toggle classes).  The HBM-bound launches move by 4-7 % from box to box and drift with the clocks inside a run: the
+two settings are measured alternately, four times each.
 
     python tools/ab_row_slices.py [n] [cycles] [--problem laplacian|27pt|difconv] [--relax 18]
 """
@@ -20,7 +22,7 @@ ap.add_argument("cycles", type=int, nargs="?", default=30)
 ap.add_argument("--problem", default="laplacian")
 ap.add_argument("--relax", type=int, default=18)
 ap.add_argument("--codes", type=int, default=1)
-ap.add_argument("--toggle", default="rowslices", choices=["rowslices", "fusion", "smalltail"], help="what is switched between the two samples")
+ap.add_argument("--toggle", default="rowslices", choices=["rowslices", "fusion", "smalltail", "classes"], help="what is switched between the two samples")
 args = ap.parse_args()
 L = B.load_library()
 n = args.n
@@ -37,6 +39,10 @@ for rep in range(4):
             L.hypre_amd_SpmvSetRowSlices(mode)
         elif args.toggle == "smalltail":
             L.hypre_amd_SetSmallTail(mode)
+        elif args.toggle == "classes":
+            # class bytes instead of packed words in the slice form: the fine-level plan is rebuilt under the switch
+            L.hypre_amd_SpmvSetSliceClasses(mode)
+            L.hypre_amd_CSRMatrixInvalidatePlan(A.contents.diag)
         else:
             L.hypre_amd_SetCycleFusion(mode)
         s = ij.create_amg(opt, memory_location=B.HYPRE_MEMORY_DEVICE)
