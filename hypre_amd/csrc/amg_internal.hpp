@@ -75,6 +75,17 @@ struct AmgPrivate
    hypre_ParVector *mv_resid = nullptr;
    int              mv_resid_cols = 0;
 
+   // Level vectors of NV columns for the fused levels 0 .. mv_first - 1 of a multi-column cycle (par_solve.cpp:
+   // amg_cycle_columns) and the hand-over level mv_first: right-hand side, iterate (home and second buffer) and one residual
+   // scratch, columns one after the other with an even stride.  Level 0 holds a second buffer only (f and u are the caller's),
+   // level mv_first no second buffer.  Checked allocations (plan_alloc): a failure leaves nothing behind and the solve takes
+   // the column loop.
+   struct MvLevel { double *f = nullptr, *home = nullptr, *alt = nullptr; size_t stride = 0; int n = 0; };
+   std::vector<MvLevel> mv_lev;
+   double *mv_vtemp = nullptr;
+   int     mv_cols = 0, mv_first = -1;
+   void release_mv_levels();
+
    // Coarse tail of a single-rank V-cycle as one HIP graph.  From level graph_level down and back up every kernel is a
    // few microseconds of work behind a launch that costs as much; the sub-cycle reads F[graph_level], writes U[graph_level]
    // and touches only buffers the hierarchy owns, so its launches are recorded once (on the second cycle: the first one

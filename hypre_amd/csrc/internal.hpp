@@ -210,7 +210,8 @@ bool is_owned(const hypre_CSRMatrix *A);
 bool plan_verify(hypre_CSRMatrix *A);
 // checked device allocation of the plan builders (seq_mv.cpp): false — nothing allocated, no HIP error left behind — when the
 // memory is not to be had, when the request exceeds half of what is free, or when a test armed this site
-enum PlanAllocSite { PLAN_SITE_TILES = 1, PLAN_SITE_XS = 2, PLAN_SITE_CODES = 3, PLAN_SITE_SLICE = 4, PLAN_SITE_ROWSLICE = 5, PLAN_SITE_SLICE_CLASSES = 6 };
+enum PlanAllocSite { PLAN_SITE_TILES = 1, PLAN_SITE_XS = 2, PLAN_SITE_CODES = 3, PLAN_SITE_SLICE = 4, PLAN_SITE_ROWSLICE = 5, PLAN_SITE_SLICE_CLASSES = 6,
+                     PLAN_SITE_MV_LEVELS = 7 };
 bool plan_alloc(void **ptr, size_t bytes, int site);
 void plan_free(void *ptr);
 // where a solve begins: the plans of the caller's matrix are verified against its arrays (plan_verify) — a plan that
@@ -306,9 +307,20 @@ void launch_spmv(const SpmvPlan *plan, const SpmvArgs &args, SpmvOp op, hipStrea
 // y = M x and, in the same pass, u = (w y) ./ d  (seq_mv.cpp): the restriction f_c = P^T r fused with the zero-guess Jacobi
 // sweep u_c = w f_c ./ d_c that follows it on the coarse level; false: not served (empty matrix), nothing was launched
 bool spmv_with_scaled_quotient(hypre_CSRMatrix *M, const double *x, double *y, double w, const double *d, double *u);
-// y(:, v) = alpha A x(:, v) + beta b(:, v), v < nv, in one pass over the matrix (columns xstride / bstride / ystride doubles
-// apart); false: not served by this plan or these operands, nothing launched — the caller loops over the columns
-bool launch_spmv_mv(const SpmvPlan *plan, const SpmvArgs &args, int nv, long xstride, long bstride, long ystride, hipStream_t s);
+// One pass over the matrix for the columns v < nv of a multivector (columns xstride / bstride / ystride / auxstride doubles
+// apart, one diagonal for all): op = OP_AXPBY, OP_AXPBY_DIV or OP_JACOBI, by the multivector form of the kernel launch_spmv
+// would pick (row slices, slice form, x-staged tiles), groups of 2 - 4 columns per launch; every column bit for bit its
+// single-vector launch.  false: no multivector form serves this plan or these operands, nothing launched — the caller loops
+// over the columns
+bool launch_spmv_mv(const SpmvPlan *plan, const SpmvArgs &args, SpmvOp op, int nv, long xstride, long bstride, long ystride, long auxstride,
+                    hipStream_t s);
+// the passes of a cycle over nv columns (seq_mv.cpp): the fused launch where it serves, else the single-vector call per column
+void spmv_columns(HYPRE_Complex alpha, hypre_CSRMatrix *A, const double *x, size_t xstride, HYPRE_Complex beta, const double *b,
+                  size_t bstride, double *y, size_t ystride, int nv);
+void spmv_columns_jacobi(hypre_CSRMatrix *A, const double *f, size_t fstride, double w, const double *d, const double *u_in, size_t instride,
+                         double *u_out, size_t outstride, int nv);
+bool spmv_columns_scaled_quotient(hypre_CSRMatrix *M, const double *x, size_t xstride, double *y, size_t ystride, double w, const double *d,
+                                  double *u, size_t ustride, int nv);
 long &spmv_mv_launches();               // fused launches so far (tests)
 bool &spmv_fused_multivectors();       // default on; HYPRE_AMD_SPMV_FUSED_MV=0 / hypre_amd_SpmvSetFusedMultivectors
 void launch_spmv_rownnz(const HYPRE_Int *rownnz, int num_rownnz, const SpmvArgs &args, hipStream_t s);

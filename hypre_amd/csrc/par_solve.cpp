@@ -36,9 +36,18 @@ void AmgPrivate::drop_graph()
    graph_cur.clear();
 }
 
+void AmgPrivate::release_mv_levels()
+{
+   for (MvLevel &m : mv_lev) { plan_free(m.f); plan_free(m.home); plan_free(m.alt); }
+   mv_lev.clear();
+   plan_free(mv_vtemp); mv_vtemp = nullptr;
+   mv_cols = 0; mv_first = -1;
+}
+
 void AmgPrivate::release_device()
 {
    drop_graph();
+   release_mv_levels();
    graph_level = -1;
    for (double *p : u_alt) { if (p) { hypre_Free(p, HYPRE_MEMORY_DEVICE); } }
    u_alt.clear(); u_alt_len.clear();
@@ -690,7 +699,16 @@ HYPRE_Int hypre_amd_SetSmallTailForm(HYPRE_Int form)
    return hypre_error_flag;
 }
 
+// The cycle from level `first` down and back up to it (0: the whole cycle).  first > 0 is the entry of the multi-column driver
+// below: the levels above were cycled for all columns at once, F_array[first] holds the restricted residual of one column
+// and, with first_presmoothed, U_array[first] the sweep from zero the restriction's epilogue wrote; the result is left in
+// U_array[first].  The one-workgroup tail and the recorded graph start where they always do.
+static HYPRE_Int amg_cycle_from(void *amg_vdata, hypre_ParVector **F_array, hypre_ParVector **U_array, int first, int first_presmoothed);
 HYPRE_Int hypre_BoomerAMGCycle(void *amg_vdata, hypre_ParVector **F_array, hypre_ParVector **U_array)
+{
+   return amg_cycle_from(amg_vdata, F_array, U_array, 0, 0);
+}
+static HYPRE_Int amg_cycle_from(void *amg_vdata, hypre_ParVector **F_array, hypre_ParVector **U_array, int first, int first_presmoothed)
 {
    hypre_ParAMGData *d = (hypre_ParAMGData *) amg_vdata;
    AmgPrivate *pv = (AmgPrivate *) d->amd_private;
@@ -726,10 +744,11 @@ HYPRE_Int hypre_BoomerAMGCycle(void *amg_vdata, hypre_ParVector **F_array, hypre
    std::vector<int> lev_counter((size_t) L, 0), zeros((size_t) L, 0);
    // presmoothed[l]: the restriction into level l also wrote the result of the level's first sweep from zero, u = (w f) ./ d
    std::vector<int> presmoothed((size_t) L, 0);
-   zeros[0] = U_array[0]->all_zeros;
-   lev_counter[0] = 1;
+   zeros[(size_t) first] = U_array[first]->all_zeros;
    for (int k = 1; k < L; k++) { lev_counter[(size_t) k] = d->fcycle ? 1 : d->cycle_type; }
-   int fcycle_lev = L - 2, level = 0, cycle_param = 1, err = 0;
+   lev_counter[(size_t) first] = 1;
+   presmoothed[(size_t) first] = first_presmoothed;
+   int fcycle_lev = L - 2, level = first, cycle_param = (first > 0 && first == L - 1) ? 3 : 1, err = 0;
    bool not_finished = true;
    double *vtemp = d->Vtemp->local_vector->data;
    double *ztemp = d->Ztemp->local_vector->data;
@@ -817,7 +836,7 @@ HYPRE_Int hypre_BoomerAMGCycle(void *amg_vdata, hypre_ParVector **F_array, hypre
          pv->graph_sig = sig;
       }
    }
-   bool arrived_down = false, capturing = false;
+   bool arrived_down = first > 0, capturing = false;
    double op_count_at_capture = 0.0, csr_at_capture = 0.0, stream_at_capture = 0.0;
 
    while (not_finished)
@@ -1069,7 +1088,7 @@ HYPRE_Int hypre_BoomerAMGCycle(void *amg_vdata, hypre_ParVector **F_array, hypre
          lev_counter[(size_t) level] = std::max(lev_counter[(size_t) level], (int) d->cycle_type);
          cycle_param = (level == L - 1) ? 3 : 1;
       }
-      else if (level != 0)
+      else if (level != first || (capturing && level == gl))
       {
          if (capturing && level == gl)
          {
@@ -1096,6 +1115,7 @@ HYPRE_Int hypre_BoomerAMGCycle(void *amg_vdata, hypre_ParVector **F_array, hypre
             else { (void) hipGetLastError(); pv->graph_state = 0; err = 1; hypre_error_w_msg(HYPRE_ERROR_GENERIC, "hypre_BoomerAMGCycle: capturing the coarse tail failed"); }
             if (err) { break; }
          }
+         if (level == first) { not_finished = false; continue; }      // (entered at the tail's first level: nothing above it here)
          // ascend: u_f += P u_c, written to whichever buffer lets the
          // post-smoothing sweeps end in the level's home vector
          const int fine = level - 1;
@@ -1137,11 +1157,11 @@ HYPRE_Int hypre_BoomerAMGCycle(void *amg_vdata, hypre_ParVector **F_array, hypre
    }
    else if (gl >= 0 && pv->graph_state == 0 && !err) { pv->graph_state = 1; }      // warmed up: record at the next cycle
    // the caller's vector must hold the result
-   if (lv[0].cur != lv[0].home)
+   if (lv[(size_t) first].cur != lv[(size_t) first].home)
    {
-      launch_copy(lv[0].home, lv[0].cur, (size_t) A[0]->diag->num_rows, s);
+      launch_copy(lv[(size_t) first].home, lv[(size_t) first].cur, (size_t) A[first]->diag->num_rows, s);
    }
-   U_array[0]->all_zeros = 0;
+   U_array[first]->all_zeros = 0;
    d->cycle_op_count = cycle_op_count;
    (void) ztemp;
    handle().fp32_values = saved_fp32;
@@ -1182,6 +1202,221 @@ static std::string multivector_refusal(const hypre_ParAMGData *d)
       return "Requested relaxation type " + std::to_string(t) + " doesn't support multicomponent vectors";
    }
    return "";
+}
+
+// ---------------------------------------------------------------------------
+// The V-cycle over NV columns with the large matrix passes fused: on levels 0 .. K - 1 every pass over an operator — the
+// sweep, the residual, the restriction (with the epilogue that writes the coarse level's sweep from zero), the prolongation,
+// the post-sweep — is one launch for a group of 2 - 4 columns (launch_spmv_mv: the multivector form of the kernel the
+// single-vector pass takes, so every column keeps the single-vector cycle's bits); from level K down and back up to it each
+// column runs the single-column cycle (amg_cycle_from) on the solver's own level vectors: the one-workgroup tail, the
+// recorded graph and the dense solve see what they always see.
+// ---------------------------------------------------------------------------
+extern "C++" {
+namespace {
+int &multivector_cycle()
+{
+   // (off until the fused cycle has been timed against the column loop on a device: DESIGN.md section 4)
+   static int on = [] { const char *e = getenv("HYPRE_AMD_MULTIVECTOR_CYCLE"); return e ? (atoi(e) != 0 ? 1 : 0) : 0; }();
+   return on;
+}
+constexpr int MV_CYCLE_MIN_ROWS = 64;     // levels below this many rows are left to the single-column cycle: nothing to share
+
+// first level of the single-column part, or -1: this solver's cycle is not served (the column loop takes it)
+int multivector_cycle_first(const hypre_ParAMGData *d, const AmgPrivate *pv)
+{
+   const int L = d->num_levels;
+   if (L < 2 || d->cycle_type != 1 || d->fcycle || d->grid_relax_points || d->relax_order != 0 || pv->tail || pv->mixed_precision) { return -1; }
+   HYPRE_Int np = 1;
+   hypre_MPI_Comm_size(d->A_array[0]->comm, &np);
+   if (np != 1) { return -1; }
+   const int t1 = d->grid_relax_type[1], t2 = d->grid_relax_type[2], t3 = d->grid_relax_type[3];
+   if (!(t1 == 7 || t1 == 18) || !(t2 == 7 || t2 == 18) || !is_ge_type(t3)) { return -1; }
+   if (d->num_grid_sweeps[1] < 1 || d->num_grid_sweeps[2] < 1 || d->num_grid_sweeps[1] > 4 || d->num_grid_sweeps[2] > 4) { return -1; }
+   int K = L - 1;
+   for (int l = 1; l < L - 1; l++)
+   {
+      const hypre_CSRMatrix *Al = d->A_array[l]->diag;
+      if (Al->num_rows < MV_CYCLE_MIN_ROWS || (small_tail_on() && pv->small_tail_nnz > 0 && Al->num_nonzeros <= pv->small_tail_nnz) ||
+          (pv->graph_rows > 0 && d->A_array[l]->global_num_rows <= (HYPRE_BigInt) pv->graph_rows)) { K = l; break; }
+   }
+   // never below where the tail kernel or the recorded graph was found to begin
+   if (pv->small_tail_level >= 1) { K = std::min(K, pv->small_tail_level); }
+   if (pv->graph_rows > 0 && pv->graph_level >= 1) { K = std::min(K, pv->graph_level); }
+   for (int l = 0; l < K; l++)
+   {
+      const hypre_ParCSRMatrix *Al = d->A_array[l], *Pl = d->P_array[l];
+      if (Al->diag->memory_location != HYPRE_MEMORY_DEVICE || Al->offd->num_nonzeros != 0 || Al->offd->num_cols != 0) { return -1; }
+      if (!Pl || !Pl->diagT || Pl->diagT->memory_location != HYPRE_MEMORY_DEVICE || Pl->diag->memory_location != HYPRE_MEMORY_DEVICE ||
+          Pl->offd->num_cols != 0) { return -1; }
+   }
+   return K;
+}
+
+bool ensure_mv_levels(hypre_ParAMGData *d, AmgPrivate *pv, int nv, int K)
+{
+   bool fits = pv->mv_first == K && pv->mv_cols >= nv && (int) pv->mv_lev.size() == K + 1;
+   for (int l = 0; fits && l <= K; l++) { fits = pv->mv_lev[(size_t) l].n == d->A_array[l]->diag->num_rows; }
+   if (fits) { return true; }
+   HIP_CHECK(hipStreamSynchronize(stream()));
+   pv->release_mv_levels();
+   pv->mv_lev.resize((size_t) K + 1);
+   size_t widest = 0;
+   bool ok = true;
+   for (int l = 0; ok && l <= K; l++)
+   {
+      AmgPrivate::MvLevel &m = pv->mv_lev[(size_t) l];
+      m.n = d->A_array[l]->diag->num_rows;
+      m.stride = ((size_t) m.n + 1) & ~(size_t) 1;
+      const size_t bytes = sizeof(double) * ((size_t) nv * m.stride + 8);
+      if (l < K) { widest = std::max(widest, m.stride); }
+      if (l > 0) { ok = ok && plan_alloc((void **) &m.f, bytes, PLAN_SITE_MV_LEVELS) && plan_alloc((void **) &m.home, bytes, PLAN_SITE_MV_LEVELS); }
+      if (l < K) { ok = ok && plan_alloc((void **) &m.alt, bytes, PLAN_SITE_MV_LEVELS); }
+   }
+   ok = ok && plan_alloc((void **) &pv->mv_vtemp, sizeof(double) * ((size_t) nv * widest + 8), PLAN_SITE_MV_LEVELS);
+   if (!ok) { pv->release_mv_levels(); return false; }
+   pv->mv_cols = nv; pv->mv_first = K;
+   return true;
+}
+
+// one cycle of all columns; f and u: the caller's columns, n doubles apart
+HYPRE_Int amg_cycle_columns(hypre_ParAMGData *d, AmgPrivate *pv, const double *f, double *u, int n, int nv, int K, int u_zero)
+{
+   struct Lv
+   {
+      double *home, *alt, *cur; size_t hs, as;
+      size_t cs() const { return cur == home ? hs : as; }
+      double *other() const { return cur == home ? alt : home; }
+      size_t os() const { return cur == home ? as : hs; }
+      void flip() { cur = other(); }
+   };
+   hipStream_t s = stream();
+   hypre_ParCSRMatrix **A = d->A_array, **P = d->P_array;
+   const int L = d->num_levels;
+   const bool saved_fp32 = handle().fp32_values;
+   handle().fp32_values = false;
+   std::vector<Lv> lv((size_t) K + 1);
+   std::vector<const double *> F((size_t) K + 1);
+   std::vector<size_t> fs((size_t) K + 1);
+   for (int l = 0; l <= K; l++)
+   {
+      const AmgPrivate::MvLevel &m = pv->mv_lev[(size_t) l];
+      lv[(size_t) l] = Lv{l == 0 ? u : m.home, m.alt, l == 0 ? u : m.home, l == 0 ? (size_t) n : m.stride, m.stride};
+      F[(size_t) l] = l == 0 ? f : m.f;
+      fs[(size_t) l] = l == 0 ? (size_t) n : m.stride;
+   }
+   auto diag_of = [&](int l, int relax_type) -> const double *
+   {
+      const double *dg = d->l1_norms[l] ? d->l1_norms[l]->data : nullptr;
+      if (relax_type == 0 || !dg)
+      {
+         double *dd = pv->level_diag(l, A[l]->diag->num_rows);
+         launch_diag_first(A[l]->diag->i, A[l]->diag->data, dd, A[l]->diag->num_rows, s);
+         dg = dd;
+      }
+      return dg;
+   };
+   double op_count = 0.0;
+   std::vector<int> presmoothed((size_t) K + 1, 0);
+   double *vtemp = pv->mv_vtemp;
+   // ---- down
+   for (int l = 0; l < K; l++)
+   {
+      const int nl = A[l]->diag->num_rows, coarse = l + 1;
+      Lv &ul = lv[(size_t) l];
+      const double w = d->relax_weight[l];
+      const double *dg = diag_of(l, d->grid_relax_type[1]);
+      bool zero = l == 0 ? u_zero != 0 : true;
+      for (int j = 0; j < d->num_grid_sweeps[1]; j++)
+      {
+         op_count += A[l]->d_num_nonzeros;
+         if (zero)
+         {
+            if (presmoothed[(size_t) l]) { presmoothed[(size_t) l] = 0; }      // the restriction's epilogue did it
+            else
+            {
+               for (int v = 0; v < nv; v++) { launch_scaled_div(w, F[(size_t) l] + (size_t) v * fs[(size_t) l], dg, ul.cur + (size_t) v * ul.cs(), nullptr, 0, (size_t) nl, s); }
+            }
+         }
+         else
+         {
+            spmv_columns_jacobi(A[l]->diag, F[(size_t) l], fs[(size_t) l], w, dg, ul.cur, ul.cs(), ul.other(), ul.os(), nv);
+            ul.flip();
+         }
+         zero = false;
+      }
+      // r = f - A u ; f_c = P^T r (and u_c = w f_c ./ d_c where the single-column cycle fuses it)
+      Lv &uc = lv[(size_t) coarse];
+      uc.cur = uc.home;
+      const size_t vs = pv->mv_lev[(size_t) l].stride;
+      spmv_columns(-1.0, A[l]->diag, ul.cur, ul.cs(), 1.0, F[(size_t) l], fs[(size_t) l], vtemp, vs, nv);
+      double *fc = pv->mv_lev[(size_t) coarse].f;
+      const size_t fcs = pv->mv_lev[(size_t) coarse].stride;
+      bool restricted = false;
+      if (cycle_fusion() && coarse != L - 1 && d->l1_norms[coarse] && d->l1_norms[coarse]->data)
+      {
+         restricted = spmv_columns_scaled_quotient(P[l]->diagT, vtemp, vs, fc, fcs, d->relax_weight[coarse], d->l1_norms[coarse]->data,
+                                                   uc.cur, uc.hs, nv);
+         presmoothed[(size_t) coarse] = restricted ? 1 : 0;
+      }
+      if (!restricted) { spmv_columns(1.0, P[l]->diagT, vtemp, vs, 0.0, fc, fcs, fc, fcs, nv); }
+   }
+   // ---- level K and below: column by column on the solver's single-column level vectors
+   HYPRE_Int err = 0;
+   double tail_count = 0.0;
+   {
+      const int nK = A[K]->diag->num_rows;
+      const AmgPrivate::MvLevel &m = pv->mv_lev[(size_t) K];
+      double *fK = d->F_array[K]->local_vector->data, *uK = d->U_array[K]->local_vector->data;
+      for (int v = 0; v < nv && !err; v++)
+      {
+         launch_copy(fK, m.f + (size_t) v * m.stride, (size_t) nK, s);
+         if (presmoothed[(size_t) K]) { launch_copy(uK, m.home + (size_t) v * m.stride, (size_t) nK, s); d->F_array[K]->all_zeros = 0; }
+         d->U_array[K]->all_zeros = 1;
+         d->cycle_op_count = 0;
+         err = amg_cycle_from(d, d->F_array, d->U_array, K, presmoothed[(size_t) K]);
+         tail_count = d->cycle_op_count;
+         launch_copy(m.home + (size_t) v * m.stride, uK, (size_t) nK, s);
+      }
+      handle().fp32_values = false;
+      lv[(size_t) K].cur = lv[(size_t) K].home;
+   }
+   // ---- up
+   for (int l = K - 1; l >= 0 && !err; l--)
+   {
+      Lv &uf = lv[(size_t) l], &uc = lv[(size_t) (l + 1)];
+      const int flips = d->num_grid_sweeps[2];
+      double *target = (flips % 2 == 0) ? uf.home : uf.alt;
+      const size_t ts = (flips % 2 == 0) ? uf.hs : uf.as;
+      spmv_columns(1.0, P[l]->diag, uc.cur, uc.cs(), 1.0, uf.cur, uf.cs(), target, ts, nv);
+      uf.cur = target;
+      const double w = d->relax_weight[l];
+      const double *dg = diag_of(l, d->grid_relax_type[2]);
+      for (int j = 0; j < d->num_grid_sweeps[2]; j++)
+      {
+         op_count += A[l]->d_num_nonzeros;
+         spmv_columns_jacobi(A[l]->diag, F[(size_t) l], fs[(size_t) l], w, dg, uf.cur, uf.cs(), uf.other(), uf.os(), nv);
+         uf.flip();
+      }
+   }
+   if (!err && lv[0].cur != lv[0].home)
+   {
+      for (int v = 0; v < nv; v++) { launch_copy(lv[0].home + (size_t) v * lv[0].hs, lv[0].cur + (size_t) v * lv[0].as, (size_t) n, s); }
+   }
+   d->cycle_op_count = op_count + tail_count;          // (one cycle's count, as with one column)
+   handle().fp32_values = saved_fp32;
+   return err;
+}
+}  // namespace
+}  // extern "C++"
+
+// Multi-column solves cycle their large levels for all columns at once from now on (1) or column by column (0): speed only,
+// same bits.  Nothing recorded is invalidated: a graph only ever sees the single-column vectors.  on < 0: unchanged; returns
+// the setting.
+HYPRE_Int hypre_amd_SetMultivectorCycle(HYPRE_Int on)
+{
+   if (on >= 0) { multivector_cycle() = on != 0; }
+   return multivector_cycle();
 }
 
 // The solve of num_vectors = NV columns stored one after the other.  Every cycle runs column by column on the solver's
@@ -1270,11 +1505,21 @@ static HYPRE_Int amg_solve_columns(hypre_ParAMGData *d, hypre_ParCSRMatrix *A, h
    HYPRE_Int cycle_count = 0;
    while ((relative_resid >= tol || cycle_count < d->min_iter) && cycle_count < d->max_iter)
    {
-      for (int v = 0; v < nv; v++)
+      // the large levels for all columns at once where this solver's cycle is served and the level vectors are to be had
+      const int first_single = multivector_cycle() ? multivector_cycle_first(d, pv) : -1;
+      if (first_single >= 1 && ensure_mv_levels(d, pv, nv, first_single))
       {
-         d->cycle_op_count = 0;          // (one cycle's count, as with one column)
-         d->F_array[0] = &fp[(size_t) v]; d->U_array[0] = &up[(size_t) v];
-         hypre_BoomerAMGCycle(d, d->F_array, d->U_array);
+         d->F_array[0] = &fp[0]; d->U_array[0] = &up[0];
+         amg_cycle_columns(d, pv, fl->data, ul->data, n, nv, first_single, u->all_zeros);
+      }
+      else
+      {
+         for (int v = 0; v < nv; v++)
+         {
+            d->cycle_op_count = 0;          // (one cycle's count, as with one column)
+            d->F_array[0] = &fp[(size_t) v]; d->U_array[0] = &up[(size_t) v];
+            hypre_BoomerAMGCycle(d, d->F_array, d->U_array);
+         }
       }
       u->all_zeros = 0;
       if (track)

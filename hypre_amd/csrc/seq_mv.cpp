@@ -1131,13 +1131,63 @@ static void spmv_device_columns(HYPRE_Complex alpha, hypre_CSRMatrix *A, const H
       a.x = x; a.b = b; a.y = y; a.d = nullptr; a.marker = nullptr; a.marker_val = 0;
       a.alpha = alpha; a.beta = beta; a.fill = fill; a.row_offset = 0;
       spmv_default_flags(a);
-      if (launch_spmv_mv(get_plan(A), a, nv, (long) xstride, (long) bstride, (long) ystride, stream())) { return; }
+      if (launch_spmv_mv(get_plan(A), a, OP_AXPBY, nv, (long) xstride, (long) bstride, (long) ystride, 0, stream())) { return; }
    }
    for (HYPRE_Int v = 0; v < nv; v++)
    {
       spmv_device_core(alpha, A, x + (size_t) v * xstride, beta, b + (size_t) v * bstride, y + (size_t) v * ystride, fill);
    }
 }
+
+extern "C++" {
+namespace hamd {
+void spmv_columns(HYPRE_Complex alpha, hypre_CSRMatrix *A, const double *x, size_t xstride, HYPRE_Complex beta, const double *b,
+                  size_t bstride, double *y, size_t ystride, int nv)
+{
+   spmv_device_columns(alpha, A, x, xstride, beta, b, bstride, y, ystride, nv, HYPRE_SPMV_FILL_WHOLE);
+}
+// the sweep of dev_jacobi_sweep (one rank, all points) over nv columns against one diagonal
+void spmv_columns_jacobi(hypre_CSRMatrix *A, const double *f, size_t fstride, double w, const double *d, const double *u_in, size_t instride,
+                         double *u_out, size_t outstride, int nv)
+{
+   if (A->num_rows <= 0) { return; }
+   SpmvPlan *plan = get_plan(A);
+   SpmvArgs a{};
+   a.Ai = A->i; a.Aj = A->j; a.Aa = A->data; a.Aa32 = nullptr;
+   a.x = u_in; a.b = f; a.y = u_out; a.aux = nullptr; a.d = d;
+   a.marker = nullptr; a.marker_val = 0;
+   a.alpha = w; a.beta = 0.0; a.fill = HYPRE_SPMV_FILL_WHOLE; a.row_offset = 0;
+   spmv_default_flags(a);
+   if (nv > 1 && spmv_fused_multivectors() && launch_spmv_mv(plan, a, OP_JACOBI, nv, (long) instride, (long) fstride, (long) outstride, 0, stream())) { return; }
+   for (int v = 0; v < nv; v++)
+   {
+      SpmvArgs c = a;
+      c.x = u_in + (size_t) v * instride; c.b = f + (size_t) v * fstride; c.y = u_out + (size_t) v * outstride;
+      launch_spmv(plan, c, OP_JACOBI, stream());
+   }
+}
+// spmv_with_scaled_quotient over nv columns
+bool spmv_columns_scaled_quotient(hypre_CSRMatrix *M, const double *x, size_t xstride, double *y, size_t ystride, double w, const double *d,
+                                  double *u, size_t ustride, int nv)
+{
+   if (!M || M->num_rows <= 0 || M->num_nonzeros <= 0 || !d || !u || M->memory_location != HYPRE_MEMORY_DEVICE) { return false; }
+   SpmvArgs a{};
+   a.Ai = M->i; a.Aj = M->j; a.Aa = M->data; a.Aa32 = nullptr;
+   a.x = x; a.b = nullptr; a.y = y; a.d = d; a.aux = u; a.marker = nullptr; a.marker_val = 0;
+   a.alpha = 1.0; a.beta = 0.0; a.scale2 = w; a.fill = HYPRE_SPMV_FILL_WHOLE; a.row_offset = 0;
+   spmv_default_flags(a);
+   SpmvPlan *plan = get_plan(M);
+   if (nv > 1 && spmv_fused_multivectors() && launch_spmv_mv(plan, a, OP_AXPBY_DIV, nv, (long) xstride, 0, (long) ystride, (long) ustride, stream())) { return true; }
+   for (int v = 0; v < nv; v++)
+   {
+      SpmvArgs c = a;
+      c.x = x + (size_t) v * xstride; c.y = y + (size_t) v * ystride; c.aux = u + (size_t) v * ustride;
+      launch_spmv(plan, c, OP_AXPBY_DIV, stream());
+   }
+   return true;
+}
+}  // namespace hamd
+}  // extern "C++"
 
 // Multivector products in one pass over the matrix (default) or column by column: speed only, same bits.
 HYPRE_Int hypre_amd_SpmvSetFusedMultivectors(HYPRE_Int on)

@@ -894,12 +894,62 @@ void spmv_xs_kernel(SpmvArgs p, const int *__restrict__ tile_row, const int *__r
 // Same bits as NV single-vector products: every product rounded, then the additions of tile_reduce in its order (stored
 // order on one lane; W interleaved partial sums and the xor tree on W lanes, W chosen as tile_reduce chooses it).
 // Serves fp64 and coded matrices (VF_F64 / VF_CODE) multiplied as a whole; everything else keeps the column loop.
+// Row epilogues of the multivector kernels (all three families): OP_AXPBY, OP_AXPBY_DIV and OP_JACOBI over NV columns against
+// ONE diagonal, each column with the expression of row_epilogue, rounding for rounding.
 // ---------------------------------------------------------------------------
-template <int NV, bool CODED, int W>
+template <int NV>
+struct MvOps
+{
+   double b[NV], x[NV], d;
+};
+template <int NV, int OP>
+__device__ __forceinline__ void mv_load_ops(MvOps<NV> &o, const SpmvArgs &p, int row, long xstride, long bstride)
+{
+   o.d = 1.0;
+#pragma unroll
+   for (int v = 0; v < NV; v++) { o.b[v] = 0.0; o.x[v] = 0.0; }
+   if (OP == OP_JACOBI)
+   {
+      o.d = p.d[row];
+#pragma unroll
+      for (int v = 0; v < NV; v++) { o.b[v] = p.b[(size_t) v * bstride + row]; o.x[v] = p.x[(size_t) v * xstride + row]; }
+   }
+   else
+   {
+      if (p.beta != 0.0)
+      {
+#pragma unroll
+         for (int v = 0; v < NV; v++) { o.b[v] = p.b[(size_t) v * bstride + row]; }
+      }
+      if (OP == OP_AXPBY_DIV) { o.d = p.d[row]; }
+   }
+}
+template <int NV, int OP>
+__device__ __forceinline__ void mv_epilogue(const SpmvArgs &p, int row, const double *sum, const MvOps<NV> &o, long ystride, long auxstride)
+{
+#pragma unroll
+   for (int v = 0; v < NV; v++)
+   {
+      if (OP == OP_JACOBI)
+      {
+         const double t = __fma_rn(p.alpha, o.b[v], -__dmul_rn(p.alpha, sum[v]));
+         p.y[(size_t) v * ystride + row] = __dadd_rn(o.x[v], t / o.d);
+      }
+      else
+      {
+         double r = __dmul_rn(p.alpha, sum[v]);
+         if (p.beta != 0.0) { r = __fma_rn(p.beta, o.b[v], r); }
+         p.y[(size_t) v * ystride + row] = r;
+         if (OP == OP_AXPBY_DIV) { p.aux[(size_t) v * auxstride + row] = __dmul_rn(p.scale2, r) / o.d; }
+      }
+   }
+}
+
+template <int NV, bool CODED, int W, int OP>
 __device__ __forceinline__ void mv_row_sums(const SpmvArgs &p, int r0, int nrows, int ka, int rp_cap, bool staged, int stage_elems,
                                             const double *xsv, const double *valS, const unsigned char *cdS, const double *dictl,
                                             const unsigned short *liS, const int *rp, long xstride, long bstride, long ystride,
-                                            const double *bv)
+                                            long auxstride, const MvOps<NV> &ops)
 {
    constexpr int MB = 4;                     // entries a lane has in flight (values, indices, then NV x each): the additions keep their order
    const int G = (int) blockDim.x / W;       // rows a pass takes (the workgroup may have more lanes than the 256 that stream the tile)
@@ -978,24 +1028,25 @@ __device__ __forceinline__ void mv_row_sums(const SpmvArgs &p, int r0, int nrows
       }
       if (live && sub == 0)
       {
-#pragma unroll
-         for (int v = 0; v < NV; v++)
+         // the row's operands: fetched early for the row of a lane's own number, else here
+         if (W == 1 && rr == tid) { mv_epilogue<NV, OP>(p, row, sum, ops, ystride, auxstride); }
+         else
          {
-            // the epilogue of OP_AXPBY (row_epilogue)
-            double r = __dmul_rn(p.alpha, sum[v]);
-            if (p.beta != 0.0) { r = __fma_rn(p.beta, (W == 1 && rr == tid) ? bv[v] : p.b[(size_t) v * bstride + row], r); }
-            p.y[(size_t) v * ystride + row] = r;
+            MvOps<NV> o;
+            mv_load_ops<NV, OP>(o, p, row, xstride, bstride);
+            mv_epilogue<NV, OP>(p, row, sum, o, ystride, auxstride);
          }
       }
    }
 }
 
 constexpr int MV_THREADS_MAX = 384;       // tiles of short rows hold more rows than 256: a fifth and sixth wave take them in the same pass
-template <int NV, bool CODED>
+template <int NV, bool CODED, int OP>
 __global__ __launch_bounds__(MV_THREADS_MAX)
 void spmv_xs_mv_kernel(SpmvArgs p, const int *__restrict__ tile_row, const int *__restrict__ tile_k,
                        const int *__restrict__ xs_cnt, const int *__restrict__ xs_desc, const unsigned short *__restrict__ lidx,
-                       int num_tiles, int stage_elems, int win_elems, int rp_cap, int xs_units, long xstride, long bstride, long ystride)
+                       int num_tiles, int stage_elems, int win_elems, int rp_cap, int xs_units, long xstride, long bstride, long ystride,
+                       long auxstride)
 {
    extern __shared__ __align__(16) unsigned char smem_raw[];
    double *xsv  = reinterpret_cast<double *>(smem_raw);                               // NV staged copies of x, stage_elems each
@@ -1103,15 +1154,8 @@ void spmv_xs_mv_kernel(SpmvArgs p, const int *__restrict__ tile_row, const int *
       }
    }
    // the first row's operands of every lane: same trip
-   double bv[NV];
-#pragma unroll
-   for (int v = 0; v < NV; v++) { bv[v] = 0.0; }
-   if (p.beta != 0.0)
-   {
-      const int rb = max(r0 + min(tid, nrows - 1), 0);
-#pragma unroll
-      for (int v = 0; v < NV; v++) { bv[v] = p.b[(size_t) v * bstride + rb]; }
-   }
+   MvOps<NV> ops;
+   mv_load_ops<NV, OP>(ops, p, max(r0 + min(tid, nrows - 1), 0), xstride, bstride);
    if (streamer)
    {
       // the spill of the tile's last row past the window (rows of at most SPMV_THREADS entries: the launcher's condition) and
@@ -1162,7 +1206,7 @@ void spmv_xs_mv_kernel(SpmvArgs p, const int *__restrict__ tile_row, const int *
       Wd = p.reduce_w;
       if (Wd <= 0) { Wd = 32; while (Wd > 1 && nrows * Wd > SPMV_THREADS) { Wd >>= 1; } }
    }
-#define MV_SUMS(WW) mv_row_sums<NV, CODED, WW>(p, r0, nrows, ka, rp_cap, staged, stage_elems, xsv, valS, cdS, dictl, liS, rp, xstride, bstride, ystride, bv)
+#define MV_SUMS(WW) mv_row_sums<NV, CODED, WW, OP>(p, r0, nrows, ka, rp_cap, staged, stage_elems, xsv, valS, cdS, dictl, liS, rp, xstride, bstride, ystride, auxstride, ops)
    switch (Wd)
    {
       case 1:  MV_SUMS(1); break;
@@ -1594,12 +1638,12 @@ void spmv_sl_kernel_cls(SpmvArgs p, const int *__restrict__ sl_desc, const int *
 
 // The slice form with a multivector: a lane's codes and local indices are in registers, so the columns cost their x pieces
 // (NV staged copies), NV reads per entry and NV sums — the matrix words are read once.  Same bits as spmv_sl_kernel column
-// by column (and so as every other form).  y = alpha A x + beta b only.
-template <int NV, int W, int KP, bool CLS>
+// by column (and so as every other form).  Epilogues: OP_AXPBY, OP_AXPBY_DIV, OP_JACOBI (mv_epilogue).
+template <int NV, int W, int KP, bool CLS, int OP>
 __device__ __forceinline__
 void spmv_sl_mv_body(const SpmvArgs &p, const int *__restrict__ sl_desc, const int *__restrict__ sl_k0,
                      const int *__restrict__ sl_fp, const int *__restrict__ sl_perm, const SlStream &st,
-                     int blocks, int num_rows, int nnz, int stage_elems, long xstride, long bstride, long ystride)
+                     int blocks, int num_rows, int nnz, int stage_elems, long xstride, long bstride, long ystride, long auxstride)
 {
    extern __shared__ __align__(16) unsigned char smem_raw[];
    double *xs = reinterpret_cast<double *>(smem_raw);
@@ -1621,15 +1665,8 @@ void spmv_sl_mv_body(const SpmvArgs &p, const int *__restrict__ sl_desc, const i
    const int r = block * R + tid / W, sub = tid % W;
    SlLane<CLS, KP> me;
    sl_lane_load<CLS, W, KP>(me, st, p.Ai, block, wave, lane, tid, r, num_rows);
-   const int rc = max(min(r, num_rows - 1), 0);
-   double bv[NV];
-#pragma unroll
-   for (int v = 0; v < NV; v++) { bv[v] = 0.0; }
-   if (p.beta != 0.0)
-   {
-#pragma unroll
-      for (int v = 0; v < NV; v++) { bv[v] = p.b[(size_t) v * bstride + rc]; }
-   }
+   MvOps<NV> ops;
+   mv_load_ops<NV, OP>(ops, p, max(min(r, num_rows - 1), 0), xstride, bstride);
    const int *dsc = sl_desc + (size_t) block * XS_DESC + XS_WSEG * wave;
    int seg_start[XS_WSEG], seg_ol[XS_WSEG];
 #pragma unroll
@@ -1695,35 +1732,26 @@ void spmv_sl_mv_body(const SpmvArgs &p, const int *__restrict__ sl_desc, const i
       if (tid == 0) { off = off || fp_plan != (int) ((unsigned) fc0 * 2654435761u + (unsigned) fc1) || me.rs != k0; }
       if (off) { __hip_atomic_fetch_or(p.stale, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
    }
-   if (r < num_rows && sub == 0)
-   {
-#pragma unroll
-      for (int v = 0; v < NV; v++)
-      {
-         double t = __dmul_rn(p.alpha, sum[v]);
-         if (p.beta != 0.0) { t = __fma_rn(p.beta, bv[v], t); }
-         p.y[(size_t) v * ystride + r] = t;
-      }
-   }
+   if (r < num_rows && sub == 0) { mv_epilogue<NV, OP>(p, r, sum, ops, ystride, auxstride); }
 }
-template <int NV, int W, int KP>
+template <int NV, int W, int KP, int OP>
 __global__ __launch_bounds__(SPMV_THREADS)
 void spmv_sl_mv_kernel(SpmvArgs p, const int *__restrict__ sl_desc, const int *__restrict__ sl_k0,
                        const int *__restrict__ sl_fp, const int *__restrict__ sl_perm, const unsigned *__restrict__ sl_data,
-                       int blocks, int num_rows, int nnz, int stage_elems, long xstride, long bstride, long ystride)
+                       int blocks, int num_rows, int nnz, int stage_elems, long xstride, long bstride, long ystride, long auxstride)
 {
    const SlStream st = {sl_data, nullptr, nullptr, nullptr};
-   spmv_sl_mv_body<NV, W, KP, false>(p, sl_desc, sl_k0, sl_fp, sl_perm, st, blocks, num_rows, nnz, stage_elems, xstride, bstride, ystride);
+   spmv_sl_mv_body<NV, W, KP, false, OP>(p, sl_desc, sl_k0, sl_fp, sl_perm, st, blocks, num_rows, nnz, stage_elems, xstride, bstride, ystride, auxstride);
 }
-template <int NV, int W, int KP>
+template <int NV, int W, int KP, int OP>
 __global__ __launch_bounds__(SPMV_THREADS)
 void spmv_sl_mv_kernel_cls(SpmvArgs p, const int *__restrict__ sl_desc, const int *__restrict__ sl_k0, const int *__restrict__ sl_fp,
                            const int *__restrict__ sl_perm, const unsigned char *__restrict__ sl_cls, const unsigned *__restrict__ sl_tab,
                            const int *__restrict__ sl_toff, int blocks, int num_rows, int nnz, int stage_elems, long xstride, long bstride,
-                           long ystride)
+                           long ystride, long auxstride)
 {
    const SlStream st = {nullptr, sl_cls, sl_tab, sl_toff};
-   spmv_sl_mv_body<NV, W, KP, true>(p, sl_desc, sl_k0, sl_fp, sl_perm, st, blocks, num_rows, nnz, stage_elems, xstride, bstride, ystride);
+   spmv_sl_mv_body<NV, W, KP, true, OP>(p, sl_desc, sl_k0, sl_fp, sl_perm, st, blocks, num_rows, nnz, stage_elems, xstride, bstride, ystride, auxstride);
 }
 
 // ---- slice form construction
@@ -2125,6 +2153,137 @@ void spmv_rs_kernel(SpmvArgs p, const int *__restrict__ rs_desc, const int *__re
       double total = part[tid];
       for (int j = 1; j < W; j++) { total += part[j * R + tid]; }
       row_epilogue<OP>(p, r, total, ops);
+   }
+}
+
+// The row-slice form with a multivector: a lane's values and staged positions are in registers, so a further column costs its x
+// pieces (NV staged copies, one after the other), one LDS read and one fused multiply-add per entry and one partial sum — the
+// values and position words are read once.  Same bits as spmv_rs_kernel column by column: a lane's entries in stored order
+// (fused multiply-adds, as there), then the W partial sums of a row in lane order.  fp64 values only.
+template <int NV, int OP, int KP>
+__global__ __launch_bounds__(SPMV_THREADS)
+void spmv_rs_mv_kernel(SpmvArgs p, const int *__restrict__ rs_desc, const int *__restrict__ rs_perm, const int *__restrict__ rs_hdr,
+                       const unsigned *__restrict__ rs_meta, const double *__restrict__ rs_val, const unsigned *__restrict__ rs_idx,
+                       int blocks, int num_rows, int R, int W, int stage_elems, long xstride, long bstride, long ystride, long auxstride)
+{
+   extern __shared__ __align__(16) unsigned char smem_raw[];
+   double *xs = reinterpret_cast<double *>(smem_raw);              // NV staged copies of x, stage_elems each
+   double *part = xs + (size_t) NV * stage_elems;                  // [NV][SPMV_THREADS] partial sums, lane-of-the-row major
+
+   int block = (int) blockIdx.x;
+   if (rs_perm)
+   {
+      if (block >= blocks) { return; }
+      block = rs_perm[block];
+   }
+   else { const int g = block >> 3, c = block & 7; block = (g >> 3) * 64 + c * 8 + (g & 7); }     // runs of 8 blocks per XCD
+   if ((unsigned) block >= (unsigned) blocks) { return; }
+
+   const int tid = threadIdx.x, lane = tid & 63;
+   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+   const unsigned meta = rs_meta[(size_t) block * SPMV_THREADS + tid];
+   const int r = block * R + tid;
+   MvOps<NV> ops;
+   mv_load_ops<NV, OP>(ops, p, max(min(r, num_rows - 1), 0), xstride, bstride);
+   constexpr int NH = 4 + KP / 4;
+   const int *hdr = rs_hdr + (size_t) (block * 4 + wave) * RS_HDR;
+   int h[NH];
+#pragma unroll
+   for (int i = 0; i < NH; i++) { h[i] = hdr[i]; }
+   const int *dsc = rs_desc + (size_t) block * XS_DESC + XS_WSEG * wave;
+   int seg_start[XS_WSEG], seg_ol[XS_WSEG];
+#pragma unroll
+   for (int j = 0; j < XS_WSEG; j++) { seg_start[j] = dsc[j]; seg_ol[j] = dsc[XS_SEGS + j]; }
+   asm volatile("" :: "s"(rs_desc), "s"(rs_hdr), "s"(rs_meta) : "memory");
+   const int nch = h[1];
+   // the stream, as spmv_rs_kernel reads it
+   const double *wv = rs_val + h[0];
+   const unsigned *wi = rs_idx + h[2];
+   double   vv[KP];
+   unsigned iw[KP / 2];
+   {
+      int off = 0, offi = 0;
+#pragma unroll
+      for (int g = 0; g < KP / 4; g++)
+      {
+         if (4 * g < nch)
+         {
+#pragma unroll
+            for (int c = 4 * g; c < 4 * g + 4; c++)
+            {
+               const int na = (h[4 + (c >> 2)] >> (8 * (c & 3))) & 0xff;
+               vv[c] = wv[(unsigned) (off + min(lane, na - 1))];
+               if ((c & 1) == 0) { iw[c >> 1] = wi[(unsigned) (offi + min(lane, na - 1))]; offi += na; }
+               off += na;
+            }
+         }
+      }
+   }
+   // the x pieces of every column, straight into LDS
+#pragma unroll
+   for (int v = 0; v < NV; v++)
+   {
+#pragma unroll
+      for (int j = 0; j < XS_WSEG; j++)
+      {
+         const unsigned offb = (unsigned) seg_ol[j] >> 16, lanes = (unsigned) seg_ol[j] & 0xffffu;
+         if ((unsigned) lane < lanes)
+         {
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) (p.x + (size_t) v * xstride + (size_t) (unsigned) seg_start[j] + 2 * lane),
+                                             (__attribute__((address_space(3))) void *) (reinterpret_cast<char *>(xs + (size_t) v * stage_elems) + offb), 16, 0, 0);
+         }
+      }
+   }
+   __syncthreads();
+
+   const int cnt = (int) (meta >> 10);
+   const char *xb = reinterpret_cast<const char *>(xs);
+   double sum[NV];
+#pragma unroll
+   for (int v = 0; v < NV; v++) { sum[v] = 0.0; }
+   // entries in stored order, FG of them with their NV reads in flight together (the order of a column's additions is that of
+   // the one-by-one loop whatever FG is)
+   constexpr int FG = (KP >= 32 || NV >= 4) ? 2 : 4;
+#pragma unroll
+   for (int g = 0; g < KP / FG; g++)
+   {
+      if (FG * g < nch)
+      {
+         double xv[FG][NV];
+#pragma unroll
+         for (int j = 0; j < FG; j++)
+         {
+            const int c = FG * g + j;
+            const unsigned pos = (c & 1) ? (iw[c >> 1] >> 16) : (iw[c >> 1] & 0xffffu);
+#pragma unroll
+            for (int v = 0; v < NV; v++) { xv[j][v] = *reinterpret_cast<const double *>(xb + sizeof(double) * (size_t) v * stage_elems + pos); }
+         }
+#pragma unroll
+         for (int j = 0; j < FG; j++)
+         {
+            const int c = FG * g + j;
+#pragma unroll
+            for (int v = 0; v < NV; v++)
+            {
+               const double t = __fma_rn(vv[c], xv[j][v], sum[v]);
+               sum[v] = (c < cnt) ? t : sum[v];
+            }
+         }
+      }
+   }
+#pragma unroll
+   for (int v = 0; v < NV; v++) { part[v * SPMV_THREADS + (meta & 0x3ffu)] = sum[v]; }
+   lds_barrier();
+   if (tid < R && r < num_rows)
+   {
+      double total[NV];
+#pragma unroll
+      for (int v = 0; v < NV; v++)
+      {
+         total[v] = part[v * SPMV_THREADS + tid];
+         for (int j = 1; j < W; j++) { total[v] += part[v * SPMV_THREADS + j * R + tid]; }
+      }
+      mv_epilogue<NV, OP>(p, r, total, ops, ystride, auxstride);
    }
 }
 
@@ -2850,16 +3009,15 @@ void launch_spmv(const SpmvPlan *plan, const SpmvArgs &args, SpmvOp op, hipStrea
    }
 }
 
-// Fused product with a multivector (spmv_xs_mv_kernel): columns v < nv of x, b, y lie xstride / bstride / ystride doubles
-// apart.  false: this plan or these operands are not served (the caller multiplies column by column); nothing was launched.
-template <int NV, bool CODED>
+// Fused passes over a multivector: columns v < nv of x, b, y, aux lie xstride / bstride / ystride / auxstride doubles apart.
+template <int NV, bool CODED, int OP>
 static void launch_xs_mv(const SpmvPlan *plan, const SpmvArgs &a, int stage_elems, int win_elems, int rp_cap, size_t lds,
-                         long xstride, long bstride, long ystride, hipStream_t s)
+                         long xstride, long bstride, long ystride, long auxstride, hipStream_t s)
 {
    static bool raised = false;
    if (!raised)
    {
-      (void) hipFuncSetAttribute((const void *) (spmv_xs_mv_kernel<NV, CODED>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      (void) hipFuncSetAttribute((const void *) (spmv_xs_mv_kernel<NV, CODED, OP>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       (void) hipGetLastError();
       raised = true;
    }
@@ -2868,51 +3026,94 @@ static void launch_xs_mv(const SpmvPlan *plan, const SpmvArgs &a, int stage_elem
    // a lane per row where the rows are short: a fifth and a sixth wave take rows 256 .. 383 of a tile in the same pass
    const int threads = (plan->max_tile_rows > SPMV_THREADS && plan->max_tile_rows <= 320) ? 320 :
                        (plan->max_tile_rows > 320 ? MV_THREADS_MAX : SPMV_THREADS);
-   hipLaunchKernelGGL((spmv_xs_mv_kernel<NV, CODED>), dim3(grid), dim3(threads), lds, s, a,
+   hipLaunchKernelGGL((spmv_xs_mv_kernel<NV, CODED, OP>), dim3(grid), dim3(threads), lds, s, a,
                       plan->d_tile_row, plan->d_tile_k, plan->d_xs_cnt, plan->d_xs_desc, plan->d_lidx,
-                      plan->num_tiles, stage_elems, win_elems, rp_cap, plan->xs_launch_units, xstride, bstride, ystride);
+                      plan->num_tiles, stage_elems, win_elems, rp_cap, plan->xs_launch_units, xstride, bstride, ystride, auxstride);
 }
 
 long &spmv_mv_launches() { static long n = 0; return n; }
-template <int NV, int W, int KP>
-static void launch_sl_mv(const SpmvPlan *plan, const SpmvArgs &a, int stage_elems, size_t lds, long xstride, long bstride, long ystride, hipStream_t s)
+template <int NV, int W, int KP, int OP>
+static void launch_sl_mv(const SpmvPlan *plan, const SpmvArgs &a, int stage_elems, size_t lds, long xstride, long bstride, long ystride,
+                         long auxstride, hipStream_t s)
 {
-   static bool raised = false;
-   if (!raised)
-   {
-      (void) hipFuncSetAttribute((const void *) (spmv_sl_mv_kernel<NV, W, KP>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void) hipGetLastError();
-      raised = true;
-   }
    const int grid = plan->d_sl_perm ? plan->sl_blocks : ((plan->sl_blocks + 63) / 64) * 64;
    if (plan->d_sl_cls)
    {
       static bool raised_cls = false;
       if (!raised_cls)
       {
-         (void) hipFuncSetAttribute((const void *) (spmv_sl_mv_kernel_cls<NV, W, KP>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+         (void) hipFuncSetAttribute((const void *) (spmv_sl_mv_kernel_cls<NV, W, KP, OP>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
          (void) hipGetLastError();
          raised_cls = true;
       }
-      hipLaunchKernelGGL((spmv_sl_mv_kernel_cls<NV, W, KP>), dim3(grid), dim3(SPMV_THREADS), lds, s, a, plan->d_sl_desc, plan->d_sl_k0, plan->d_sl_fp,
+      hipLaunchKernelGGL((spmv_sl_mv_kernel_cls<NV, W, KP, OP>), dim3(grid), dim3(SPMV_THREADS), lds, s, a, plan->d_sl_desc, plan->d_sl_k0, plan->d_sl_fp,
                          plan->d_sl_perm, plan->d_sl_cls, plan->d_sl_tab, plan->d_sl_toff, plan->sl_blocks, plan->num_rows, plan->nnz, stage_elems,
-                         xstride, bstride, ystride);
+                         xstride, bstride, ystride, auxstride);
       return;
    }
-   hipLaunchKernelGGL((spmv_sl_mv_kernel<NV, W, KP>), dim3(grid), dim3(SPMV_THREADS), lds, s, a, plan->d_sl_desc, plan->d_sl_k0,
-                      plan->d_sl_fp, plan->d_sl_perm, plan->d_sl_data, plan->sl_blocks, plan->num_rows, plan->nnz, stage_elems, xstride, bstride, ystride);
+   static bool raised = false;
+   if (!raised)
+   {
+      (void) hipFuncSetAttribute((const void *) (spmv_sl_mv_kernel<NV, W, KP, OP>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      (void) hipGetLastError();
+      raised = true;
+   }
+   hipLaunchKernelGGL((spmv_sl_mv_kernel<NV, W, KP, OP>), dim3(grid), dim3(SPMV_THREADS), lds, s, a, plan->d_sl_desc, plan->d_sl_k0,
+                      plan->d_sl_fp, plan->d_sl_perm, plan->d_sl_data, plan->sl_blocks, plan->num_rows, plan->nnz, stage_elems, xstride, bstride, ystride,
+                      auxstride);
 }
-template <int NV>
-static void launch_sl_mv_nv(const SpmvPlan *plan, const SpmvArgs &a, int stage_elems, size_t lds, long xstride, long bstride, long ystride, hipStream_t s)
+template <int NV, int OP>
+static void launch_sl_mv_nv(const SpmvPlan *plan, const SpmvArgs &a, int stage_elems, size_t lds, long xstride, long bstride, long ystride,
+                            long auxstride, hipStream_t s)
 {
-   if (plan->sl_w == 1) { launch_sl_mv<NV, 1, 8>(plan, a, stage_elems, lds, xstride, bstride, ystride, s); }
-   else if (plan->sl_k == 8) { launch_sl_mv<NV, 2, 8>(plan, a, stage_elems, lds, xstride, bstride, ystride, s); }
-   else { launch_sl_mv<NV, 2, 16>(plan, a, stage_elems, lds, xstride, bstride, ystride, s); }
+   if (plan->sl_w == 1) { launch_sl_mv<NV, 1, 8, OP>(plan, a, stage_elems, lds, xstride, bstride, ystride, auxstride, s); }
+   else if (plan->sl_k == 8) { launch_sl_mv<NV, 2, 8, OP>(plan, a, stage_elems, lds, xstride, bstride, ystride, auxstride, s); }
+   else { launch_sl_mv<NV, 2, 16, OP>(plan, a, stage_elems, lds, xstride, bstride, ystride, auxstride, s); }
 }
 static inline size_t sl_mv_lds_bytes(const SpmvPlan *plan, int nv, int ndict, int &stage_elems)
 {
    stage_elems = sl_stage_elems(plan);
    return sizeof(double) * ((size_t) nv * stage_elems + (size_t) ((ndict + 1) & ~1)) + sl_table_bytes(plan);
+}
+
+template <int NV, int OP, int KP>
+static void launch_rs_mv_form(const SpmvPlan *plan, const SpmvArgs &a, int stage_elems, size_t lds, long xstride, long bstride, long ystride,
+                              long auxstride, hipStream_t s)
+{
+   static bool raised = false;
+   if (!raised)
+   {
+      (void) hipFuncSetAttribute((const void *) (spmv_rs_mv_kernel<NV, OP, KP>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      (void) hipGetLastError();
+      raised = true;
+   }
+   const int grid = plan->d_rs_perm ? plan->rs_blocks : ((plan->rs_blocks + 63) / 64) * 64;
+   hipLaunchKernelGGL((spmv_rs_mv_kernel<NV, OP, KP>), dim3(grid), dim3(SPMV_THREADS), lds, s, a, plan->d_rs_desc, plan->d_rs_perm, plan->d_rs_hdr,
+                      plan->d_rs_meta, plan->d_rs_val, plan->d_rs_idx, plan->rs_blocks, plan->num_rows, plan->rs_rows, plan->rs_w, stage_elems,
+                      xstride, bstride, ystride, auxstride);
+}
+template <int NV, int OP>
+static void launch_rs_mv(const SpmvPlan *plan, const SpmvArgs &a, int stage_elems, size_t lds, long xstride, long bstride, long ystride,
+                         long auxstride, hipStream_t s)
+{
+   switch (plan->rs_kp)
+   {
+      case 8:  launch_rs_mv_form<NV, OP, 8>(plan, a, stage_elems, lds, xstride, bstride, ystride, auxstride, s); break;
+      case 16: launch_rs_mv_form<NV, OP, 16>(plan, a, stage_elems, lds, xstride, bstride, ystride, auxstride, s); break;
+      case 24: launch_rs_mv_form<NV, OP, 24>(plan, a, stage_elems, lds, xstride, bstride, ystride, auxstride, s); break;
+      default: launch_rs_mv_form<NV, OP, 32>(plan, a, stage_elems, lds, xstride, bstride, ystride, auxstride, s); break;
+   }
+}
+static inline size_t rs_mv_lds_bytes(const SpmvPlan *plan, int nv, int &stage_elems)
+{
+   stage_elems = 2 * plan->rs_units + 8;
+   return sizeof(double) * (size_t) nv * (size_t) (stage_elems + SPMV_THREADS);
+}
+// columns per pass of the row-slice multivector kernel (HYPRE_AMD_SPMV_RS_MV_COLS: 2, 3 or 4; for measurements)
+static int rs_mv_columns()
+{
+   static const int c = [] { const char *e = getenv("HYPRE_AMD_SPMV_RS_MV_COLS"); const int v = e ? atoi(e) : 0; return (v >= 2 && v <= 4) ? v : 0; }();
+   return c;
 }
 
 constexpr int MV_WIN = 2320;        // SPMV_TILE + SPMV_THREADS entries of a window and its spill, a multiple of 16
@@ -2925,76 +3126,138 @@ static inline size_t mv_lds_bytes(const SpmvPlan *plan, int nv, bool coded, int 
           sizeof(int) * (size_t) ((rp_cap + 4) & ~3) + (coded ? sizeof(double) * (size_t) ((ndict + 1) & ~1) : 0);
 }
 
-bool spmv_mv_serves(const SpmvPlan *plan, const SpmvArgs &args, long xstride)
+// The multivector form of the kernel launch_spmv would pick for this plan and these operands: 0 none (the pass runs column by
+// column on the single-vector kernel), 1 row slices, 2 slice form, 3 x-staged tiles.  A column's bits are those of its
+// single-vector launch only when the form is the same: the forms differ in the association of a row's sum.
+enum { MV_NONE = 0, MV_RS = 1, MV_SL = 2, MV_XS = 3 };
+static int spmv_mv_form(const SpmvPlan *plan, const SpmvArgs &args, long xstride)
 {
-   SpmvArgs a = args;
-   if (!plan->tiled || !takes_xs(plan, a) || a.fill != HYPRE_SPMV_FILL_WHOLE || a.Aa32 || handle().fp32_values) { return false; }
-   if (plan->max_row_nnz > SPMV_THREADS || (xstride & 1) != 0 || !plan->d_tile_fp || !plan->d_stale) { return false; }
-   // nearly all tiles staged: the others gather NV columns through the cache, entry by entry
-   if ((long long) plan->xs_tiles * 10 < (long long) plan->num_tiles * 9) { return false; }
+   const SpmvArgs &a = args;
+   if (!plan->tiled || a.fill != HYPRE_SPMV_FILL_WHOLE || a.Aa32 || handle().fp32_values || a.rowmap || (xstride & 1) != 0) { return MV_NONE; }
+   if (takes_rs(plan, a))
+   {
+      int stage_elems;
+      return rs_mv_lds_bytes(plan, 2, stage_elems) <= (size_t) 160 * 1024 ? MV_RS : MV_NONE;
+   }
+   if (!takes_xs(plan, a) || !plan->d_tile_fp || !plan->d_stale) { return MV_NONE; }
    int stage_elems, rp_cap;
-   return mv_lds_bytes(plan, 2, plan->d_codes != nullptr, plan->ndict, stage_elems, rp_cap) <= (size_t) 160 * 1024;
+   if (plan->d_codes && plan->has_slice_form())
+   {
+      return sl_mv_lds_bytes(plan, 2, plan->ndict, stage_elems) <= (size_t) 160 * 1024 ? MV_SL : MV_NONE;
+   }
+   if (plan->max_row_nnz > SPMV_THREADS) { return MV_NONE; }
+   // nearly all tiles staged: the others gather NV columns through the cache, entry by entry
+   if ((long long) plan->xs_tiles * 10 < (long long) plan->num_tiles * 9) { return MV_NONE; }
+   return mv_lds_bytes(plan, 2, plan->d_codes != nullptr, plan->ndict, stage_elems, rp_cap) <= (size_t) 160 * 1024 ? MV_XS : MV_NONE;
 }
 
-bool launch_spmv_mv(const SpmvPlan *plan, const SpmvArgs &args, int nv, long xstride, long bstride, long ystride, hipStream_t s)
+template <int OP>
+static void launch_mv_group(const SpmvPlan *plan, const SpmvArgs &c, int form, int g, bool coded, int stage_elems, int rp_cap, size_t lds,
+                            long xstride, long bstride, long ystride, long auxstride, hipStream_t s)
 {
-   if (plan->num_rows <= 0 || nv < 2 || !spmv_mv_serves(plan, args, xstride)) { return false; }
+   if (form == MV_RS)
+   {
+      switch (g)
+      {
+         case 2:  launch_rs_mv<2, OP>(plan, c, stage_elems, lds, xstride, bstride, ystride, auxstride, s); break;
+         case 3:  launch_rs_mv<3, OP>(plan, c, stage_elems, lds, xstride, bstride, ystride, auxstride, s); break;
+         default: launch_rs_mv<4, OP>(plan, c, stage_elems, lds, xstride, bstride, ystride, auxstride, s); break;
+      }
+   }
+   else if (form == MV_SL)
+   {
+      switch (g)
+      {
+         case 2:  launch_sl_mv_nv<2, OP>(plan, c, stage_elems, lds, xstride, bstride, ystride, auxstride, s); break;
+         case 3:  launch_sl_mv_nv<3, OP>(plan, c, stage_elems, lds, xstride, bstride, ystride, auxstride, s); break;
+         default: launch_sl_mv_nv<4, OP>(plan, c, stage_elems, lds, xstride, bstride, ystride, auxstride, s); break;
+      }
+   }
+   else
+   {
+      switch (g)
+      {
+         case 2: if (coded) launch_xs_mv<2, true, OP>(plan, c, stage_elems, MV_WIN, rp_cap, lds, xstride, bstride, ystride, auxstride, s);
+                 else       launch_xs_mv<2, false, OP>(plan, c, stage_elems, MV_WIN, rp_cap, lds, xstride, bstride, ystride, auxstride, s); break;
+         case 3: if (coded) launch_xs_mv<3, true, OP>(plan, c, stage_elems, MV_WIN, rp_cap, lds, xstride, bstride, ystride, auxstride, s);
+                 else       launch_xs_mv<3, false, OP>(plan, c, stage_elems, MV_WIN, rp_cap, lds, xstride, bstride, ystride, auxstride, s); break;
+         default: if (coded) launch_xs_mv<4, true, OP>(plan, c, stage_elems, MV_WIN, rp_cap, lds, xstride, bstride, ystride, auxstride, s);
+                  else       launch_xs_mv<4, false, OP>(plan, c, stage_elems, MV_WIN, rp_cap, lds, xstride, bstride, ystride, auxstride, s); break;
+      }
+   }
+}
+
+bool launch_spmv_mv(const SpmvPlan *plan, const SpmvArgs &args, SpmvOp op, int nv, long xstride, long bstride, long ystride, long auxstride,
+                    hipStream_t s)
+{
+   if (plan->num_rows <= 0 || nv < 2 || (op != OP_AXPBY && op != OP_AXPBY_DIV && op != OP_JACOBI)) { return false; }
    SpmvArgs a = args;
+   // (what takes_rs / takes_xs look at is in the caller's arguments)
+   const int form = spmv_mv_form(plan, a, xstride);
+   if (form == MV_NONE) { return false; }
    a.last_quad = (plan->nnz > 0 ? (int) (plan->nnz - 1) : 0) & ~3;
    a.x_last = plan->num_cols > 0 ? plan->num_cols - 1 : 0;
    a.tile_perm = plan->d_tile_perm;
    a.tile_fp = plan->d_tile_fp;
    a.stale = plan->d_stale;
    a.nnz = plan->nnz;
-   a.Ac8 = nullptr; a.dict = nullptr; a.ndict = 0; a.dict_rounded = 0; a.use_rs = 0;
-   const bool coded = plan->d_codes != nullptr;
+   a.Ac8 = nullptr; a.dict = nullptr; a.ndict = 0; a.dict_rounded = 0; a.use_rs = form == MV_RS ? 1 : 0;
+   const bool coded = form != MV_RS && plan->d_codes != nullptr;
    if (coded) { a.Ac8 = plan->d_codes; a.ndict = plan->ndict; a.dict = plan->d_dict; }
    const double nz = (double) plan->nnz, nr = (double) plan->num_rows;
-   const double vecs = (8.0 + ((a.beta != 0.0) ? 8.0 : 0.0)) * nr + 8.0 * std::min((double) plan->num_cols, nz);     // per column: y (+ b), x
+   // bytes per column: y (+ b), x — the sweep: f and u' (u is the x read); the restriction's epilogue: u as well — and once
+   // for all columns the diagonal
+   const double xcols = 8.0 * std::min((double) plan->num_cols, nz);
+   const double vecs = (op == OP_JACOBI ? 16.0 : (op == OP_AXPBY_DIV ? 16.0 : 8.0) + ((a.beta != 0.0) ? 8.0 : 0.0)) * nr + xcols;
+   const double once = op == OP_AXPBY ? 0.0 : 8.0 * nr;
    for (int v0 = 0; v0 < nv; )
    {
-      const bool slice = coded && plan->has_slice_form();          // a lane per row (or half row), the matrix words in registers
       // columns per pass: four over the tiles (the matrix stream is what the pass saves); the slice form's matrix words are
       // few, its passes are bound by the x pieces, and a fourth staged copy costs a resident workgroup per CU: threes and twos
-      // (measured per column on the 256^3 7-point operator: 0.108 / 0.104 / 0.118 ms at 2 / 3 / 4 columns, 0.150 alone)
+      // (measured per column on the 256^3 7-point operator: 0.108 / 0.104 / 0.118 ms at 2 / 3 / 4 columns, 0.150 alone).
+      // Row slices: a block stages up to 40 KB of x per column, so every further column of a pass costs resident workgroups
+      // (4 per CU alone, 2 with two columns, 1 with three or four): twos, and a three where three columns are left
+      // (not measured yet on a device: HYPRE_AMD_SPMV_RS_MV_COLS sets the group for such measurements)
       const int left = nv - v0;
-      int g = slice ? (left == 4 ? 2 : std::min(3, left)) : std::min(4, left), stage_elems = 0, rp_cap = 0;
+      int g, stage_elems = 0, rp_cap = 0;
+      if (form == MV_SL) { g = left == 4 ? 2 : std::min(3, left); }
+      else if (form == MV_RS) { g = rs_mv_columns() ? std::min(rs_mv_columns(), left) : (left == 3 ? 3 : std::min(2, left)); }
+      else { g = std::min(4, left); }
       size_t lds = 0;
-      if (slice) { while (g > 1 && (lds = sl_mv_lds_bytes(plan, g, a.ndict, stage_elems)) > (size_t) 160 * 1024) { g--; } }
+      if (form == MV_SL) { while (g > 1 && (lds = sl_mv_lds_bytes(plan, g, a.ndict, stage_elems)) > (size_t) 160 * 1024) { g--; } }
+      else if (form == MV_RS) { while (g > 1 && (lds = rs_mv_lds_bytes(plan, g, stage_elems)) > (size_t) 160 * 1024) { g--; } }
       else { while (g > 1 && (lds = mv_lds_bytes(plan, g, coded, a.ndict, stage_elems, rp_cap)) > (size_t) 160 * 1024) { g--; } }
       SpmvArgs c = a;
       c.x = a.x + (size_t) v0 * xstride;
       c.y = a.y + (size_t) v0 * ystride;
       c.b = a.b ? a.b + (size_t) v0 * bstride : nullptr;
-      if (g == 1) { launch_spmv(plan, c, OP_AXPBY, s); v0 += 1; continue; }
-      c.rot = const_cast<SpmvPlan *>(plan)->launches++;
-      spmv_mv_launches()++;
-      // bytes: the matrix once (CSR count: 12 bytes per entry and the row pointers; streamed: what the x-staged form holds
-      // per entry and per tile), the vectors of every column
-      if (slice)
+      c.aux = a.aux ? a.aux + (size_t) v0 * auxstride : nullptr;
+      if (g == 1)
       {
-         account_bytes(nz * 12.0 + 4.0 * (nr + 1.0) + g * vecs,
-                       sl_matrix_bytes(plan, a.ndict) + g * vecs);
-         switch (g)
-         {
-            case 2:  launch_sl_mv_nv<2>(plan, c, stage_elems, lds, xstride, bstride, ystride, s); break;
-            case 3:  launch_sl_mv_nv<3>(plan, c, stage_elems, lds, xstride, bstride, ystride, s); break;
-            default: launch_sl_mv_nv<4>(plan, c, stage_elems, lds, xstride, bstride, ystride, s); break;
-         }
-         v0 += g;
+         SpmvArgs one = args;
+         one.x = c.x; one.y = c.y; one.b = c.b; one.aux = c.aux;
+         launch_spmv(plan, one, op, s);
+         v0 += 1;
          continue;
       }
-      account_bytes(nz * 12.0 + 4.0 * (nr + 1.0) + g * vecs,
-                    nz * ((coded ? 1.0 : 8.0) + 2.0) + 4.0 * (nr + 1.0) + g * vecs +
-                    (double) plan->num_tiles * (4.0 * (XS_DESC + 6) + (coded ? 8.0 * a.ndict + 4.0 * 72.0 : 0.0)));
-      switch (g)
+      c.rot = const_cast<SpmvPlan *>(plan)->launches++;
+      spmv_mv_launches()++;
+      // bytes: the matrix once (CSR count: 12 bytes per entry and the row pointers; streamed: what the form holds per entry and
+      // per tile or block), the vectors of every column
+      double streamed;
+      if (form == MV_RS) { streamed = nz * 10.0 + (double) plan->rs_blocks * (4.0 * (4 * RS_HDR + SPMV_THREADS + XS_DESC)); }
+      else if (form == MV_SL) { streamed = sl_matrix_bytes(plan, a.ndict); }
+      else
       {
-         case 2: if (coded) launch_xs_mv<2, true>(plan, c, stage_elems, MV_WIN, rp_cap, lds, xstride, bstride, ystride, s);
-                 else       launch_xs_mv<2, false>(plan, c, stage_elems, MV_WIN, rp_cap, lds, xstride, bstride, ystride, s); break;
-         case 3: if (coded) launch_xs_mv<3, true>(plan, c, stage_elems, MV_WIN, rp_cap, lds, xstride, bstride, ystride, s);
-                 else       launch_xs_mv<3, false>(plan, c, stage_elems, MV_WIN, rp_cap, lds, xstride, bstride, ystride, s); break;
-         default: if (coded) launch_xs_mv<4, true>(plan, c, stage_elems, MV_WIN, rp_cap, lds, xstride, bstride, ystride, s);
-                  else       launch_xs_mv<4, false>(plan, c, stage_elems, MV_WIN, rp_cap, lds, xstride, bstride, ystride, s); break;
+         streamed = nz * ((coded ? 1.0 : 8.0) + 2.0) + 4.0 * (nr + 1.0) +
+                    (double) plan->num_tiles * (4.0 * (XS_DESC + 6) + (coded ? 8.0 * a.ndict + 4.0 * 72.0 : 0.0));
+      }
+      account_bytes(nz * 12.0 + 4.0 * (nr + 1.0) + once + g * vecs, streamed + once + g * vecs);
+      switch (op)
+      {
+         case OP_JACOBI:    launch_mv_group<OP_JACOBI>(plan, c, form, g, coded, stage_elems, rp_cap, lds, xstride, bstride, ystride, auxstride, s); break;
+         case OP_AXPBY_DIV: launch_mv_group<OP_AXPBY_DIV>(plan, c, form, g, coded, stage_elems, rp_cap, lds, xstride, bstride, ystride, auxstride, s); break;
+         default:           launch_mv_group<OP_AXPBY>(plan, c, form, g, coded, stage_elems, rp_cap, lds, xstride, bstride, ystride, auxstride, s); break;
       }
       v0 += g;
    }

@@ -308,6 +308,13 @@ HYPRE_Int hypre_amd_BoomerAMGSetMixedPrecision(HYPRE_Solver solver, HYPRE_Int on
  * of a kernel of its own reading f_c and d_c again (par_cycle.c:340-420 runs the two as separate steps).  Same bits either
  * way; the switch is for comparisons.  on < 0 leaves the setting; returns it. */
 HYPRE_Int hypre_amd_SetCycleFusion(HYPRE_Int on);
+/* Solves of several columns (num_vectors > 1) cycle their large levels for all columns at once (default off; environment
+ * HYPRE_AMD_MULTIVECTOR_CYCLE=1): on one rank, for a V-cycle with relax 7 / 18 over all points and a direct coarsest solve,
+ * every pass over an operator of those levels is one launch for a group of 2 - 4 columns, and from the level where the
+ * one-workgroup tail or the recorded graph begins each column runs the single-column cycle.  Every column keeps the bits of
+ * its single-vector solve; every other configuration cycles column by column.  hypre_amd_SpmvSetFusedMultivectors(0) sends
+ * every pass down the column path as well.  on < 0 leaves the setting; returns it. */
+HYPRE_Int hypre_amd_SetMultivectorCycle(HYPRE_Int on);
 /* The smallest levels of a V(1,1) cycle with Jacobi / l1-Jacobi or two-stage Gauss-Seidel smoothing (relax 7 / 18 / 11 / 12,
  * no C/F ordering) and a direct
  * coarse solve in ONE kernel of one workgroup (default on; environment HYPRE_AMD_SMALL_TAIL=0): from the first level whose

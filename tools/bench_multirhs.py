@@ -1,15 +1,18 @@
 """BoomerAMG cycles on several right-hand sides at once (hypre_BoomerAMGSolve with num_vectors = NV columns) against NV
 single-vector cycles, on the benchmark's C2 problem: 7-point Laplacian, PMIS, ext+i(4), l1-Jacobi V(1,1), fp64, one GPU.
 
-    python tools/bench_multirhs.py [--grid 256] [--nv 1 2 4 8] [--cycles 10] [--warmup 3] [--pause-ms 0]
+    python tools/bench_multirhs.py [--grid 256] [--nv 1 2 4 8] [--cycles 10] [--warmup 3] [--pause-ms 0] [--fused 0 1]
 
-One JSON line per NV: ms per NV-column cycle, ms per column, NV single-vector cycles for comparison and their ratio.
-A cycle of NV columns runs the single-column cycle once per column (each column bit for bit the single-vector cycle), so
-its matrix bytes are NV times those of one cycle; the ratio shows what that costs.
+One JSON line per NV and path: ms per NV-column cycle, ms per column, NV single-vector cycles for comparison and their
+ratio, and the bytes one cycle streams (hypre_amd_ByteCounters).  --fused 0: the column loop — the single-column cycle once
+per column, its matrix bytes NV times those of one cycle; --fused 1: the large levels cycled for all columns at once
+(hypre_amd_SetMultivectorCycle), each operator read once per group of columns.  Both (the default) are measured alternately in
+one process, on the same solver; each column is bit for bit the single-vector cycle either way.
 
 --pause-ms P leaves the GPU idle for P ms before every timed loop, so that a kernel trace of the run can be cut there:
 tools/multirhs_trace_stats.py takes the launches after the last such gap, the timed cycles of the last NV."""
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -28,6 +31,7 @@ def main():
     ap.add_argument("--cycles", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--pause-ms", type=float, default=0.0)
+    ap.add_argument("--fused", type=int, nargs="+", default=[0, 1], choices=[0, 1])
     args = ap.parse_args()
     from hypre_amd import binding as B, ij
     L = B.load_library()
@@ -61,25 +65,37 @@ def main():
             step()
         L.hypre_SyncComputeStream()
         ms = 1e3 * (time.perf_counter() - t0) / args.cycles
-        return ms
+        csr, streamed = C.c_double(), C.c_double()
+        L.hypre_amd_ByteCounters(C.byref(csr), C.byref(streamed), 1)
+        step()
+        L.hypre_SyncComputeStream()
+        L.hypre_amd_ByteCounters(C.byref(csr), C.byref(streamed), 0)
+        return ms, streamed.value
 
     b1 = B.parvec_from_numpy(np.ones(n))
     u1 = B.parvec_from_numpy(np.zeros(n))
-    ms1 = timed(b1, u1)
+    ms1, bytes1 = timed(b1, u1)
+    before = L.hypre_amd_SetMultivectorCycle(-1)
     for nv in args.nv:
-        if nv == 1:
-            ms = ms1
-        else:
-            bm = B.parmultivec_from_numpy(np.repeat(np.ones(n)[:, None], nv, axis=1))
-            um = B.parmultivec_from_numpy(np.zeros((n, nv)))
-            ms = timed(bm, um)
-            L.hypre_ParVectorDestroy(bm); L.hypre_ParVectorDestroy(um)
-        print(json.dumps({
-            "metric": "BoomerAMG cycle on NV right-hand sides (%d^3 7-pt, PMIS / ext+i(4) / l1-Jacobi V(1,1), fp64)" % n1,
-            "nv": nv, "ms_per_cycle": round(ms, 4), "ms_per_column": round(ms / nv, 4),
-            "ms_nv_single_cycles": round(nv * ms1, 4), "ratio_to_nv_single": round(ms / (nv * ms1), 4),
-            "cycles": args.cycles, "levels": L.hypre_amd_BoomerAMGGetNumLevels(s),
-            "column_path": "single-column cycle per column (bitwise the single-vector cycle)"}), flush=True)
+        for fused in ([0] if nv == 1 else args.fused):
+            L.hypre_amd_SetMultivectorCycle(fused)
+            if nv == 1:
+                ms, streamed = ms1, bytes1
+            else:
+                bm = B.parmultivec_from_numpy(np.repeat(np.ones(n)[:, None], nv, axis=1))
+                um = B.parmultivec_from_numpy(np.zeros((n, nv)))
+                ms, streamed = timed(bm, um)
+                L.hypre_ParVectorDestroy(bm); L.hypre_ParVectorDestroy(um)
+            print(json.dumps({
+                "metric": "BoomerAMG cycle on NV right-hand sides (%d^3 7-pt, PMIS / ext+i(4) / l1-Jacobi V(1,1), fp64)" % n1,
+                "nv": nv, "fused": fused, "ms_per_cycle": round(ms, 4), "ms_per_column": round(ms / nv, 4),
+                "ms_nv_single_cycles": round(nv * ms1, 4), "ratio_to_nv_single": round(ms / (nv * ms1), 4),
+                "gb_streamed_per_cycle": round(streamed / 1e9, 3),
+                "cycles": args.cycles, "levels": L.hypre_amd_BoomerAMGGetNumLevels(s),
+                "column_path": "large levels for all columns at once, the tail per column" if fused else
+                               "single-column cycle per column",
+                "bits": "every column bitwise the single-vector cycle"}), flush=True)
+    L.hypre_amd_SetMultivectorCycle(before)
     L.hypre_ParVectorDestroy(b1); L.hypre_ParVectorDestroy(u1)
     L.HYPRE_BoomerAMGDestroy(s)
 
