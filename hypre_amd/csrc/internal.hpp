@@ -314,6 +314,7 @@ bool spmv_with_scaled_quotient(hypre_CSRMatrix *M, const double *x, double *y, d
 // over the columns
 bool launch_spmv_mv(const SpmvPlan *plan, const SpmvArgs &args, SpmvOp op, int nv, long xstride, long bstride, long ystride, long auxstride,
                     hipStream_t s);
+struct MvStrides { long x, b, y, aux; };     // doubles between two columns of x, b, y, aux: how the multivector kernels take them
 // the passes of a cycle over nv columns (seq_mv.cpp): the fused launch where it serves, else the single-vector call per column
 void spmv_columns(HYPRE_Complex alpha, hypre_CSRMatrix *A, const double *x, size_t xstride, HYPRE_Complex beta, const double *b,
                   size_t bstride, double *y, size_t ystride, int nv);

@@ -467,7 +467,62 @@ __device__ __forceinline__ RowOps tile_row_ops(const SpmvArgs &p, int r0, int nr
    return load_row_ops<OP>(p, max(r0 + rr, 0));
 }
 
-// One workgroup per tile, in dispatch order (or a re-mapped order, see xcd_map).
+// ---- steps the kernel families share (DESIGN.md section 4 lists who calls what).  Loops and address arithmetic only: the
+// fences, barriers and early returns that fix the order of issue stay in the kernels, where their comments are.
+// The tile of this workgroup, negative when it has none.  Workgroups are dealt round-robin over the 8 XCDs (workgroup g ->
+// XCD g % 8), each XCD with its own L2.  xcd_map > 0: every XCD takes chunks of xcd_map consecutive tiles; xcd_map < 0
+// (EIGHTHS only): one contiguous eighth of the tiles per XCD.  Speed only: any placement is correct.
+// The grid may be padded past num_tiles (launch_tiled_gt): a padding workgroup must leave before it touches the placement
+// table, which holds num_tiles entries.  Every tile is visited exactly once — the in-place epilogues (OP_TSGS adds into aux,
+// OP_AXPBY with b == y) rely on it — so a table entry outside [0, num_tiles) is dropped too.
+// EIGHTHS = false is spmv_xs_mv_kernel, which never had the third mapping and whose launches can see a negative xcd_map (it
+// is HYPRE_AMD_SPMV_XCD as the caller's spmv_default_flags read it): such a launch keeps dispatch order, as before.
+template <bool EIGHTHS>
+__device__ __forceinline__ int tile_of_workgroup(const int *__restrict__ tile_perm, int xcd_map, int num_tiles)
+{
+   int tile = (int) blockIdx.x;
+   if (tile_perm) { tile = tile < num_tiles ? tile_perm[tile] : -1; }
+   else if (xcd_map > 0)
+   {
+      const int g = blockIdx.x >> 3, c = blockIdx.x & 7, C = xcd_map;
+      tile = (g / C) * (8 * C) + c * C + (g % C);
+   }
+   else if (EIGHTHS && xcd_map < 0) { tile = (blockIdx.x & 7) * ((num_tiles + 7) >> 3) + (blockIdx.x >> 3); }
+   return (unsigned) tile < (unsigned) num_tiles ? tile : -1;
+}
+// the block of this workgroup (slice and row-slice forms), negative when it has none: the plan's placement table, else runs
+// of 8 blocks per XCD
+__device__ __forceinline__ int block_of_workgroup(const int *__restrict__ block_perm, int blocks)
+{
+   int block = (int) blockIdx.x;
+   if (block_perm) { block = block < blocks ? block_perm[block] : -1; }
+   else { const int g = block >> 3, c = block & 7; block = (g >> 3) * 64 + c * 8 + (g & 7); }
+   return (unsigned) block < (unsigned) blocks ? block : -1;
+}
+// what the plan's fingerprint tables hold: two entries of the column array, mixed (written by build_fp_kernel and
+// sl_fp_kernel, compared by every kernel that does not read the columns)
+__host__ __device__ inline int plan_fingerprint(int c0, int c1) { return (int) ((unsigned) c0 * 2654435761u + (unsigned) c1); }
+// the plan no longer describes the matrix it is launched with
+__device__ __forceinline__ void mark_stale(const SpmvArgs &p) { __hip_atomic_fetch_or(p.stale, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+// Row pointers of a tile, one per lane and pass: loaded unconditionally (clamped to lim = min(nrows, rp_cap); lanes past
+// the tile's rows repeat its last pointer into the last slot) and stored afterwards — a conditional load-and-store makes
+// the compiler wait for everything in flight before each store: three more round trips per tile
+constexpr int RPJ = (RP_CAP + SPMV_THREADS) / SPMV_THREADS;
+struct TileRowPtrs { int v[RPJ]; };
+__device__ __forceinline__ TileRowPtrs load_tile_row_ptrs(const int *__restrict__ Ai, int r0, int lim, int tid)
+{
+   TileRowPtrs q;
+#pragma unroll
+   for (int j = 0; j < RPJ; j++) { q.v[j] = Ai[r0 + min(tid + j * SPMV_THREADS, lim)]; }
+   return q;
+}
+__device__ __forceinline__ void park_tile_row_ptrs(int *rp, const TileRowPtrs &q, int lim, int tid)
+{
+#pragma unroll
+   for (int j = 0; j < RPJ; j++) { rp[min(tid + j * SPMV_THREADS, lim)] = q.v[j]; }
+}
+
+// One workgroup per tile, in dispatch order (or a re-mapped order, see tile_of_workgroup).
 template <int OP, bool F32, bool HASFILL, bool GT>
 __global__ __launch_bounds__(SPMV_THREADS)
 void spmv_tiled_kernel(SpmvArgs p, const int *__restrict__ tile_row, const int *__restrict__ tile_k,
@@ -478,29 +533,8 @@ void spmv_tiled_kernel(SpmvArgs p, const int *__restrict__ tile_row, const int *
    double *rowsum = prod + prod_elems;                                 // [rowsum_elems]
    int    *rp     = reinterpret_cast<int *>(rowsum + rowsum_elems);    // [rp_cap + 1]
 
-   // Workgroups are dealt round-robin over the 8 XCDs (workgroup g -> XCD g % 8),
-   // each XCD with its own L2.  xcd_map > 0: every XCD takes chunks of xcd_map
-   // consecutive tiles; xcd_map < 0: one contiguous eighth of the tiles per XCD.
-   // Speed only: any placement is correct.
-   // The grid may be padded past num_tiles (launch_tiled_gt): a padding workgroup must leave before it touches the
-   // placement table, which holds num_tiles entries.  Every tile is visited exactly once — the in-place epilogues
-   // (OP_TSGS adds into aux, OP_AXPBY with b == y) rely on it — so a table entry outside [0, num_tiles) is dropped too.
-   int tile = (int) blockIdx.x;
-   if (p.tile_perm)
-   {
-      if (tile >= num_tiles) { return; }
-      tile = p.tile_perm[tile];
-   }
-   else if (p.xcd_map > 0)
-   {
-      const int g = blockIdx.x >> 3, c = blockIdx.x & 7, C = p.xcd_map;
-      tile = (g / C) * (8 * C) + c * C + (g % C);
-   }
-   else if (p.xcd_map < 0)
-   {
-      tile = (blockIdx.x & 7) * ((num_tiles + 7) >> 3) + (blockIdx.x >> 3);
-   }
-   if ((unsigned) tile >= (unsigned) num_tiles) { return; }
+   const int tile = tile_of_workgroup<true>(p.tile_perm, p.xcd_map, num_tiles);
+   if (tile < 0) { return; }
 
    // The tile's entries [k0, k1) start inside [tile*TILE, tile*TILE + longest row): the first
    // TILE entries from tile*TILE on are requested before the tile's bounds are known, so the
@@ -600,6 +634,52 @@ __host__ __device__ inline size_t xs_dict_offset(int prod_elems, int rowsum_elem
 {
    return (sizeof(double) * (size_t) (prod_elems + rowsum_elems) + sizeof(int) * (size_t) (rp_cap + 4) + 15) & ~(size_t) 15;
 }
+// this wave's piece descriptors of tile or block `unit` (wave-uniform: they arrive through the scalar cache)
+struct XPieces { int start[XS_WSEG], ol[XS_WSEG]; };      // unsigned first column; LDS byte offset << 16 | lanes
+__device__ __forceinline__ XPieces wave_x_pieces(const int *__restrict__ desc, int unit, int wave)
+{
+   const int *dsc = desc + (size_t) unit * XS_DESC + XS_WSEG * wave;
+   XPieces pc;
+#pragma unroll
+   for (int j = 0; j < XS_WSEG; j++) { pc.start[j] = dsc[j]; pc.ol[j] = dsc[XS_SEGS + j]; }
+   return pc;
+}
+// The x pieces of NV columns (xstride doubles apart) into NV staged copies (stage_elems doubles apart), written straight
+// into LDS: at most 128 doubles a piece, one 16-byte load per lane (global_load_lds: no registers, no ds_write pass; the
+// LDS address is the piece's base + 16 * lane, which is exactly how a piece is laid out).  A piece starts at an even
+// column and x is 16-byte aligned, so a lane's 16 bytes never straddle a page: when x has an odd length the upper
+// half of its last pair is read (not used) but cannot fault.  With NV = 1 the stride terms fold away.
+// (the plan keeps what a slot needs as it needs it: the piece's LDS offset in bytes, its length in lanes, an unsigned first
+// column — a slot is a dozen instructions per wave whether it loads or not)
+template <int NV, int SLOTS = XS_WSEG>
+__device__ __forceinline__ void stage_x_pieces(const double *x, long xstride, double *xs, int stage_elems, const XPieces &pc, int lane)
+{
+#pragma unroll
+   for (int v = 0; v < NV; v++)
+   {
+#pragma unroll
+      for (int j = 0; j < SLOTS; j++)
+      {
+         const unsigned offb = (unsigned) pc.ol[j] >> 16, lanes = (unsigned) pc.ol[j] & 0xffffu;
+         if ((unsigned) lane < lanes)
+         {
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) (x + (size_t) v * xstride + (size_t) (unsigned) pc.start[j] + 2 * lane),
+                                             (__attribute__((address_space(3))) void *) (reinterpret_cast<char *>(xs + (size_t) v * stage_elems) + offb), 16, 0, 0);
+         }
+      }
+   }
+}
+// the value table of a coded matrix into LDS the same way: 16 bytes per lane, in the same trip as the x pieces (the table is
+// allocated, and readable, up to DICT_CAP entries whatever it holds)
+__device__ __forceinline__ void stage_value_table(const double *dict, int ndict, const double *dictl, int wave, int lane)
+{
+   const int dl = (ndict + 1) >> 1;                   // lanes the table takes
+   if (lane < dl - 64 * wave)
+   {
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) (dict + 128 * wave + 2 * lane),
+                                       (__attribute__((address_space(3))) void *) (reinterpret_cast<char *>(const_cast<double *>(dictl)) + 1024 * wave), 16, 0, 0);
+   }
+}
 
 template <int OP, int VF, bool HASFILL>
 __global__ __launch_bounds__(SPMV_THREADS)
@@ -615,19 +695,8 @@ void spmv_xs_kernel(SpmvArgs p, const int *__restrict__ tile_row, const int *__r
    int    *rp     = reinterpret_cast<int *>(rowsum + rowsum_elems);
    const double *dictl = reinterpret_cast<const double *>(smem_raw + xs_dict_offset(prod_elems, rowsum_elems, rp_cap));   // CODED only
 
-   int tile = (int) blockIdx.x;
-   if (p.tile_perm)
-   {
-      if (tile >= num_tiles) { return; }
-      tile = p.tile_perm[tile];
-   }
-   else if (p.xcd_map > 0)
-   {
-      const int g = blockIdx.x >> 3, c = blockIdx.x & 7, C = p.xcd_map;
-      tile = (g / C) * (8 * C) + c * C + (g % C);
-   }
-   else if (p.xcd_map < 0) { tile = (blockIdx.x & 7) * ((num_tiles + 7) >> 3) + (blockIdx.x >> 3); }
-   if ((unsigned) tile >= (unsigned) num_tiles) { return; }
+   const int tile = tile_of_workgroup<true>(p.tile_perm, p.xcd_map, num_tiles);
+   if (tile < 0) { return; }
 
    const int tid = threadIdx.x, lane = tid & 63;
    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -662,10 +731,7 @@ void spmv_xs_kernel(SpmvArgs p, const int *__restrict__ tile_row, const int *__r
    }
    const v2i lA = stream_load<v2i>(lidx + qA), lB = stream_load<v2i>(lidx + qB);
 #endif
-   const int *dsc = xs_desc + (size_t) tile * XS_DESC + XS_WSEG * wave;
-   int seg_start[XS_WSEG], seg_ol[XS_WSEG];
-#pragma unroll
-   for (int j = 0; j < XS_WSEG; j++) { seg_start[j] = dsc[j]; seg_ol[j] = dsc[XS_SEGS + j]; }
+   const XPieces pc = wave_x_pieces(xs_desc, tile, wave);
    const int r0 = tile_row[tile], r1 = tile_row[tile + 1];
    const int k0 = tile_k[tile], k1 = tile_k[tile + 1];
    const int xc = xs_cnt[tile];                // (covered units << 8) | pieces
@@ -694,22 +760,8 @@ void spmv_xs_kernel(SpmvArgs p, const int *__restrict__ tile_row, const int *__r
    }
    asm volatile("" :: "s"(tile_row), "s"(tile_k), "s"(xs_cnt), "s"(xs_desc), "s"(lidx), "s"(p.Aa), "s"(p.Aa32), "s"(p.Aj), "s"(p.tile_fp), "s"(p.Ac8) : "memory");
    if (r1 <= r0) { return; }
-   {
-      const bool off = fp_plan != (int) ((unsigned) fc0 * 2654435761u + (unsigned) fc1);
-      if (off && tid == 0) { __hip_atomic_fetch_or(p.stale, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
-   }
-   if (CODED)
-   {
-      // the value table: 16 bytes per lane straight into LDS, in the same trip as the stream (the table is allocated, and
-      // readable, up to DICT_CAP entries whatever it holds)
-      const int dl = (p.ndict + 1) >> 1;                   // lanes the table takes
-      const int mine = dl - 64 * wave;
-      if (lane < mine)
-      {
-         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) (p.dict + 128 * wave + 2 * lane),
-                                          (__attribute__((address_space(3))) void *) (reinterpret_cast<char *>(const_cast<double *>(dictl)) + 1024 * wave), 16, 0, 0);
-      }
-   }
+   if (fp_plan != plan_fingerprint(fc0, fc1) && tid == 0) { mark_stale(p); }
+   if (CODED) { stage_value_table(p.dict, p.ndict, dictl, wave, lane); }      // in the same trip as the stream
 #if !XS_EARLY_STREAM
    if (CODED)
    {
@@ -738,16 +790,9 @@ void spmv_xs_kernel(SpmvArgs p, const int *__restrict__ tile_row, const int *__r
       S.cA = stream_load<v4i>(p.Aj + qA);
       S.cB = stream_load<v4i>(p.Aj + qB);
       stream_issue_spill<F32>(p, ka, k1, S);
-      // row pointers: loaded unconditionally (clamped) and stored afterwards — a conditional load-and-store here makes
-      // the compiler wait for everything in flight before each store: three more round trips per tile
       {
-         constexpr int RPJ = (RP_CAP + SPMV_THREADS) / SPMV_THREADS;
          const int lim = min(nrows, rp_cap);
-         int rpv[RPJ];
-#pragma unroll
-         for (int j = 0; j < RPJ; j++) { rpv[j] = p.Ai[r0 + min(tid + j * SPMV_THREADS, lim)]; }
-#pragma unroll
-         for (int j = 0; j < RPJ; j++) { rp[min(tid + j * SPMV_THREADS, lim)] = rpv[j]; }
+         park_tile_row_ptrs(rp, load_tile_row_ptrs(p.Ai, r0, lim, tid), lim, tid);
       }
       const RowOps ops = tile_row_ops<OP>(p, r0, nrows);
       if (CODED)
@@ -757,57 +802,34 @@ void spmv_xs_kernel(SpmvArgs p, const int *__restrict__ tile_row, const int *__r
          __syncthreads();
          S.vA01.x = dictl[cdA & 0xff]; S.vA01.y = dictl[(cdA >> 8) & 0xff]; S.vA23.x = dictl[(cdA >> 16) & 0xff]; S.vA23.y = dictl[cdA >> 24];
          S.vB01.x = dictl[cdB & 0xff]; S.vB01.y = dictl[(cdB >> 8) & 0xff]; S.vB23.x = dictl[(cdB >> 16) & 0xff]; S.vB23.y = dictl[cdB >> 24];
-         if (__double_as_longlong(dictl[ckc]) != __double_as_longlong(p.dict_rounded ? (double) (float) ckv : ckv))
-         {
-            __hip_atomic_fetch_or(p.stale, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-         }
+         if (__double_as_longlong(dictl[ckc]) != __double_as_longlong(p.dict_rounded ? (double) (float) ckv : ckv)) { mark_stale(p); }
          if (p.dict_rounded) { S.vC = (double) (float) S.vC; }
       }
       stream_consume_gt<F32>(p, k0, k1, ka, S, prod);
       __syncthreads();
-      if (F32 && (float) ckv != ckf) { __hip_atomic_fetch_or(p.stale, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+      if (F32 && (float) ckv != ckf) { mark_stale(p); }
       tile_reduce<OP, HASFILL>(p, r0, nrows, k0, k1, ka, prod, rowsum, rp, rp_cap, ops);
       return;
    }
 
-   // x pieces (at most 128 doubles each: one 16-byte load per lane), requested in the same trip through the memory
-   // pipeline as the stream above and written straight into LDS (global_load_lds: no registers, no ds_write pass; the
-   // LDS address is the piece's base + 16 * lane, which is exactly how a piece is laid out).  A piece starts at an even
-   // column and x is 16-byte aligned, so a lane's 16 bytes never straddle a page: when x has an odd length the upper
-   // half of its last pair is read (not used) but cannot fault.
-#pragma unroll
-   for (int j = 0; j < (XS_WSEG < XS_EXP_SLOTS ? XS_WSEG : XS_EXP_SLOTS); j++)
-   {
-      // (the plan keeps what the slot needs as it needs it: the piece's LDS offset in bytes, its length in lanes, an
-      // unsigned first column — a slot is a dozen instructions per wave whether it loads or not)
-      const unsigned offb = (unsigned) seg_ol[j] >> 16, lanes = (unsigned) seg_ol[j] & 0xffffu;
-      if ((unsigned) lane < lanes)
-      {
-         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) (p.x + (size_t) (unsigned) seg_start[j] + 2 * lane),
-                                          (__attribute__((address_space(3))) void *) (reinterpret_cast<char *>(prod) + offb), 16, 0, 0);
-      }
-   }
+   // x pieces, requested in the same trip through the memory pipeline as the stream above (stage_x_pieces)
+   stage_x_pieces<1, (XS_WSEG < XS_EXP_SLOTS ? XS_WSEG : XS_EXP_SLOTS)>(p.x, 0, prod, 0, pc, lane);
    // spill of the tile's last row past the window (one entry per lane), row pointers, epilogue operands: same trip
    const int kC = ka + 8 * SPMV_THREADS + tid;
    const int qC = kC < k1 ? kC : min(ka + 8 * SPMV_THREADS, p.last_quad);
    const unsigned lC = lidx[qC];
    unsigned cdC = 0;
    if (CODED) { cdC = p.Ac8[qC]; } else { S.vC = F32 ? (double) p.Aa32[qC] : p.Aa[qC]; }
-   constexpr int RPJ = (RP_CAP + SPMV_THREADS) / SPMV_THREADS;
    const int lim = min(nrows, rp_cap);
-   int rpv[RPJ];
-#pragma unroll
-   for (int j = 0; j < RPJ; j++) { rpv[j] = p.Ai[r0 + min(tid + j * SPMV_THREADS, lim)]; }
+   const TileRowPtrs rpv = load_tile_row_ptrs(p.Ai, r0, lim, tid);
    const RowOps ops = tile_row_ops<OP>(p, r0, nrows);
    // the operands of a second row per lane (tiles of short rows), where the registers allow: unconditional, clamped
    // (y = alpha A x + beta b: one operand; the sweeps' three do not fit 64 registers beside the fp64 or coded stream)
    constexpr bool OPS2 = XS_OPS2 && !HASFILL && (OP == OP_AXPBY || (OP == OP_JACOBI && VF == VF_F32));
    RowOps ops2 = ops;
    if (OPS2) { ops2 = load_row_ops<OP>(p, max(r0 + min(tid + SPMV_THREADS, nrows - 1), 0)); }
-   // lanes past the tile's rows repeat its last pointer into the last slot
-#pragma unroll
-   for (int j = 0; j < RPJ; j++) { rp[min(tid + j * SPMV_THREADS, lim)] = rpv[j]; }
-   if (tid == 0 && rpv[0] != k0) { __hip_atomic_fetch_or(p.stale, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }   // the tile table is not this matrix's
+   park_tile_row_ptrs(rp, rpv, lim, tid);
+   if (tid == 0 && rpv.v[0] != k0) { mark_stale(p); }   // the tile table is not this matrix's
    __syncthreads();
    XS_STAMP(2);
 
@@ -823,14 +845,11 @@ void spmv_xs_kernel(SpmvArgs p, const int *__restrict__ tile_row, const int *__r
       lo0.x = dictl[cdA & 0xff] * xa0; lo0.y = dictl[(cdA >> 8) & 0xff] * xa1; hi0.x = dictl[(cdA >> 16) & 0xff] * xa2; hi0.y = dictl[cdA >> 24] * xa3;
       lo1.x = dictl[cdB & 0xff] * xb0; lo1.y = dictl[(cdB >> 8) & 0xff] * xb1; hi1.x = dictl[(cdB >> 16) & 0xff] * xb2; hi1.y = dictl[cdB >> 24] * xb3;
       S.vC = dictl[cdC];
-      if (__double_as_longlong(dictl[ckc]) != __double_as_longlong(p.dict_rounded ? (double) (float) ckv : ckv))
-      {
-         __hip_atomic_fetch_or(p.stale, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
+      if (__double_as_longlong(dictl[ckc]) != __double_as_longlong(p.dict_rounded ? (double) (float) ckv : ckv)) { mark_stale(p); }
    }
    else if (F32)
    {
-      if ((float) ckv != ckf) { __hip_atomic_fetch_or(p.stale, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+      if ((float) ckv != ckf) { mark_stale(p); }
       lo0.x = (double) S.fA.x * xa0; lo0.y = (double) S.fA.y * xa1; hi0.x = (double) S.fA.z * xa2; hi0.y = (double) S.fA.w * xa3;
       lo1.x = (double) S.fB.x * xb0; lo1.y = (double) S.fB.y * xb1; hi1.x = (double) S.fB.z * xb2; hi1.y = (double) S.fB.w * xb3;
    }
@@ -903,7 +922,7 @@ struct MvOps
    double b[NV], x[NV], d;
 };
 template <int NV, int OP>
-__device__ __forceinline__ void mv_load_ops(MvOps<NV> &o, const SpmvArgs &p, int row, long xstride, long bstride)
+__device__ __forceinline__ void mv_load_ops(MvOps<NV> &o, const SpmvArgs &p, int row, MvStrides st)
 {
    o.d = 1.0;
 #pragma unroll
@@ -912,20 +931,20 @@ __device__ __forceinline__ void mv_load_ops(MvOps<NV> &o, const SpmvArgs &p, int
    {
       o.d = p.d[row];
 #pragma unroll
-      for (int v = 0; v < NV; v++) { o.b[v] = p.b[(size_t) v * bstride + row]; o.x[v] = p.x[(size_t) v * xstride + row]; }
+      for (int v = 0; v < NV; v++) { o.b[v] = p.b[(size_t) v * st.b + row]; o.x[v] = p.x[(size_t) v * st.x + row]; }
    }
    else
    {
       if (p.beta != 0.0)
       {
 #pragma unroll
-         for (int v = 0; v < NV; v++) { o.b[v] = p.b[(size_t) v * bstride + row]; }
+         for (int v = 0; v < NV; v++) { o.b[v] = p.b[(size_t) v * st.b + row]; }
       }
       if (OP == OP_AXPBY_DIV) { o.d = p.d[row]; }
    }
 }
 template <int NV, int OP>
-__device__ __forceinline__ void mv_epilogue(const SpmvArgs &p, int row, const double *sum, const MvOps<NV> &o, long ystride, long auxstride)
+__device__ __forceinline__ void mv_epilogue(const SpmvArgs &p, int row, const double *sum, const MvOps<NV> &o, MvStrides st)
 {
 #pragma unroll
    for (int v = 0; v < NV; v++)
@@ -933,14 +952,14 @@ __device__ __forceinline__ void mv_epilogue(const SpmvArgs &p, int row, const do
       if (OP == OP_JACOBI)
       {
          const double t = __fma_rn(p.alpha, o.b[v], -__dmul_rn(p.alpha, sum[v]));
-         p.y[(size_t) v * ystride + row] = __dadd_rn(o.x[v], t / o.d);
+         p.y[(size_t) v * st.y + row] = __dadd_rn(o.x[v], t / o.d);
       }
       else
       {
          double r = __dmul_rn(p.alpha, sum[v]);
          if (p.beta != 0.0) { r = __fma_rn(p.beta, o.b[v], r); }
-         p.y[(size_t) v * ystride + row] = r;
-         if (OP == OP_AXPBY_DIV) { p.aux[(size_t) v * auxstride + row] = __dmul_rn(p.scale2, r) / o.d; }
+         p.y[(size_t) v * st.y + row] = r;
+         if (OP == OP_AXPBY_DIV) { p.aux[(size_t) v * st.aux + row] = __dmul_rn(p.scale2, r) / o.d; }
       }
    }
 }
@@ -948,8 +967,7 @@ __device__ __forceinline__ void mv_epilogue(const SpmvArgs &p, int row, const do
 template <int NV, bool CODED, int W, int OP>
 __device__ __forceinline__ void mv_row_sums(const SpmvArgs &p, int r0, int nrows, int ka, int rp_cap, bool staged, int stage_elems,
                                             const double *xsv, const double *valS, const unsigned char *cdS, const double *dictl,
-                                            const unsigned short *liS, const int *rp, long xstride, long bstride, long ystride,
-                                            long auxstride, const MvOps<NV> &ops)
+                                            const unsigned short *liS, const int *rp, MvStrides st, const MvOps<NV> &ops)
 {
    constexpr int MB = 4;                     // entries a lane has in flight (values, indices, then NV x each): the additions keep their order
    const int G = (int) blockDim.x / W;       // rows a pass takes (the workgroup may have more lanes than the 256 that stream the tile)
@@ -1003,7 +1021,7 @@ __device__ __forceinline__ void mv_row_sums(const SpmvArgs &p, int r0, int nrows
             for (int i = 0; i < MB; i++)
             {
 #pragma unroll
-               for (int v = 0; v < NV; v++) { xv[i][v] = p.x[(size_t) v * xstride + c[i]]; }
+               for (int v = 0; v < NV; v++) { xv[i][v] = p.x[(size_t) v * st.x + c[i]]; }
             }
          }
 #pragma unroll
@@ -1029,12 +1047,12 @@ __device__ __forceinline__ void mv_row_sums(const SpmvArgs &p, int r0, int nrows
       if (live && sub == 0)
       {
          // the row's operands: fetched early for the row of a lane's own number, else here
-         if (W == 1 && rr == tid) { mv_epilogue<NV, OP>(p, row, sum, ops, ystride, auxstride); }
+         if (W == 1 && rr == tid) { mv_epilogue<NV, OP>(p, row, sum, ops, st); }
          else
          {
             MvOps<NV> o;
-            mv_load_ops<NV, OP>(o, p, row, xstride, bstride);
-            mv_epilogue<NV, OP>(p, row, sum, o, ystride, auxstride);
+            mv_load_ops<NV, OP>(o, p, row, st);
+            mv_epilogue<NV, OP>(p, row, sum, o, st);
          }
       }
    }
@@ -1045,8 +1063,7 @@ template <int NV, bool CODED, int OP>
 __global__ __launch_bounds__(MV_THREADS_MAX)
 void spmv_xs_mv_kernel(SpmvArgs p, const int *__restrict__ tile_row, const int *__restrict__ tile_k,
                        const int *__restrict__ xs_cnt, const int *__restrict__ xs_desc, const unsigned short *__restrict__ lidx,
-                       int num_tiles, int stage_elems, int win_elems, int rp_cap, int xs_units, long xstride, long bstride, long ystride,
-                       long auxstride)
+                       int num_tiles, int stage_elems, int win_elems, int rp_cap, int xs_units, MvStrides st)
 {
    extern __shared__ __align__(16) unsigned char smem_raw[];
    double *xsv  = reinterpret_cast<double *>(smem_raw);                               // NV staged copies of x, stage_elems each
@@ -1056,18 +1073,8 @@ void spmv_xs_mv_kernel(SpmvArgs p, const int *__restrict__ tile_row, const int *
    int *rp = reinterpret_cast<int *>(liS + win_elems);
    const double *dictl = reinterpret_cast<const double *>(rp + ((rp_cap + 4) & ~3));  // CODED only
 
-   int tile = (int) blockIdx.x;
-   if (p.tile_perm)
-   {
-      if (tile >= num_tiles) { return; }
-      tile = p.tile_perm[tile];
-   }
-   else if (p.xcd_map > 0)
-   {
-      const int g = blockIdx.x >> 3, c = blockIdx.x & 7, C = p.xcd_map;
-      tile = (g / C) * (8 * C) + c * C + (g % C);
-   }
-   if ((unsigned) tile >= (unsigned) num_tiles) { return; }
+   const int tile = tile_of_workgroup<false>(p.tile_perm, p.xcd_map, num_tiles);      // (no eighths: see there)
+   if (tile < 0) { return; }
 
    const int tid = threadIdx.x, lane = tid & 63;
    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1080,7 +1087,7 @@ void spmv_xs_mv_kernel(SpmvArgs p, const int *__restrict__ tile_row, const int *
    unsigned cdA = 0, cdB = 0;
    v2d vA01 = {0.0, 0.0}, vA23 = {0.0, 0.0}, vB01 = {0.0, 0.0}, vB23 = {0.0, 0.0};
    v2i lA = {0, 0}, lB = {0, 0};
-   int seg_start[XS_WSEG], seg_ol[XS_WSEG];
+   XPieces pc;
    int fp_plan = 0, fc0 = 0, fc1 = 0;
    double   ckv = 0.0;
    unsigned ckc = 0;
@@ -1097,9 +1104,7 @@ void spmv_xs_mv_kernel(SpmvArgs p, const int *__restrict__ tile_row, const int *
          vB01 = stream_load<v2d>(p.Aa + qB); vB23 = stream_load<v2d>(p.Aa + qB + 2);
       }
       lA = stream_load<v2i>(lidx + qA); lB = stream_load<v2i>(lidx + qB);
-      const int *dsc = xs_desc + (size_t) tile * XS_DESC + XS_WSEG * wave;
-#pragma unroll
-      for (int j = 0; j < XS_WSEG; j++) { seg_start[j] = dsc[j]; seg_ol[j] = dsc[XS_SEGS + j]; }
+      pc = wave_x_pieces(xs_desc, tile, wave);
       const int qs0 = min(ka + 5, p.last_quad), qs1 = min(ka + 1029, p.last_quad);
       fp_plan = p.tile_fp[tile];
       fc0 = p.Aj[qs0]; fc1 = p.Aj[qs1];
@@ -1121,41 +1126,14 @@ void spmv_xs_mv_kernel(SpmvArgs p, const int *__restrict__ tile_row, const int *
    const bool staged = nseg != 0;
    if (streamer)
    {
-      {
-         const bool off = fp_plan != (int) ((unsigned) fc0 * 2654435761u + (unsigned) fc1);
-         if (off && tid == 0) { __hip_atomic_fetch_or(p.stale, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
-      }
-      if (CODED)
-      {
-         const int dl = (p.ndict + 1) >> 1;
-         if (lane < dl - 64 * wave)
-         {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) (p.dict + 128 * wave + 2 * lane),
-                                             (__attribute__((address_space(3))) void *) (reinterpret_cast<char *>(const_cast<double *>(dictl)) + 1024 * wave), 16, 0, 0);
-         }
-      }
-      if (staged)
-      {
-         // the x pieces of every column: NV copies of the tile's staging area, one after the other
-#pragma unroll
-         for (int v = 0; v < NV; v++)
-         {
-#pragma unroll
-            for (int j = 0; j < XS_WSEG; j++)
-            {
-               const unsigned offb = (unsigned) seg_ol[j] >> 16, lanes = (unsigned) seg_ol[j] & 0xffffu;
-               if ((unsigned) lane < lanes)
-               {
-                  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) (p.x + (size_t) v * xstride + (size_t) (unsigned) seg_start[j] + 2 * lane),
-                                                   (__attribute__((address_space(3))) void *) (reinterpret_cast<char *>(xsv + (size_t) v * stage_elems) + offb), 16, 0, 0);
-               }
-            }
-         }
-      }
+      if (fp_plan != plan_fingerprint(fc0, fc1) && tid == 0) { mark_stale(p); }
+      if (CODED) { stage_value_table(p.dict, p.ndict, dictl, wave, lane); }
+      // the x pieces of every column: NV copies of the tile's staging area, one after the other
+      if (staged) { stage_x_pieces<NV>(p.x, st.x, xsv, stage_elems, pc, lane); }
    }
    // the first row's operands of every lane: same trip
    MvOps<NV> ops;
-   mv_load_ops<NV, OP>(ops, p, max(r0 + min(tid, nrows - 1), 0), xstride, bstride);
+   mv_load_ops<NV, OP>(ops, p, max(r0 + min(tid, nrows - 1), 0), st);
    if (streamer)
    {
       // the spill of the tile's last row past the window (rows of at most SPMV_THREADS entries: the launcher's condition) and
@@ -1166,14 +1144,10 @@ void spmv_xs_mv_kernel(SpmvArgs p, const int *__restrict__ tile_row, const int *
       unsigned cdC = 0;
       double vC = 0.0;
       if (CODED) { cdC = p.Ac8[qC]; } else { vC = p.Aa[qC]; }
-      constexpr int RPJ = (RP_CAP + SPMV_THREADS) / SPMV_THREADS;
       const int lim = min(nrows, rp_cap);
-      int rpv[RPJ];
-#pragma unroll
-      for (int j = 0; j < RPJ; j++) { rpv[j] = p.Ai[r0 + min(tid + j * SPMV_THREADS, lim)]; }
-#pragma unroll
-      for (int j = 0; j < RPJ; j++) { rp[min(tid + j * SPMV_THREADS, lim)] = rpv[j]; }
-      if (tid == 0 && rpv[0] != k0) { __hip_atomic_fetch_or(p.stale, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+      const TileRowPtrs rpv = load_tile_row_ptrs(p.Ai, r0, lim, tid);
+      park_tile_row_ptrs(rp, rpv, lim, tid);
+      if (tid == 0 && rpv.v[0] != k0) { mark_stale(p); }
       // park the window
       if (CODED)
       {
@@ -1194,10 +1168,8 @@ void spmv_xs_mv_kernel(SpmvArgs p, const int *__restrict__ tile_row, const int *
       if (kC < k1) { liS[kC - ka] = (unsigned short) lC; }
    }
    __syncthreads();
-   if (CODED && streamer)
-   {
-      if (__double_as_longlong(dictl[ckc]) != __double_as_longlong(ckv)) { __hip_atomic_fetch_or(p.stale, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
-   }
+   // (no p.dict_rounded here, unlike spmv_xs_kernel: the multivector launch refuses rounded values)
+   if (CODED && streamer && __double_as_longlong(dictl[ckc]) != __double_as_longlong(ckv)) { mark_stale(p); }
 
    const int avg = (k1 - k0) / nrows;
    int Wd = 1;
@@ -1206,7 +1178,7 @@ void spmv_xs_mv_kernel(SpmvArgs p, const int *__restrict__ tile_row, const int *
       Wd = p.reduce_w;
       if (Wd <= 0) { Wd = 32; while (Wd > 1 && nrows * Wd > SPMV_THREADS) { Wd >>= 1; } }
    }
-#define MV_SUMS(WW) mv_row_sums<NV, CODED, WW, OP>(p, r0, nrows, ka, rp_cap, staged, stage_elems, xsv, valS, cdS, dictl, liS, rp, xstride, bstride, ystride, auxstride, ops)
+#define MV_SUMS(WW) mv_row_sums<NV, CODED, WW, OP>(p, r0, nrows, ka, rp_cap, staged, stage_elems, xsv, valS, cdS, dictl, liS, rp, st, ops)
    switch (Wd)
    {
       case 1:  MV_SUMS(1); break;
@@ -1541,14 +1513,8 @@ void spmv_sl_body(const SpmvArgs &p, const int *__restrict__ sl_desc, const int 
    const double *dictl = xs + stage_elems;
    unsigned *tabl = reinterpret_cast<unsigned *>(xs + stage_elems + ((p.ndict + 1) & ~1));      // class table (CLS), behind the value table
 
-   int block = (int) blockIdx.x;
-   if (sl_perm)
-   {
-      if (block >= blocks) { return; }
-      block = sl_perm[block];
-   }
-   else { const int g = block >> 3, c = block & 7; block = (g >> 3) * 64 + c * 8 + (g & 7); }     // runs of 8 blocks per XCD
-   if ((unsigned) block >= (unsigned) blocks) { return; }
+   const int block = block_of_workgroup(sl_perm, blocks);
+   if (block < 0) { return; }
 
    const int tid = threadIdx.x, lane = tid & 63;
    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1559,31 +1525,12 @@ void spmv_sl_body(const SpmvArgs &p, const int *__restrict__ sl_desc, const int 
    sl_lane_load<CLS, W, KP>(me, st, p.Ai, block, wave, lane, tid, r, num_rows);
    const RowOps ops = load_row_ops<OP>(p, max(min(r, num_rows - 1), 0));
    // wave-uniform, through the scalar cache: this wave's piece descriptors, the block's first entry and fingerprint
-   const int *dsc = sl_desc + (size_t) block * XS_DESC + XS_WSEG * wave;
-   int seg_start[XS_WSEG], seg_ol[XS_WSEG];
-#pragma unroll
-   for (int j = 0; j < XS_WSEG; j++) { seg_start[j] = dsc[j]; seg_ol[j] = dsc[XS_SEGS + j]; }
+   const XPieces pc = wave_x_pieces(sl_desc, block, wave);
    const int k0 = sl_k0[block], k1b = sl_k0[block + 1], fp_plan = sl_fp[block];
    asm volatile("" :: "s"(sl_desc), "s"(sl_k0), "s"(sl_fp), "s"(CLS ? (const void *) st.toff : (const void *) st.data), "s"(st.tab), "s"(p.Ai) : "memory");
-#pragma unroll
-   for (int j = 0; j < XS_WSEG; j++)
-   {
-      const unsigned offb = (unsigned) seg_ol[j] >> 16, lanes = (unsigned) seg_ol[j] & 0xffffu;
-      if ((unsigned) lane < lanes)
-      {
-         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) (p.x + (size_t) (unsigned) seg_start[j] + 2 * lane),
-                                          (__attribute__((address_space(3))) void *) (reinterpret_cast<char *>(xs) + offb), 16, 0, 0);
-      }
-   }
+   stage_x_pieces<1>(p.x, 0, xs, 0, pc, lane);
    sl_lane_stage<CLS, KP>(me, st, wave, lane, tabl);
-   {
-      const int dl = (p.ndict + 1) >> 1;
-      if (lane < dl - 64 * wave)
-      {
-         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) (p.dict + 128 * wave + 2 * lane),
-                                          (__attribute__((address_space(3))) void *) (reinterpret_cast<char *>(const_cast<double *>(dictl)) + 1024 * wave), 16, 0, 0);
-      }
-   }
+   stage_value_table(p.dict, p.ndict, dictl, wave, lane);
    // the watch's samples: two columns and one value of the block's first entries (a second scalar trip, back long before
    // the vector loads above)
    const int q0 = min(max(k0, 0), nnz - 1), q1 = min(max(k0, 0) + 1, nnz - 1);
@@ -1611,8 +1558,8 @@ void spmv_sl_body(const SpmvArgs &p, const int *__restrict__ sl_desc, const int 
    if (W == 2) { sum += __shfl_xor(sum, 1, 64); }
    {
       bool off = __double_as_longlong(dictl[ckc]) != __double_as_longlong(p.dict_rounded ? (double) (float) ckv : ckv);
-      if (tid == 0) { off = off || fp_plan != (int) ((unsigned) fc0 * 2654435761u + (unsigned) fc1) || me.rs != k0; }
-      if (off) { __hip_atomic_fetch_or(p.stale, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+      if (tid == 0) { off = off || fp_plan != plan_fingerprint(fc0, fc1) || me.rs != k0; }
+      if (off) { mark_stale(p); }
    }
    if (r < num_rows && sub == 0) { row_epilogue<OP>(p, r, sum, ops); }
 }
@@ -1643,21 +1590,15 @@ template <int NV, int W, int KP, bool CLS, int OP>
 __device__ __forceinline__
 void spmv_sl_mv_body(const SpmvArgs &p, const int *__restrict__ sl_desc, const int *__restrict__ sl_k0,
                      const int *__restrict__ sl_fp, const int *__restrict__ sl_perm, const SlStream &st,
-                     int blocks, int num_rows, int nnz, int stage_elems, long xstride, long bstride, long ystride, long auxstride)
+                     int blocks, int num_rows, int nnz, int stage_elems, MvStrides ms)
 {
    extern __shared__ __align__(16) unsigned char smem_raw[];
    double *xs = reinterpret_cast<double *>(smem_raw);
    const double *dictl = xs + (size_t) NV * stage_elems;
    unsigned *tabl = reinterpret_cast<unsigned *>(xs + (size_t) NV * stage_elems + ((p.ndict + 1) & ~1));
 
-   int block = (int) blockIdx.x;
-   if (sl_perm)
-   {
-      if (block >= blocks) { return; }
-      block = sl_perm[block];
-   }
-   else { const int g = block >> 3, c = block & 7; block = (g >> 3) * 64 + c * 8 + (g & 7); }
-   if ((unsigned) block >= (unsigned) blocks) { return; }
+   const int block = block_of_workgroup(sl_perm, blocks);
+   if (block < 0) { return; }
 
    const int tid = threadIdx.x, lane = tid & 63;
    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1666,36 +1607,13 @@ void spmv_sl_mv_body(const SpmvArgs &p, const int *__restrict__ sl_desc, const i
    SlLane<CLS, KP> me;
    sl_lane_load<CLS, W, KP>(me, st, p.Ai, block, wave, lane, tid, r, num_rows);
    MvOps<NV> ops;
-   mv_load_ops<NV, OP>(ops, p, max(min(r, num_rows - 1), 0), xstride, bstride);
-   const int *dsc = sl_desc + (size_t) block * XS_DESC + XS_WSEG * wave;
-   int seg_start[XS_WSEG], seg_ol[XS_WSEG];
-#pragma unroll
-   for (int j = 0; j < XS_WSEG; j++) { seg_start[j] = dsc[j]; seg_ol[j] = dsc[XS_SEGS + j]; }
+   mv_load_ops<NV, OP>(ops, p, max(min(r, num_rows - 1), 0), ms);
+   const XPieces pc = wave_x_pieces(sl_desc, block, wave);
    const int k0 = sl_k0[block], k1b = sl_k0[block + 1], fp_plan = sl_fp[block];
    asm volatile("" :: "s"(sl_desc), "s"(sl_k0), "s"(sl_fp), "s"(CLS ? (const void *) st.toff : (const void *) st.data), "s"(st.tab), "s"(p.Ai) : "memory");
-   sl_lane_stage<CLS, KP>(me, st, wave, lane, tabl);
-#pragma unroll
-   for (int v = 0; v < NV; v++)
-   {
-#pragma unroll
-      for (int j = 0; j < XS_WSEG; j++)
-      {
-         const unsigned offb = (unsigned) seg_ol[j] >> 16, lanes = (unsigned) seg_ol[j] & 0xffffu;
-         if ((unsigned) lane < lanes)
-         {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) (p.x + (size_t) v * xstride + (size_t) (unsigned) seg_start[j] + 2 * lane),
-                                             (__attribute__((address_space(3))) void *) (reinterpret_cast<char *>(xs + (size_t) v * stage_elems) + offb), 16, 0, 0);
-         }
-      }
-   }
-   {
-      const int dl = (p.ndict + 1) >> 1;
-      if (lane < dl - 64 * wave)
-      {
-         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) (p.dict + 128 * wave + 2 * lane),
-                                          (__attribute__((address_space(3))) void *) (reinterpret_cast<char *>(const_cast<double *>(dictl)) + 1024 * wave), 16, 0, 0);
-      }
-   }
+   sl_lane_stage<CLS, KP>(me, st, wave, lane, tabl);      // (before the x pieces here, after them in spmv_sl_body)
+   stage_x_pieces<NV>(p.x, ms.x, xs, stage_elems, pc, lane);
+   stage_value_table(p.dict, p.ndict, dictl, wave, lane);
    // the watch's samples and the rotating value check, as spmv_sl_kernel
    const int q0 = min(max(k0, 0), nnz - 1), q1 = min(max(k0, 0) + 1, nnz - 1);
    const int fc0 = p.Aj[q0], fc1 = p.Aj[q1];
@@ -1728,30 +1646,30 @@ void spmv_sl_mv_body(const SpmvArgs &p, const int *__restrict__ sl_desc, const i
       for (int v = 0; v < NV; v++) { sum[v] += __shfl_xor(sum[v], 1, 64); }
    }
    {
+      // (no p.dict_rounded here, unlike spmv_sl_body: the multivector launch refuses rounded values)
       bool off = __double_as_longlong(dictl[ckc]) != __double_as_longlong(ckv);
-      if (tid == 0) { off = off || fp_plan != (int) ((unsigned) fc0 * 2654435761u + (unsigned) fc1) || me.rs != k0; }
-      if (off) { __hip_atomic_fetch_or(p.stale, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+      if (tid == 0) { off = off || fp_plan != plan_fingerprint(fc0, fc1) || me.rs != k0; }
+      if (off) { mark_stale(p); }
    }
-   if (r < num_rows && sub == 0) { mv_epilogue<NV, OP>(p, r, sum, ops, ystride, auxstride); }
+   if (r < num_rows && sub == 0) { mv_epilogue<NV, OP>(p, r, sum, ops, ms); }
 }
 template <int NV, int W, int KP, int OP>
 __global__ __launch_bounds__(SPMV_THREADS)
 void spmv_sl_mv_kernel(SpmvArgs p, const int *__restrict__ sl_desc, const int *__restrict__ sl_k0,
                        const int *__restrict__ sl_fp, const int *__restrict__ sl_perm, const unsigned *__restrict__ sl_data,
-                       int blocks, int num_rows, int nnz, int stage_elems, long xstride, long bstride, long ystride, long auxstride)
+                       int blocks, int num_rows, int nnz, int stage_elems, MvStrides ms)
 {
    const SlStream st = {sl_data, nullptr, nullptr, nullptr};
-   spmv_sl_mv_body<NV, W, KP, false, OP>(p, sl_desc, sl_k0, sl_fp, sl_perm, st, blocks, num_rows, nnz, stage_elems, xstride, bstride, ystride, auxstride);
+   spmv_sl_mv_body<NV, W, KP, false, OP>(p, sl_desc, sl_k0, sl_fp, sl_perm, st, blocks, num_rows, nnz, stage_elems, ms);
 }
 template <int NV, int W, int KP, int OP>
 __global__ __launch_bounds__(SPMV_THREADS)
 void spmv_sl_mv_kernel_cls(SpmvArgs p, const int *__restrict__ sl_desc, const int *__restrict__ sl_k0, const int *__restrict__ sl_fp,
                            const int *__restrict__ sl_perm, const unsigned char *__restrict__ sl_cls, const unsigned *__restrict__ sl_tab,
-                           const int *__restrict__ sl_toff, int blocks, int num_rows, int nnz, int stage_elems, long xstride, long bstride,
-                           long ystride, long auxstride)
+                           const int *__restrict__ sl_toff, int blocks, int num_rows, int nnz, int stage_elems, MvStrides ms)
 {
    const SlStream st = {nullptr, sl_cls, sl_tab, sl_toff};
-   spmv_sl_mv_body<NV, W, KP, true, OP>(p, sl_desc, sl_k0, sl_fp, sl_perm, st, blocks, num_rows, nnz, stage_elems, xstride, bstride, ystride, auxstride);
+   spmv_sl_mv_body<NV, W, KP, true, OP>(p, sl_desc, sl_k0, sl_fp, sl_perm, st, blocks, num_rows, nnz, stage_elems, ms);
 }
 
 // ---- slice form construction
@@ -1765,7 +1683,7 @@ __global__ void sl_fp_kernel(const int *__restrict__ Aj, const int *__restrict__
    const int b = blockIdx.x * blockDim.x + threadIdx.x;
    if (b >= blocks) { return; }
    const int q0 = min(max(k0[b], 0), nnz - 1), q1 = min(max(k0[b], 0) + 1, nnz - 1);
-   fp[b] = (int) ((unsigned) Aj[q0] * 2654435761u + (unsigned) Aj[q1]);
+   fp[b] = plan_fingerprint(Aj[q0], Aj[q1]);
 }
 template <int W>
 __global__ __launch_bounds__(SPMV_THREADS)
@@ -2031,6 +1949,26 @@ constexpr int RS_HDR = 16;          // ints per wave: [0] position of its first 
 // (A persistent form — a workgroup walking blocks v, v + G, ... with the NEXT block's header and descriptors requested behind
 // the current block's vector loads, so that no block waits for a cold scalar round trip — was built and measured: level 1
 // of the benchmark hierarchy 0.377 ms against 0.332 ms, whatever the number of workgroups; the doubled scalars spill.  Removed.)
+// a wave's header (wave-uniform, through the scalar cache)
+template <int KP>
+struct RsHeader { int h[4 + KP / 4]; };
+template <int KP>
+__device__ __forceinline__ RsHeader<KP> rs_wave_header(const int *__restrict__ rs_hdr, int block, int wave)
+{
+   const int *hdr = rs_hdr + (size_t) (block * 4 + wave) * RS_HDR;
+   RsHeader<KP> H;
+#pragma unroll
+   for (int i = 0; i < 4 + KP / 4; i++) { H.h[i] = hdr[i]; }
+   return H;
+}
+// the sum of a row: the partial sums of its W lanes (lane-of-the-row major in part[]), in lane order
+__device__ __forceinline__ double rs_row_total(const double *part, int R, int W, int tid)
+{
+   double total = part[tid];
+   for (int j = 1; j < W; j++) { total += part[j * R + tid]; }
+   return total;
+}
+
 template <int OP, int KP, bool F32>
 __global__ __launch_bounds__(SPMV_THREADS)
 void spmv_rs_kernel(SpmvArgs p, const int *__restrict__ rs_desc, const int *__restrict__ rs_perm, const int *__restrict__ rs_hdr,
@@ -2041,14 +1979,8 @@ void spmv_rs_kernel(SpmvArgs p, const int *__restrict__ rs_desc, const int *__re
    double *xs = reinterpret_cast<double *>(smem_raw);
    double *part = xs + stage_elems;                 // [SPMV_THREADS] partial sums, lane-of-the-row major
 
-   int block = (int) blockIdx.x;
-   if (rs_perm)
-   {
-      if (block >= blocks) { return; }
-      block = rs_perm[block];
-   }
-   else { const int g = block >> 3, c = block & 7; block = (g >> 3) * 64 + c * 8 + (g & 7); }     // runs of 8 blocks per XCD
-   if ((unsigned) block >= (unsigned) blocks) { return; }
+   const int block = block_of_workgroup(rs_perm, blocks);
+   if (block < 0) { return; }
 
    const int tid = threadIdx.x, lane = tid & 63;
    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2057,25 +1989,19 @@ void spmv_rs_kernel(SpmvArgs p, const int *__restrict__ rs_desc, const int *__re
    const int r = block * R + tid;
    const RowOps ops = load_row_ops<OP>(p, max(min(r, num_rows - 1), 0));
    // wave-uniform, through the scalar cache: the wave's header and its piece descriptors
-   constexpr int NH = 4 + KP / 4;
-   const int *hdr = rs_hdr + (size_t) (block * 4 + wave) * RS_HDR;
-   int h[NH];
-#pragma unroll
-   for (int i = 0; i < NH; i++) { h[i] = hdr[i]; }
-   const int *dsc = rs_desc + (size_t) block * XS_DESC + XS_WSEG * wave;
-   int seg_start[XS_WSEG], seg_ol[XS_WSEG];
-#pragma unroll
-   for (int j = 0; j < XS_WSEG; j++) { seg_start[j] = dsc[j]; seg_ol[j] = dsc[XS_SEGS + j]; }
+   const RsHeader<KP> H = rs_wave_header<KP>(rs_hdr, block, wave);
+   const XPieces pc = wave_x_pieces(rs_desc, block, wave);
    asm volatile("" :: "s"(rs_desc), "s"(rs_hdr), "s"(rs_meta) : "memory");
-   const int nch = h[1];
+   const int nch = H.h[1];
    // The stream, in groups of four chunks (a group the wave has none of is skipped: wave-uniform): chunk c of this wave
    // starts where chunk c - 1 ended; lanes past a chunk's last entry — and chunks past the wave's last one inside a group —
    // re-read the entry in front (same cache line, no traffic), so that every load of a group is unconditional.  The 16-bit
    // positions come in pairs, one 32-bit word per lane for chunks 2p and 2p + 1 (as many words as chunk 2p has lanes): no
    // 16-bit loads — those are widened on arrival, i.e. waited for where they are issued.
-   const double *wv = rs_val + h[0];
-   const float *wf = rs_val32 + h[0];
-   const unsigned *wi = rs_idx + h[2];
+   // (Inline here and in spmv_rs_mv_kernel, not a shared helper: see the note there.)
+   const double *wv = rs_val + H.h[0];
+   const float *wf = rs_val32 + H.h[0];
+   const unsigned *wi = rs_idx + H.h[2];
    double   vv[KP];
    float    vf[KP];
    unsigned iw[KP / 2];                  // staged positions (byte offsets) of the lane's entries of chunks 2p (low half) and 2p + 1
@@ -2089,7 +2015,7 @@ void spmv_rs_kernel(SpmvArgs p, const int *__restrict__ rs_desc, const int *__re
 #pragma unroll
             for (int c = 4 * g; c < 4 * g + 4; c++)
             {
-               const int na = (h[4 + (c >> 2)] >> (8 * (c & 3))) & 0xff;
+               const int na = (H.h[4 + (c >> 2)] >> (8 * (c & 3))) & 0xff;
                const unsigned q = (unsigned) (off + min(lane, na - 1));
                if (F32) { vf[c] = wf[q]; } else { vv[c] = wv[q]; }
                if ((c & 1) == 0) { iw[c >> 1] = wi[(unsigned) (offi + min(lane, na - 1))]; offi += na; }
@@ -2099,16 +2025,7 @@ void spmv_rs_kernel(SpmvArgs p, const int *__restrict__ rs_desc, const int *__re
       }
    }
    // the x pieces, straight into LDS (see spmv_xs_kernel)
-#pragma unroll
-   for (int j = 0; j < XS_WSEG; j++)
-   {
-      const unsigned offb = (unsigned) seg_ol[j] >> 16, lanes = (unsigned) seg_ol[j] & 0xffffu;
-      if ((unsigned) lane < lanes)
-      {
-         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) (p.x + (size_t) (unsigned) seg_start[j] + 2 * lane),
-                                          (__attribute__((address_space(3))) void *) (reinterpret_cast<char *>(xs) + offb), 16, 0, 0);
-      }
-   }
+   stage_x_pieces<1>(p.x, 0, xs, 0, pc, lane);
    __syncthreads();
 
    // a lane's sum, four entries at a time: the LDS reads of a group in flight together, then the multiply-adds in stored
@@ -2148,12 +2065,7 @@ void spmv_rs_kernel(SpmvArgs p, const int *__restrict__ rs_desc, const int *__re
    }
    part[meta & 0x3ffu] = sum;
    lds_barrier();
-   if (tid < R && r < num_rows)
-   {
-      double total = part[tid];
-      for (int j = 1; j < W; j++) { total += part[j * R + tid]; }
-      row_epilogue<OP>(p, r, total, ops);
-   }
+   if (tid < R && r < num_rows) { row_epilogue<OP>(p, r, rs_row_total(part, R, W, tid), ops); }
 }
 
 // The row-slice form with a multivector: a lane's values and staged positions are in registers, so a further column costs its x
@@ -2164,41 +2076,30 @@ template <int NV, int OP, int KP>
 __global__ __launch_bounds__(SPMV_THREADS)
 void spmv_rs_mv_kernel(SpmvArgs p, const int *__restrict__ rs_desc, const int *__restrict__ rs_perm, const int *__restrict__ rs_hdr,
                        const unsigned *__restrict__ rs_meta, const double *__restrict__ rs_val, const unsigned *__restrict__ rs_idx,
-                       int blocks, int num_rows, int R, int W, int stage_elems, long xstride, long bstride, long ystride, long auxstride)
+                       int blocks, int num_rows, int R, int W, int stage_elems, MvStrides st)
 {
    extern __shared__ __align__(16) unsigned char smem_raw[];
    double *xs = reinterpret_cast<double *>(smem_raw);              // NV staged copies of x, stage_elems each
    double *part = xs + (size_t) NV * stage_elems;                  // [NV][SPMV_THREADS] partial sums, lane-of-the-row major
 
-   int block = (int) blockIdx.x;
-   if (rs_perm)
-   {
-      if (block >= blocks) { return; }
-      block = rs_perm[block];
-   }
-   else { const int g = block >> 3, c = block & 7; block = (g >> 3) * 64 + c * 8 + (g & 7); }     // runs of 8 blocks per XCD
-   if ((unsigned) block >= (unsigned) blocks) { return; }
+   const int block = block_of_workgroup(rs_perm, blocks);
+   if (block < 0) { return; }
 
    const int tid = threadIdx.x, lane = tid & 63;
    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
    const unsigned meta = rs_meta[(size_t) block * SPMV_THREADS + tid];
    const int r = block * R + tid;
    MvOps<NV> ops;
-   mv_load_ops<NV, OP>(ops, p, max(min(r, num_rows - 1), 0), xstride, bstride);
-   constexpr int NH = 4 + KP / 4;
-   const int *hdr = rs_hdr + (size_t) (block * 4 + wave) * RS_HDR;
-   int h[NH];
-#pragma unroll
-   for (int i = 0; i < NH; i++) { h[i] = hdr[i]; }
-   const int *dsc = rs_desc + (size_t) block * XS_DESC + XS_WSEG * wave;
-   int seg_start[XS_WSEG], seg_ol[XS_WSEG];
-#pragma unroll
-   for (int j = 0; j < XS_WSEG; j++) { seg_start[j] = dsc[j]; seg_ol[j] = dsc[XS_SEGS + j]; }
+   mv_load_ops<NV, OP>(ops, p, max(min(r, num_rows - 1), 0), st);
+   const RsHeader<KP> H = rs_wave_header<KP>(rs_hdr, block, wave);
+   const XPieces pc = wave_x_pieces(rs_desc, block, wave);
    asm volatile("" :: "s"(rs_desc), "s"(rs_hdr), "s"(rs_meta) : "memory");
-   const int nch = h[1];
-   // the stream, as spmv_rs_kernel reads it
-   const double *wv = rs_val + h[0];
-   const unsigned *wi = rs_idx + h[2];
+   const int nch = H.h[1];
+   // The stream, exactly as spmv_rs_kernel reads it.  The loop stands in both kernels and is not a shared helper: with the
+   // arrays filled through one (array references, force-inlined) the three OP_JACOBI instances of this kernel with KP = 16
+   // lost one or two waves per SIMD.  A change to the stream's format is made in both.
+   const double *wv = rs_val + H.h[0];
+   const unsigned *wi = rs_idx + H.h[2];
    double   vv[KP];
    unsigned iw[KP / 2];
    {
@@ -2211,7 +2112,7 @@ void spmv_rs_mv_kernel(SpmvArgs p, const int *__restrict__ rs_desc, const int *_
 #pragma unroll
             for (int c = 4 * g; c < 4 * g + 4; c++)
             {
-               const int na = (h[4 + (c >> 2)] >> (8 * (c & 3))) & 0xff;
+               const int na = (H.h[4 + (c >> 2)] >> (8 * (c & 3))) & 0xff;
                vv[c] = wv[(unsigned) (off + min(lane, na - 1))];
                if ((c & 1) == 0) { iw[c >> 1] = wi[(unsigned) (offi + min(lane, na - 1))]; offi += na; }
                off += na;
@@ -2220,20 +2121,7 @@ void spmv_rs_mv_kernel(SpmvArgs p, const int *__restrict__ rs_desc, const int *_
       }
    }
    // the x pieces of every column, straight into LDS
-#pragma unroll
-   for (int v = 0; v < NV; v++)
-   {
-#pragma unroll
-      for (int j = 0; j < XS_WSEG; j++)
-      {
-         const unsigned offb = (unsigned) seg_ol[j] >> 16, lanes = (unsigned) seg_ol[j] & 0xffffu;
-         if ((unsigned) lane < lanes)
-         {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) (p.x + (size_t) v * xstride + (size_t) (unsigned) seg_start[j] + 2 * lane),
-                                             (__attribute__((address_space(3))) void *) (reinterpret_cast<char *>(xs + (size_t) v * stage_elems) + offb), 16, 0, 0);
-         }
-      }
-   }
+   stage_x_pieces<NV>(p.x, st.x, xs, stage_elems, pc, lane);
    __syncthreads();
 
    const int cnt = (int) (meta >> 10);
@@ -2278,12 +2166,8 @@ void spmv_rs_mv_kernel(SpmvArgs p, const int *__restrict__ rs_desc, const int *_
    {
       double total[NV];
 #pragma unroll
-      for (int v = 0; v < NV; v++)
-      {
-         total[v] = part[v * SPMV_THREADS + tid];
-         for (int j = 1; j < W; j++) { total[v] += part[v * SPMV_THREADS + j * R + tid]; }
-      }
-      mv_epilogue<NV, OP>(p, r, total, ops, ystride, auxstride);
+      for (int v = 0; v < NV; v++) { total[v] = rs_row_total(part + v * SPMV_THREADS, R, W, tid); }
+      mv_epilogue<NV, OP>(p, r, total, ops, st);
    }
 }
 
@@ -2549,7 +2433,7 @@ __global__ void build_fp_kernel(const HYPRE_Int *__restrict__ Aj, int last_quad,
    if (t >= num_tiles) { return; }
    const int ka = t * SPMV_TILE;
    const int c0 = Aj[min(ka + 5, last_quad)], c1 = Aj[min(ka + 1029, last_quad)];
-   fp[t] = (int) ((unsigned) c0 * 2654435761u + (unsigned) c1);
+   fp[t] = plan_fingerprint(c0, c1);
 }
 void launch_build_fp(const HYPRE_Int *Aj, int nnz, int num_tiles, int *fp, hipStream_t s)
 {
@@ -2912,16 +2796,24 @@ static void launch_spmv_op(const SpmvPlan *plan, const SpmvArgs &a, hipStream_t 
    }
 }
 
-void launch_spmv(const SpmvPlan *plan, const SpmvArgs &args, SpmvOp op, hipStream_t s)
+// what every launch takes from the plan, whatever the caller put there
+static void fill_plan_fields(SpmvArgs &a, const SpmvPlan *plan)
 {
-   if (plan->num_rows <= 0) { return; }
-   SpmvArgs a = args;
    a.last_quad = (plan->nnz > 0 ? (int) (plan->nnz - 1) : 0) & ~3;
    a.x_last = plan->num_cols > 0 ? plan->num_cols - 1 : 0;
    a.tile_perm = plan->d_tile_perm;
    a.tile_fp = plan->d_tile_fp;
    a.stale = plan->d_stale;
    a.nnz = plan->nnz;
+}
+// bytes of the per-block tables a row-slice launch reads (hypre_amd_ByteCounters): the wave headers, the lane words, the descriptors
+static inline double rs_block_table_bytes(const SpmvPlan *plan) { return (double) plan->rs_blocks * (4.0 * (4 * RS_HDR + SPMV_THREADS + XS_DESC)); }
+
+void launch_spmv(const SpmvPlan *plan, const SpmvArgs &args, SpmvOp op, hipStream_t s)
+{
+   if (plan->num_rows <= 0) { return; }
+   SpmvArgs a = args;
+   fill_plan_fields(a, plan);
    a.rot = const_cast<SpmvPlan *>(plan)->launches++;
    // value codes (the x-staged kernel only): one byte per entry and the table of the matrix's values
    a.Ac8 = nullptr; a.dict = nullptr; a.ndict = 0; a.dict_rounded = 0;
@@ -2983,7 +2875,7 @@ void launch_spmv(const SpmvPlan *plan, const SpmvArgs &args, SpmvOp op, hipStrea
       if (a.use_rs)
       {
          // row slices: value + 16-bit position per entry, no row pointers; per block the wave headers, lane words and descriptors
-         streamed = nz * (vw + 2.0) + (double) plan->rs_blocks * (4.0 * (4 * RS_HDR + SPMV_THREADS + XS_DESC)) + rowb * nr + xcols;
+         streamed = nz * (vw + 2.0) + rs_block_table_bytes(plan) + rowb * nr + xcols;
       }
       else if (slice)
       {
@@ -3009,66 +2901,64 @@ void launch_spmv(const SpmvPlan *plan, const SpmvArgs &args, SpmvOp op, hipStrea
    }
 }
 
-// Fused passes over a multivector: columns v < nv of x, b, y, aux lie xstride / bstride / ystride / auxstride doubles apart.
-template <int NV, bool CODED, int OP>
-static void launch_xs_mv(const SpmvPlan *plan, const SpmvArgs &a, int stage_elems, int win_elems, int rp_cap, size_t lds,
-                         long xstride, long bstride, long ystride, long auxstride, hipStream_t s)
+// Fused passes over a multivector: columns v < nv of x, b, y, aux lie MvStrides doubles apart.
+constexpr int MV_WIN = 2320;        // SPMV_TILE + SPMV_THREADS entries of a window and its spill, a multiple of 16
+// what one pass hands to its kernel's launcher
+struct MvLaunch
+{
+   int       stage_elems, rp_cap;
+   size_t    lds;
+   MvStrides st;
+};
+// Dynamic LDS of kernel K up to the 160 KB of a CU, asked for once per process and kernel.  Keyed on the kernel itself, not its
+// type: instances such as spmv_rs_mv_kernel<2, OP, 8> and <2, OP, 16> share a function type and would share the flag.
+template <auto K>
+static void allow_large_lds()
 {
    static bool raised = false;
-   if (!raised)
-   {
-      (void) hipFuncSetAttribute((const void *) (spmv_xs_mv_kernel<NV, CODED, OP>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void) hipGetLastError();
-      raised = true;
-   }
+   if (raised) { return; }
+   (void) hipFuncSetAttribute((const void *) K, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+   (void) hipGetLastError();
+   raised = true;
+}
+
+template <int NV, bool CODED, int OP>
+static void launch_xs_mv(const SpmvPlan *plan, const SpmvArgs &a, const MvLaunch &m, hipStream_t s)
+{
+   allow_large_lds<spmv_xs_mv_kernel<NV, CODED, OP>>();
    const int unit = a.tile_perm ? 1 : (a.xcd_map > 0 ? 8 * a.xcd_map : 8);
    const int grid = ((plan->num_tiles + unit - 1) / unit) * unit;
    // a lane per row where the rows are short: a fifth and a sixth wave take rows 256 .. 383 of a tile in the same pass
    const int threads = (plan->max_tile_rows > SPMV_THREADS && plan->max_tile_rows <= 320) ? 320 :
                        (plan->max_tile_rows > 320 ? MV_THREADS_MAX : SPMV_THREADS);
-   hipLaunchKernelGGL((spmv_xs_mv_kernel<NV, CODED, OP>), dim3(grid), dim3(threads), lds, s, a,
+   hipLaunchKernelGGL((spmv_xs_mv_kernel<NV, CODED, OP>), dim3(grid), dim3(threads), m.lds, s, a,
                       plan->d_tile_row, plan->d_tile_k, plan->d_xs_cnt, plan->d_xs_desc, plan->d_lidx,
-                      plan->num_tiles, stage_elems, win_elems, rp_cap, plan->xs_launch_units, xstride, bstride, ystride, auxstride);
+                      plan->num_tiles, m.stage_elems, MV_WIN, m.rp_cap, plan->xs_launch_units, m.st);
 }
 
 long &spmv_mv_launches() { static long n = 0; return n; }
 template <int NV, int W, int KP, int OP>
-static void launch_sl_mv(const SpmvPlan *plan, const SpmvArgs &a, int stage_elems, size_t lds, long xstride, long bstride, long ystride,
-                         long auxstride, hipStream_t s)
+static void launch_sl_mv(const SpmvPlan *plan, const SpmvArgs &a, const MvLaunch &m, hipStream_t s)
 {
    const int grid = plan->d_sl_perm ? plan->sl_blocks : ((plan->sl_blocks + 63) / 64) * 64;
    if (plan->d_sl_cls)
    {
-      static bool raised_cls = false;
-      if (!raised_cls)
-      {
-         (void) hipFuncSetAttribute((const void *) (spmv_sl_mv_kernel_cls<NV, W, KP, OP>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-         (void) hipGetLastError();
-         raised_cls = true;
-      }
-      hipLaunchKernelGGL((spmv_sl_mv_kernel_cls<NV, W, KP, OP>), dim3(grid), dim3(SPMV_THREADS), lds, s, a, plan->d_sl_desc, plan->d_sl_k0, plan->d_sl_fp,
-                         plan->d_sl_perm, plan->d_sl_cls, plan->d_sl_tab, plan->d_sl_toff, plan->sl_blocks, plan->num_rows, plan->nnz, stage_elems,
-                         xstride, bstride, ystride, auxstride);
+      allow_large_lds<spmv_sl_mv_kernel_cls<NV, W, KP, OP>>();
+      hipLaunchKernelGGL((spmv_sl_mv_kernel_cls<NV, W, KP, OP>), dim3(grid), dim3(SPMV_THREADS), m.lds, s, a, plan->d_sl_desc, plan->d_sl_k0, plan->d_sl_fp,
+                         plan->d_sl_perm, plan->d_sl_cls, plan->d_sl_tab, plan->d_sl_toff, plan->sl_blocks, plan->num_rows, plan->nnz, m.stage_elems,
+                         m.st);
       return;
    }
-   static bool raised = false;
-   if (!raised)
-   {
-      (void) hipFuncSetAttribute((const void *) (spmv_sl_mv_kernel<NV, W, KP, OP>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void) hipGetLastError();
-      raised = true;
-   }
-   hipLaunchKernelGGL((spmv_sl_mv_kernel<NV, W, KP, OP>), dim3(grid), dim3(SPMV_THREADS), lds, s, a, plan->d_sl_desc, plan->d_sl_k0,
-                      plan->d_sl_fp, plan->d_sl_perm, plan->d_sl_data, plan->sl_blocks, plan->num_rows, plan->nnz, stage_elems, xstride, bstride, ystride,
-                      auxstride);
+   allow_large_lds<spmv_sl_mv_kernel<NV, W, KP, OP>>();
+   hipLaunchKernelGGL((spmv_sl_mv_kernel<NV, W, KP, OP>), dim3(grid), dim3(SPMV_THREADS), m.lds, s, a, plan->d_sl_desc, plan->d_sl_k0,
+                      plan->d_sl_fp, plan->d_sl_perm, plan->d_sl_data, plan->sl_blocks, plan->num_rows, plan->nnz, m.stage_elems, m.st);
 }
 template <int NV, int OP>
-static void launch_sl_mv_nv(const SpmvPlan *plan, const SpmvArgs &a, int stage_elems, size_t lds, long xstride, long bstride, long ystride,
-                            long auxstride, hipStream_t s)
+static void launch_sl_mv_nv(const SpmvPlan *plan, const SpmvArgs &a, const MvLaunch &m, hipStream_t s)
 {
-   if (plan->sl_w == 1) { launch_sl_mv<NV, 1, 8, OP>(plan, a, stage_elems, lds, xstride, bstride, ystride, auxstride, s); }
-   else if (plan->sl_k == 8) { launch_sl_mv<NV, 2, 8, OP>(plan, a, stage_elems, lds, xstride, bstride, ystride, auxstride, s); }
-   else { launch_sl_mv<NV, 2, 16, OP>(plan, a, stage_elems, lds, xstride, bstride, ystride, auxstride, s); }
+   if (plan->sl_w == 1) { launch_sl_mv<NV, 1, 8, OP>(plan, a, m, s); }
+   else if (plan->sl_k == 8) { launch_sl_mv<NV, 2, 8, OP>(plan, a, m, s); }
+   else { launch_sl_mv<NV, 2, 16, OP>(plan, a, m, s); }
 }
 static inline size_t sl_mv_lds_bytes(const SpmvPlan *plan, int nv, int ndict, int &stage_elems)
 {
@@ -3077,31 +2967,23 @@ static inline size_t sl_mv_lds_bytes(const SpmvPlan *plan, int nv, int ndict, in
 }
 
 template <int NV, int OP, int KP>
-static void launch_rs_mv_form(const SpmvPlan *plan, const SpmvArgs &a, int stage_elems, size_t lds, long xstride, long bstride, long ystride,
-                              long auxstride, hipStream_t s)
+static void launch_rs_mv_form(const SpmvPlan *plan, const SpmvArgs &a, const MvLaunch &m, hipStream_t s)
 {
-   static bool raised = false;
-   if (!raised)
-   {
-      (void) hipFuncSetAttribute((const void *) (spmv_rs_mv_kernel<NV, OP, KP>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void) hipGetLastError();
-      raised = true;
-   }
+   allow_large_lds<spmv_rs_mv_kernel<NV, OP, KP>>();
    const int grid = plan->d_rs_perm ? plan->rs_blocks : ((plan->rs_blocks + 63) / 64) * 64;
-   hipLaunchKernelGGL((spmv_rs_mv_kernel<NV, OP, KP>), dim3(grid), dim3(SPMV_THREADS), lds, s, a, plan->d_rs_desc, plan->d_rs_perm, plan->d_rs_hdr,
-                      plan->d_rs_meta, plan->d_rs_val, plan->d_rs_idx, plan->rs_blocks, plan->num_rows, plan->rs_rows, plan->rs_w, stage_elems,
-                      xstride, bstride, ystride, auxstride);
+   hipLaunchKernelGGL((spmv_rs_mv_kernel<NV, OP, KP>), dim3(grid), dim3(SPMV_THREADS), m.lds, s, a, plan->d_rs_desc, plan->d_rs_perm, plan->d_rs_hdr,
+                      plan->d_rs_meta, plan->d_rs_val, plan->d_rs_idx, plan->rs_blocks, plan->num_rows, plan->rs_rows, plan->rs_w, m.stage_elems,
+                      m.st);
 }
 template <int NV, int OP>
-static void launch_rs_mv(const SpmvPlan *plan, const SpmvArgs &a, int stage_elems, size_t lds, long xstride, long bstride, long ystride,
-                         long auxstride, hipStream_t s)
+static void launch_rs_mv(const SpmvPlan *plan, const SpmvArgs &a, const MvLaunch &m, hipStream_t s)
 {
    switch (plan->rs_kp)
    {
-      case 8:  launch_rs_mv_form<NV, OP, 8>(plan, a, stage_elems, lds, xstride, bstride, ystride, auxstride, s); break;
-      case 16: launch_rs_mv_form<NV, OP, 16>(plan, a, stage_elems, lds, xstride, bstride, ystride, auxstride, s); break;
-      case 24: launch_rs_mv_form<NV, OP, 24>(plan, a, stage_elems, lds, xstride, bstride, ystride, auxstride, s); break;
-      default: launch_rs_mv_form<NV, OP, 32>(plan, a, stage_elems, lds, xstride, bstride, ystride, auxstride, s); break;
+      case 8:  launch_rs_mv_form<NV, OP, 8>(plan, a, m, s); break;
+      case 16: launch_rs_mv_form<NV, OP, 16>(plan, a, m, s); break;
+      case 24: launch_rs_mv_form<NV, OP, 24>(plan, a, m, s); break;
+      default: launch_rs_mv_form<NV, OP, 32>(plan, a, m, s); break;
    }
 }
 static inline size_t rs_mv_lds_bytes(const SpmvPlan *plan, int nv, int &stage_elems)
@@ -3116,7 +2998,6 @@ static int rs_mv_columns()
    return c;
 }
 
-constexpr int MV_WIN = 2320;        // SPMV_TILE + SPMV_THREADS entries of a window and its spill, a multiple of 16
 static inline size_t mv_lds_bytes(const SpmvPlan *plan, int nv, bool coded, int ndict, int &stage_elems, int &rp_cap)
 {
    int rowsum_elems;
@@ -3152,37 +3033,36 @@ static int spmv_mv_form(const SpmvPlan *plan, const SpmvArgs &args, long xstride
 }
 
 template <int OP>
-static void launch_mv_group(const SpmvPlan *plan, const SpmvArgs &c, int form, int g, bool coded, int stage_elems, int rp_cap, size_t lds,
-                            long xstride, long bstride, long ystride, long auxstride, hipStream_t s)
+static void launch_mv_group(const SpmvPlan *plan, const SpmvArgs &c, int form, int g, bool coded, const MvLaunch &m, hipStream_t s)
 {
    if (form == MV_RS)
    {
       switch (g)
       {
-         case 2:  launch_rs_mv<2, OP>(plan, c, stage_elems, lds, xstride, bstride, ystride, auxstride, s); break;
-         case 3:  launch_rs_mv<3, OP>(plan, c, stage_elems, lds, xstride, bstride, ystride, auxstride, s); break;
-         default: launch_rs_mv<4, OP>(plan, c, stage_elems, lds, xstride, bstride, ystride, auxstride, s); break;
+         case 2:  launch_rs_mv<2, OP>(plan, c, m, s); break;
+         case 3:  launch_rs_mv<3, OP>(plan, c, m, s); break;
+         default: launch_rs_mv<4, OP>(plan, c, m, s); break;
       }
    }
    else if (form == MV_SL)
    {
       switch (g)
       {
-         case 2:  launch_sl_mv_nv<2, OP>(plan, c, stage_elems, lds, xstride, bstride, ystride, auxstride, s); break;
-         case 3:  launch_sl_mv_nv<3, OP>(plan, c, stage_elems, lds, xstride, bstride, ystride, auxstride, s); break;
-         default: launch_sl_mv_nv<4, OP>(plan, c, stage_elems, lds, xstride, bstride, ystride, auxstride, s); break;
+         case 2:  launch_sl_mv_nv<2, OP>(plan, c, m, s); break;
+         case 3:  launch_sl_mv_nv<3, OP>(plan, c, m, s); break;
+         default: launch_sl_mv_nv<4, OP>(plan, c, m, s); break;
       }
    }
    else
    {
       switch (g)
       {
-         case 2: if (coded) launch_xs_mv<2, true, OP>(plan, c, stage_elems, MV_WIN, rp_cap, lds, xstride, bstride, ystride, auxstride, s);
-                 else       launch_xs_mv<2, false, OP>(plan, c, stage_elems, MV_WIN, rp_cap, lds, xstride, bstride, ystride, auxstride, s); break;
-         case 3: if (coded) launch_xs_mv<3, true, OP>(plan, c, stage_elems, MV_WIN, rp_cap, lds, xstride, bstride, ystride, auxstride, s);
-                 else       launch_xs_mv<3, false, OP>(plan, c, stage_elems, MV_WIN, rp_cap, lds, xstride, bstride, ystride, auxstride, s); break;
-         default: if (coded) launch_xs_mv<4, true, OP>(plan, c, stage_elems, MV_WIN, rp_cap, lds, xstride, bstride, ystride, auxstride, s);
-                  else       launch_xs_mv<4, false, OP>(plan, c, stage_elems, MV_WIN, rp_cap, lds, xstride, bstride, ystride, auxstride, s); break;
+         case 2: if (coded) launch_xs_mv<2, true, OP>(plan, c, m, s);
+                 else       launch_xs_mv<2, false, OP>(plan, c, m, s); break;
+         case 3: if (coded) launch_xs_mv<3, true, OP>(plan, c, m, s);
+                 else       launch_xs_mv<3, false, OP>(plan, c, m, s); break;
+         default: if (coded) launch_xs_mv<4, true, OP>(plan, c, m, s);
+                  else       launch_xs_mv<4, false, OP>(plan, c, m, s); break;
       }
    }
 }
@@ -3195,12 +3075,7 @@ bool launch_spmv_mv(const SpmvPlan *plan, const SpmvArgs &args, SpmvOp op, int n
    // (what takes_rs / takes_xs look at is in the caller's arguments)
    const int form = spmv_mv_form(plan, a, xstride);
    if (form == MV_NONE) { return false; }
-   a.last_quad = (plan->nnz > 0 ? (int) (plan->nnz - 1) : 0) & ~3;
-   a.x_last = plan->num_cols > 0 ? plan->num_cols - 1 : 0;
-   a.tile_perm = plan->d_tile_perm;
-   a.tile_fp = plan->d_tile_fp;
-   a.stale = plan->d_stale;
-   a.nnz = plan->nnz;
+   fill_plan_fields(a, plan);
    a.Ac8 = nullptr; a.dict = nullptr; a.ndict = 0; a.dict_rounded = 0; a.use_rs = form == MV_RS ? 1 : 0;
    const bool coded = form != MV_RS && plan->d_codes != nullptr;
    if (coded) { a.Ac8 = plan->d_codes; a.ndict = plan->ndict; a.dict = plan->d_dict; }
@@ -3219,14 +3094,14 @@ bool launch_spmv_mv(const SpmvPlan *plan, const SpmvArgs &args, SpmvOp op, int n
       // (4 per CU alone, 2 with two columns, 1 with three or four): twos, and a three where three columns are left
       // (not measured yet on a device: HYPRE_AMD_SPMV_RS_MV_COLS sets the group for such measurements)
       const int left = nv - v0;
-      int g, stage_elems = 0, rp_cap = 0;
+      int g;
+      MvLaunch m = {0, 0, 0, {xstride, bstride, ystride, auxstride}};
       if (form == MV_SL) { g = left == 4 ? 2 : std::min(3, left); }
       else if (form == MV_RS) { g = rs_mv_columns() ? std::min(rs_mv_columns(), left) : (left == 3 ? 3 : std::min(2, left)); }
       else { g = std::min(4, left); }
-      size_t lds = 0;
-      if (form == MV_SL) { while (g > 1 && (lds = sl_mv_lds_bytes(plan, g, a.ndict, stage_elems)) > (size_t) 160 * 1024) { g--; } }
-      else if (form == MV_RS) { while (g > 1 && (lds = rs_mv_lds_bytes(plan, g, stage_elems)) > (size_t) 160 * 1024) { g--; } }
-      else { while (g > 1 && (lds = mv_lds_bytes(plan, g, coded, a.ndict, stage_elems, rp_cap)) > (size_t) 160 * 1024) { g--; } }
+      if (form == MV_SL) { while (g > 1 && (m.lds = sl_mv_lds_bytes(plan, g, a.ndict, m.stage_elems)) > (size_t) 160 * 1024) { g--; } }
+      else if (form == MV_RS) { while (g > 1 && (m.lds = rs_mv_lds_bytes(plan, g, m.stage_elems)) > (size_t) 160 * 1024) { g--; } }
+      else { while (g > 1 && (m.lds = mv_lds_bytes(plan, g, coded, a.ndict, m.stage_elems, m.rp_cap)) > (size_t) 160 * 1024) { g--; } }
       SpmvArgs c = a;
       c.x = a.x + (size_t) v0 * xstride;
       c.y = a.y + (size_t) v0 * ystride;
@@ -3245,7 +3120,7 @@ bool launch_spmv_mv(const SpmvPlan *plan, const SpmvArgs &args, SpmvOp op, int n
       // bytes: the matrix once (CSR count: 12 bytes per entry and the row pointers; streamed: what the form holds per entry and
       // per tile or block), the vectors of every column
       double streamed;
-      if (form == MV_RS) { streamed = nz * 10.0 + (double) plan->rs_blocks * (4.0 * (4 * RS_HDR + SPMV_THREADS + XS_DESC)); }
+      if (form == MV_RS) { streamed = nz * 10.0 + rs_block_table_bytes(plan); }
       else if (form == MV_SL) { streamed = sl_matrix_bytes(plan, a.ndict); }
       else
       {
@@ -3255,9 +3130,9 @@ bool launch_spmv_mv(const SpmvPlan *plan, const SpmvArgs &args, SpmvOp op, int n
       account_bytes(nz * 12.0 + 4.0 * (nr + 1.0) + once + g * vecs, streamed + once + g * vecs);
       switch (op)
       {
-         case OP_JACOBI:    launch_mv_group<OP_JACOBI>(plan, c, form, g, coded, stage_elems, rp_cap, lds, xstride, bstride, ystride, auxstride, s); break;
-         case OP_AXPBY_DIV: launch_mv_group<OP_AXPBY_DIV>(plan, c, form, g, coded, stage_elems, rp_cap, lds, xstride, bstride, ystride, auxstride, s); break;
-         default:           launch_mv_group<OP_AXPBY>(plan, c, form, g, coded, stage_elems, rp_cap, lds, xstride, bstride, ystride, auxstride, s); break;
+         case OP_JACOBI:    launch_mv_group<OP_JACOBI>(plan, c, form, g, coded, m, s); break;
+         case OP_AXPBY_DIV: launch_mv_group<OP_AXPBY_DIV>(plan, c, form, g, coded, m, s); break;
+         default:           launch_mv_group<OP_AXPBY>(plan, c, form, g, coded, m, s); break;
       }
       v0 += g;
    }
