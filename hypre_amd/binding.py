@@ -218,6 +218,9 @@ PROTOTYPES = {
     "hypre_SeqVectorAxpy": (Int, [Real, Vecp, Vecp]),
     "hypre_SeqVectorAxpyz": (Int, [Real, Vecp, Real, Vecp, Vecp]),
     "hypre_SeqVectorInnerProd": (Real, [Vecp, Vecp]),
+    "hypre_SeqVectorMassInnerProd": (Int, [Vecp, C.POINTER(Vecp), Int, Int, RealP]),
+    "hypre_SeqVectorMassDotpTwo": (Int, [Vecp, Vecp, C.POINTER(Vecp), Int, Int, RealP, RealP]),
+    "hypre_SeqVectorMassAxpy": (Int, [RealP, C.POINTER(Vecp), Vecp, Int, Int]),
     "hypre_SeqVectorElmdivpy": (Int, [Vecp, Vecp, Vecp]),
     "hypre_SeqVectorElmdivpyMarked": (Int, [Vecp, Vecp, Vecp, IntP, Int]),
     "hypre_SeqVectorSetConstantValuesDevice": (Int, [Vecp, Real]),
@@ -268,6 +271,9 @@ PROTOTYPES = {
     "hypre_ParVectorAxpy": (Int, [Real, ParVecp, ParVecp]),
     "hypre_ParVectorAxpyz": (Int, [Real, ParVecp, Real, ParVecp, ParVecp]),
     "hypre_ParVectorInnerProd": (Real, [ParVecp, ParVecp]),
+    "hypre_ParVectorMassInnerProd": (Int, [ParVecp, C.POINTER(ParVecp), Int, Int, RealP]),
+    "hypre_ParVectorMassDotpTwo": (Int, [ParVecp, ParVecp, C.POINTER(ParVecp), Int, Int, RealP, RealP]),
+    "hypre_ParVectorMassAxpy": (Int, [RealP, C.POINTER(ParVecp), ParVecp, Int, Int]),
     "hypre_ParVectorElmdivpy": (Int, [ParVecp, ParVecp, ParVecp]),
     "hypre_ParVectorElmdivpyMarked": (Int, [ParVecp, ParVecp, ParVecp, IntP, Int]),
     "GenerateLaplacian": (ParCSRp, [Int, BigInt, BigInt, BigInt, Int, Int, Int, Int, Int, Int, RealP]),

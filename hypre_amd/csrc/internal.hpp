@@ -56,7 +56,8 @@ struct Handle
    // scratch for reductions: device partials + pinned host landing zone
    double               *d_reduce      = nullptr;
    size_t                d_reduce_len  = 0;
-   double               *h_reduce      = nullptr;  // pinned, 16 doubles
+   double               *h_reduce      = nullptr;  // pinned, 16 doubles to begin with (reduce_host grows it)
+   size_t                h_reduce_len  = 0;
    int                   num_cus       = 256;
    // OpenMP thread count the hybrid Gauss-Seidel sweeps emulate (row blocks of
    // hypre_partition1D; 1 = one block per rank); set by the cycle from the solver
@@ -81,6 +82,7 @@ int     host_cpu_share();                // cores this process may use: affinity
 hipStream_t stream();                    // compute stream
 void    maybe_sync();                    // honours hypre_SetSyncCudaCompute
 double *reduce_scratch(size_t n);        // >= n doubles of device scratch
+double *reduce_host(size_t n);           // >= n doubles of pinned host memory: where read-backs of reductions land
 
 // ---------------------------------------------------------------------------
 // SpMV plan: rows are binned into fixed-nnz tiles ("row blocks").  Tile b owns
@@ -362,6 +364,13 @@ void launch_scaled_recip(double w, const double *f, const double *d, double *z, 
 void launch_diagscale2(const double *diag, const double *x, double beta, double *y, double *z,
                        int computeY, size_t n, hipStream_t s);
 void launch_dot(const double *x, const double *y, size_t n, double *d_out, hipStream_t s);
+// batched BLAS-1 (mass_kernels.hip): k vectors in chunks of MASS_CHUNK, every vector read once per chunk.  The dots
+// return where their k (2 k: <x, z_j> first, <y, z_j> behind) sums lie in device scratch, valid until the next
+// reduction; sum j has the bits of launch_dot(x, y_j), the update those of k launch_axpy calls in order.
+constexpr int MASS_CHUNK = 8;
+double *launch_mass_dot(const double *x, const double *const *y, int k, size_t n, hipStream_t s);
+double *launch_mass_dot_two(const double *x, const double *y, const double *const *z, int k, size_t n, hipStream_t s);
+void launch_mass_axpy(const double *alpha, const double *const *x, double *y, int k, size_t n, hipStream_t s);
 void launch_gather(const double *x, const int *idx, double *out, size_t n, hipStream_t s);
 void launch_scatter_add(const double *in, const int *idx, double *y, size_t n, hipStream_t s);
 void launch_f64_to_f32(const double *x, float *y, size_t n, hipStream_t s);
@@ -388,7 +397,7 @@ void launch_mc_small_sweep(int num_colors, int direction, const int *cstart, con
                            double w, double *u, int n, int nnz, hipStream_t s);
 // one per kernel file: loads its code object (runtime.cpp: ensure_device)
 void preload_cheby_kernels(); void preload_gs_kernels(); void preload_interp_kernels(); void preload_vector_kernels();
-void preload_rap_kernels(); void preload_setup_kernels(); void preload_spmv_kernels();
+void preload_rap_kernels(); void preload_setup_kernels(); void preload_spmv_kernels(); void preload_mass_kernels();
 // setup_kernels.hip: strength of connection, PMIS, coarse numbering and smoother diagonals of a single-rank level
 void device_strength(int n, const int *Ai, const int *Aj, const double *Aa, double theta, double max_row_sum,
                      int **Si_out, int **Sj_out, int *nnz_out, hipStream_t s);
@@ -447,7 +456,7 @@ void launch_pcg_update(double a, double na, const double *p, const double *s, do
 void launch_pcg_direction(double beta, const double *s, double *p, size_t n, hipStream_t stream);
 double global_sum(MPI_Comm comm, double v);     // scalar all-reduce over a communicator (identity on one rank)
 void   dev_allreduce_sum(MPI_Comm comm, double *d_buf, int n);                 // in place, device memory, stream-ordered
-void   dev_global_sums(MPI_Comm comm, double *d_vals, int n, double *h_out);   // n <= 8 device partials -> global sums on the host
+void   dev_global_sums(MPI_Comm comm, double *d_vals, int n, double *h_out);   // n device partials -> global sums on the host
 void launch_scale_copy(double b, const double *x, double *y, size_t n, hipStream_t s);   // y = b*x
 
 }  // namespace hamd

@@ -10,37 +10,14 @@
 //   seq_mv/vector_device.c              axpy / scale / dot via rocBLAS+thrust
 
 #include "amg_internal.hpp"
+#include "blas1_device.hpp"
 
 namespace hamd {
 
 // ---------------------------------------------------------------------------
-// small device helpers
+// BLAS-1.  All are grid-stride with two doubles (16 B) per lane per step (VEC_LOOP, vec_grid and the
+// lane sum: blas1_device.hpp).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v)
-{
-   // 64-lane butterfly; __shfl_xor lowers to ds_swizzle / DPP on gfx950
-#pragma unroll
-   for (int off = 32; off > 0; off >>= 1) { v += __shfl_xor(v, off, 64); }
-   return v;
-}
-
-// ---------------------------------------------------------------------------
-// BLAS-1.  All are grid-stride with two doubles (16 B) per lane per step.
-// ---------------------------------------------------------------------------
-static inline int vec_grid(size_t n)
-{
-   size_t g = (n / 2 + 255) / 256;
-   if (g > 2048) { g = 2048; }
-   if (g < 1) { g = 1; }
-   return (int) g;
-}
-
-#define VEC_LOOP_BEGIN                                                                   \
-   const size_t n2 = n >> 1;                                                             \
-   const size_t stride = (size_t) gridDim.x * blockDim.x;                                \
-   for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += stride) {
-#define VEC_LOOP_END }
-
 __global__ void set_kernel(double *__restrict__ y, double v, size_t n)
 {
    VEC_LOOP_BEGIN
@@ -177,7 +154,6 @@ __global__ void diagscale2_kernel(const double *__restrict__ diag, const double 
 
 // dot product: per-workgroup partials, then one workgroup folds them in a fixed
 // order (bitwise reproducible run to run for a fixed n).
-constexpr int DOT_BLOCKS = 1024;
 __global__ __launch_bounds__(256)
 void dot_partial_kernel(const double *__restrict__ x, const double *__restrict__ y, size_t n,
                         double *__restrict__ partial)
@@ -187,9 +163,9 @@ void dot_partial_kernel(const double *__restrict__ x, const double *__restrict__
    VEC_LOOP_BEGIN
       const double2 xv = reinterpret_cast<const double2 *>(x)[i];
       const double2 yv = reinterpret_cast<const double2 *>(y)[i];
-      acc += xv.x * yv.x + xv.y * yv.y;
+      acc += dot_pair(xv, yv);
    VEC_LOOP_END
-   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) { acc += x[n - 1] * y[n - 1]; }
+   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) { acc = dot_last(x[n - 1], y[n - 1], acc); }
    acc = wave_sum(acc);
    if ((threadIdx.x & 63) == 0) { wsum[threadIdx.x >> 6] = acc; }
    __syncthreads();

@@ -1,0 +1,249 @@
+// hypre_amd — batched vector kernels for gfx950 (CDNA4): many dot products against one vector, and one vector updated
+// with many, in one pass over HBM each.  They are what the classical Gram-Schmidt of COGMRES (par_cogmres.cpp) is built
+// on: step i of a restart cycle needs <p_i, p_j> for all j < i and p_i -= sum_j h_j p_j, which as separate dots and
+// axpys is 5 i vector passes and i read-backs; batched it is 2 i + 2 passes and one read-back.
+//
+// Replaces (behaviourally) the host loops of
+//   seq_mv/vector_batched.c   hypre_SeqVectorMassInnerProd / MassDotpTwo / MassAxpy (and their 4- and 8-fold unrollings)
+//
+// Pure streaming work: 16-byte loads, K + 1 (K + 2) loads in flight per lane, no LDS beyond the wave-sum slots.  The
+// vectors' addresses and the coefficients travel by value in the kernel arguments, and K is a template parameter with
+// fully unrolled loops, so the accumulators stay in registers.  Every result has the bits the one-at-a-time kernels of
+// kernels.hip give: same grid, same walk, same per-pair term, same fold.
+
+#include "amg_internal.hpp"
+#include "blas1_device.hpp"
+
+namespace hamd {
+
+template <int K> struct MassVectors { const double *p[K]; };
+template <int K> struct MassCoefficients { double a[K]; };
+
+// a workgroup's partial of accumulator j, folded like dot_partial_kernel folds its one
+#define MASS_FOLD(acc, wsum, J)                                                          \
+   _Pragma("unroll")                                                                     \
+   for (int j = 0; j < (J); j++)                                                         \
+   {                                                                                     \
+      const double v = wave_sum(acc[j]);                                                 \
+      if ((threadIdx.x & 63) == 0) { wsum[j][threadIdx.x >> 6] = v; }                    \
+   }                                                                                     \
+   __syncthreads();                                                                      \
+   if (threadIdx.x < (J))                                                                \
+   {                                                                                     \
+      const int j = threadIdx.x;                                                         \
+      partial[(size_t) j * DOT_BLOCKS + blockIdx.x] = (wsum[j][0] + wsum[j][1]) + (wsum[j][2] + wsum[j][3]); \
+   }
+
+// partial[j * DOT_BLOCKS + block] = this workgroup's share of <x, y_j>, j < K
+template <int K>
+__global__ __launch_bounds__(256)
+void mass_dot_kernel(const double *__restrict__ x, const MassVectors<K> y, size_t n, double *__restrict__ partial)
+{
+   __shared__ double wsum[K][4];
+   double acc[K];
+#pragma unroll
+   for (int j = 0; j < K; j++) { acc[j] = 0.0; }
+   VEC_LOOP_BEGIN
+      const double2 xv = reinterpret_cast<const double2 *>(x)[i];
+      double2 yv[K];
+#pragma unroll
+      for (int j = 0; j < K; j++) { yv[j] = reinterpret_cast<const double2 *>(y.p[j])[i]; }
+#pragma unroll
+      for (int j = 0; j < K; j++) { acc[j] += dot_pair(xv, yv[j]); }
+   VEC_LOOP_END
+   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
+   {
+#pragma unroll
+      for (int j = 0; j < K; j++) { acc[j] = dot_last(x[n - 1], y.p[j][n - 1], acc[j]); }
+   }
+   MASS_FOLD(acc, wsum, K)
+}
+
+// the same for two vectors at once: accumulators j < K hold <x, z_j>, accumulators K + j hold <y, z_j>
+template <int K>
+__global__ __launch_bounds__(256)
+void mass_dot_two_kernel(const double *__restrict__ x, const double *__restrict__ y, const MassVectors<K> z, size_t n,
+                         double *__restrict__ partial)
+{
+   __shared__ double wsum[2 * K][4];
+   double acc[2 * K];
+#pragma unroll
+   for (int j = 0; j < 2 * K; j++) { acc[j] = 0.0; }
+   VEC_LOOP_BEGIN
+      const double2 xv = reinterpret_cast<const double2 *>(x)[i];
+      const double2 yv = reinterpret_cast<const double2 *>(y)[i];
+      double2 zv[K];
+#pragma unroll
+      for (int j = 0; j < K; j++) { zv[j] = reinterpret_cast<const double2 *>(z.p[j])[i]; }
+#pragma unroll
+      for (int j = 0; j < K; j++)
+      {
+         acc[j] += dot_pair(xv, zv[j]);
+         acc[K + j] += dot_pair(yv, zv[j]);
+      }
+   VEC_LOOP_END
+   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
+   {
+#pragma unroll
+      for (int j = 0; j < K; j++)
+      {
+         acc[j] = dot_last(x[n - 1], z.p[j][n - 1], acc[j]);
+         acc[K + j] = dot_last(y[n - 1], z.p[j][n - 1], acc[K + j]);
+      }
+   }
+   MASS_FOLD(acc, wsum, 2 * K)
+}
+
+// workgroup b folds the m partials of accumulator b exactly as dot_final_kernel folds those of one dot product; the
+// first `split` accumulators land in out_a, the others in out_b
+__global__ __launch_bounds__(256)
+void mass_dot_final_kernel(const double *__restrict__ partial, int m, int split, double *__restrict__ out_a, double *__restrict__ out_b)
+{
+   __shared__ double wsum[4];
+   const int b = blockIdx.x;
+   partial += (size_t) b * DOT_BLOCKS;
+   double acc = 0.0;
+   for (int i = threadIdx.x; i < m; i += 256) { acc += partial[i]; }
+   acc = wave_sum(acc);
+   if ((threadIdx.x & 63) == 0) { wsum[threadIdx.x >> 6] = acc; }
+   __syncthreads();
+   if (threadIdx.x == 0)
+   {
+      const double r = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+      if (b < split) { out_a[b] = r; } else { out_b[b - split] = r; }
+   }
+}
+
+// y += a_0 x_0, then += a_1 x_1, ... in that order, each step rounded like axpy_kernel rounds its one (a fused
+// multiply-add); y is read and written once.  No restrict: an x_j may be y, as for axpy_kernel.
+template <int K>
+__global__ void mass_axpy_kernel(const MassCoefficients<K> alpha, const MassVectors<K> x, double *y, size_t n)
+{
+   VEC_LOOP_BEGIN
+      double2 t = reinterpret_cast<double2 *>(y)[i];
+      double2 xv[K];
+#pragma unroll
+      for (int j = 0; j < K; j++) { xv[j] = reinterpret_cast<const double2 *>(x.p[j])[i]; }
+#pragma unroll
+      for (int j = 0; j < K; j++)
+      {
+         t.x = __fma_rn(alpha.a[j], xv[j].x, t.x);
+         t.y = __fma_rn(alpha.a[j], xv[j].y, t.y);
+      }
+      reinterpret_cast<double2 *>(y)[i] = t;
+   VEC_LOOP_END
+   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
+   {
+      double t = y[n - 1];
+#pragma unroll
+      for (int j = 0; j < K; j++) { t = __fma_rn(alpha.a[j], x.p[j][n - 1], t); }
+      y[n - 1] = t;
+   }
+}
+
+// ---------------------------------------------------------------------------
+// launchers: k vectors in chunks of MASS_CHUNK, one kernel instance per chunk length
+// ---------------------------------------------------------------------------
+namespace {
+inline int dot_grid(size_t n)
+{
+   const int nb = vec_grid(n);
+   return nb > DOT_BLOCKS ? DOT_BLOCKS : nb;
+}
+// device scratch of a batched dot: room for `results` sums in front (a multiple of 16 doubles), the partials of one chunk behind
+inline double *mass_scratch(int results, double **partial)
+{
+   const size_t front = ((size_t) results + 15) & ~(size_t) 15;
+   double *base = reduce_scratch(front + 2 * (size_t) MASS_CHUNK * DOT_BLOCKS);
+   *partial = base + front;
+   return base;
+}
+
+template <int K>
+void mass_dot_chunk(const double *x, const double *const *y, size_t n, int nb, double *partial, hipStream_t s)
+{
+   MassVectors<K> v;
+   for (int j = 0; j < K; j++) { v.p[j] = y[j]; }
+   hipLaunchKernelGGL(mass_dot_kernel<K>, dim3(nb), dim3(256), 0, s, x, v, n, partial);
+}
+template <int K>
+void mass_dot_two_chunk(const double *x, const double *y, const double *const *z, size_t n, int nb, double *partial, hipStream_t s)
+{
+   MassVectors<K> v;
+   for (int j = 0; j < K; j++) { v.p[j] = z[j]; }
+   hipLaunchKernelGGL(mass_dot_two_kernel<K>, dim3(nb), dim3(256), 0, s, x, y, v, n, partial);
+}
+template <int K>
+void mass_axpy_chunk(const double *alpha, const double *const *x, double *y, size_t n, hipStream_t s)
+{
+   MassCoefficients<K> a;
+   MassVectors<K> v;
+   for (int j = 0; j < K; j++) { a.a[j] = alpha[j]; v.p[j] = x[j]; }
+   hipLaunchKernelGGL(mass_axpy_kernel<K>, dim3(vec_grid(n)), dim3(256), 0, s, a, v, y, n);
+}
+}  // namespace
+
+#define MASS_DISPATCH(kk, CALL)                                                          \
+   switch (kk)                                                                           \
+   {                                                                                     \
+      case 1: CALL(1); break;                                                            \
+      case 2: CALL(2); break;                                                            \
+      case 3: CALL(3); break;                                                            \
+      case 4: CALL(4); break;                                                            \
+      case 5: CALL(5); break;                                                            \
+      case 6: CALL(6); break;                                                            \
+      case 7: CALL(7); break;                                                            \
+      default: CALL(8); break;                                                           \
+   }
+static_assert(MASS_CHUNK == 8, "the dispatch lists the chunk lengths 1 .. 8");
+
+double *launch_mass_dot(const double *x, const double *const *y, int k, size_t n, hipStream_t s)
+{
+   double *partial;
+   double *out = mass_scratch(k, &partial);
+   const int nb = dot_grid(n);
+   for (int c = 0; c < k; c += MASS_CHUNK)
+   {
+      const int kk = k - c < MASS_CHUNK ? k - c : MASS_CHUNK;
+      account_bytes(8.0 * (kk + 1) * n);
+#define CALL(K) mass_dot_chunk<K>(x, y + c, n, nb, partial, s)
+      MASS_DISPATCH(kk, CALL)
+#undef CALL
+      hipLaunchKernelGGL(mass_dot_final_kernel, dim3(kk), dim3(256), 0, s, partial, nb, kk, out + c, out + c);
+   }
+   return out;
+}
+
+double *launch_mass_dot_two(const double *x, const double *y, const double *const *z, int k, size_t n, hipStream_t s)
+{
+   double *partial;
+   double *out = mass_scratch(2 * k, &partial);
+   const int nb = dot_grid(n);
+   for (int c = 0; c < k; c += MASS_CHUNK)
+   {
+      const int kk = k - c < MASS_CHUNK ? k - c : MASS_CHUNK;
+      account_bytes(8.0 * (kk + 2) * n);
+#define CALL(K) mass_dot_two_chunk<K>(x, y, z + c, n, nb, partial, s)
+      MASS_DISPATCH(kk, CALL)
+#undef CALL
+      hipLaunchKernelGGL(mass_dot_final_kernel, dim3(2 * kk), dim3(256), 0, s, partial, nb, kk, out + c, out + k + c);
+   }
+   return out;
+}
+
+void launch_mass_axpy(const double *alpha, const double *const *x, double *y, int k, size_t n, hipStream_t s)
+{
+   if (!n) { return; }
+   for (int c = 0; c < k; c += MASS_CHUNK)
+   {
+      const int kk = k - c < MASS_CHUNK ? k - c : MASS_CHUNK;
+      account_bytes(8.0 * (kk + 2) * n);
+#define CALL(K) mass_axpy_chunk<K>(alpha + c, x + c, y, n, s)
+      MASS_DISPATCH(kk, CALL)
+#undef CALL
+   }
+}
+
+void preload_mass_kernels() { hipFuncAttributes at; (void) hipFuncGetAttributes(&at, (const void *) mass_dot_final_kernel); (void) hipGetLastError(); }
+
+}  // namespace hamd

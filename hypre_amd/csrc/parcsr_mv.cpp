@@ -187,13 +187,13 @@ void dev_allreduce_sum(MPI_Comm comm, double *d_buf, int n)
    }
 }
 
-// Sum over the ranks of n (<= 8) doubles that sit in device memory, returned on the host: one device all-reduce and
+// Sum over the ranks of n doubles that sit in device memory, returned on the host: one device all-reduce and
 // one read-back when the transport takes device buffers (otherwise read back, then reduce on the host).
 void dev_global_sums(MPI_Comm comm, double *d_vals, int n, double *h_out)
 {
    const hypre_amd_CommOps *o = comm_ops(comm);
    Handle &hd = handle();
-   double *h = hd.h_reduce;
+   double *h = reduce_host((size_t) n);
    if (o && o->size > 1 && o->device_buffers) { dev_allreduce_sum(comm, d_vals, n); }
    HIP_CHECK(hipMemcpyAsync(h, d_vals, sizeof(double) * (size_t) n, hipMemcpyDeviceToHost, hd.compute_stream));
    HIP_CHECK(hipStreamSynchronize(hd.compute_stream));
@@ -451,6 +451,54 @@ HYPRE_Real hypre_ParVectorInnerProd(hypre_ParVector *x, hypre_ParVector *y)
    double r = 0.0;
    dev_global_sums(x->comm, d_out, 1, &r);
    return r;
+}
+// ---- batched BLAS-1 (par_vector_batched.c:21-140): the local kernels, then ONE reduction of all k (2 k) sums
+static bool par_mass_on_device(hypre_ParVector *const *v, HYPRE_Int k)
+{
+   for (HYPRE_Int j = 0; j < k; j++) { if (v[j]->local_vector->memory_location != HYPRE_MEMORY_DEVICE) { return false; } }
+   return true;
+}
+HYPRE_Int hypre_ParVectorMassAxpy(HYPRE_Complex *alpha, hypre_ParVector **x, hypre_ParVector *y, HYPRE_Int k, HYPRE_Int unroll)
+{
+   if (k <= 0) { return hypre_error_flag; }
+   std::vector<hypre_Vector *> xl((size_t) k);
+   for (HYPRE_Int j = 0; j < k; j++) { xl[(size_t) j] = x[j]->local_vector; }
+   return hypre_SeqVectorMassAxpy(alpha, xl.data(), y->local_vector, k, unroll);
+}
+HYPRE_Int hypre_ParVectorMassInnerProd(hypre_ParVector *x, hypre_ParVector **y, HYPRE_Int k, HYPRE_Int unroll, HYPRE_Real *result)
+{
+   (void) unroll;
+   if (k <= 0) { return hypre_error_flag; }
+   hypre_Vector *xl = x->local_vector;
+   if (xl->memory_location != HYPRE_MEMORY_DEVICE || !par_mass_on_device(y, k))
+   {
+      hypre_error_w_msg(HYPRE_ERROR_GENERIC, "hypre_ParVectorMassInnerProd: operand is not in device memory; host execution is not part of this library");
+      return hypre_error_flag;
+   }
+   std::vector<const double *> yd((size_t) k);
+   for (HYPRE_Int j = 0; j < k; j++) { yd[(size_t) j] = y[j]->local_vector->data; }
+   double *d_out = launch_mass_dot(xl->data, yd.data(), k, (size_t) xl->size * (size_t) xl->num_vectors, stream());
+   dev_global_sums(x->comm, d_out, k, result);
+   return hypre_error_flag;
+}
+HYPRE_Int hypre_ParVectorMassDotpTwo(hypre_ParVector *x, hypre_ParVector *y, hypre_ParVector **z, HYPRE_Int k, HYPRE_Int unroll,
+                                     HYPRE_Real *result_x, HYPRE_Real *result_y)
+{
+   (void) unroll;
+   if (k <= 0) { return hypre_error_flag; }
+   hypre_Vector *xl = x->local_vector, *yl = y->local_vector;
+   if (xl->memory_location != HYPRE_MEMORY_DEVICE || yl->memory_location != HYPRE_MEMORY_DEVICE || !par_mass_on_device(z, k))
+   {
+      hypre_error_w_msg(HYPRE_ERROR_GENERIC, "hypre_ParVectorMassDotpTwo: operand is not in device memory; host execution is not part of this library");
+      return hypre_error_flag;
+   }
+   std::vector<const double *> zd((size_t) k);
+   for (HYPRE_Int j = 0; j < k; j++) { zd[(size_t) j] = z[j]->local_vector->data; }
+   double *d_out = launch_mass_dot_two(xl->data, yl->data, zd.data(), k, (size_t) xl->size * (size_t) xl->num_vectors, stream());
+   std::vector<HYPRE_Real> sums(2 * (size_t) k);
+   dev_global_sums(x->comm, d_out, 2 * k, sums.data());
+   for (HYPRE_Int j = 0; j < k; j++) { result_x[j] = sums[(size_t) j]; result_y[j] = sums[(size_t) k + (size_t) j]; }
+   return hypre_error_flag;
 }
 // x = y ./ diag(A), column by column of a multivector (par_csr_matop.c:6479-6658: the first entry of every row of the local
 // block is its diagonal)

@@ -115,9 +115,11 @@ bool ensure_device()
       h.device_ok = false;
       return false;
    }
+   h.h_reduce_len = 16;
    h.device_ok = true;
    preload_cheby_kernels(); preload_gs_kernels(); preload_interp_kernels(); preload_vector_kernels();
    preload_rap_kernels(); preload_setup_kernels(); preload_spmv_kernels(); preload_dist_setup_kernels(); preload_mc_kernels();
+   preload_mass_kernels();
    return true;
 }
 
@@ -144,6 +146,22 @@ double *reduce_scratch(size_t n)
       h.d_reduce_len = len;
    }
    return h.d_reduce;
+}
+
+double *reduce_host(size_t n)
+{
+   Handle &h = handle();
+   if (h.h_reduce_len < n)
+   {
+      // nothing is in flight towards the old block: every read-back is followed by a synchronisation of its stream
+      if (h.h_reduce) { HIP_CHECK(hipHostFree(h.h_reduce)); }
+      h.h_reduce = nullptr;
+      h.h_reduce_len = 0;
+      const size_t len = n < 256 ? 256 : n;
+      HIP_CHECK(hipHostMalloc((void **) &h.h_reduce, len * sizeof(double), hipHostMallocDefault));
+      if (h.h_reduce) { h.h_reduce_len = len; }
+   }
+   return h.h_reduce;
 }
 
 }  // namespace hamd

@@ -1422,6 +1422,72 @@ HYPRE_Real hypre_SeqVectorInnerProd(hypre_Vector *x, hypre_Vector *y)
    return hypre_SeqVectorInnerProdDevice(x, y);
 }
 
+// ---- batched BLAS-1 (seq_mv/vector_batched.c): k vectors at once, every vector read once per chunk of MASS_CHUNK, the
+// k sums read back in one copy.  `unroll` picks among the reference's host loop unrollings and has no meaning here.
+static bool mass_operands_on_device(hypre_Vector *const *v, HYPRE_Int k)
+{
+   for (HYPRE_Int j = 0; j < k; j++) { if (v[j]->memory_location != HYPRE_MEMORY_DEVICE) { return false; } }
+   return true;
+}
+static void mass_read_back(const double *d_vals, HYPRE_Int n, HYPRE_Real *a, HYPRE_Real *b, HYPRE_Int split)
+{
+   hipStream_t s = stream();
+   double *h = reduce_host((size_t) n);
+   HIP_CHECK(hipMemcpyAsync(h, d_vals, sizeof(double) * (size_t) n, hipMemcpyDeviceToHost, s));
+   HIP_CHECK(hipStreamSynchronize(s));
+   for (HYPRE_Int j = 0; j < split; j++) { a[j] = h[j]; }
+   for (HYPRE_Int j = split; j < n; j++) { b[j - split] = h[j]; }
+}
+
+HYPRE_Int hypre_SeqVectorMassInnerProd(hypre_Vector *x, hypre_Vector **y, HYPRE_Int k, HYPRE_Int unroll, HYPRE_Real *result)
+{
+   (void) unroll;
+   if (k <= 0) { return hypre_error_flag; }
+   if (x->memory_location != HYPRE_MEMORY_DEVICE || !mass_operands_on_device(y, k))
+   {
+      hypre_error_w_msg(HYPRE_ERROR_GENERIC, "hypre_SeqVectorMassInnerProd: operand is not in device memory; host execution is not part of this library");
+      return hypre_error_flag;
+   }
+   std::vector<const double *> yd((size_t) k);
+   for (HYPRE_Int j = 0; j < k; j++) { yd[(size_t) j] = y[j]->data; }
+   const double *d_out = launch_mass_dot(x->data, yd.data(), k, vlen(x), stream());
+   mass_read_back(d_out, k, result, nullptr, k);
+   return hypre_error_flag;
+}
+
+HYPRE_Int hypre_SeqVectorMassDotpTwo(hypre_Vector *x, hypre_Vector *y, hypre_Vector **z, HYPRE_Int k, HYPRE_Int unroll,
+                                     HYPRE_Real *result_x, HYPRE_Real *result_y)
+{
+   (void) unroll;
+   if (k <= 0) { return hypre_error_flag; }
+   if (x->memory_location != HYPRE_MEMORY_DEVICE || y->memory_location != HYPRE_MEMORY_DEVICE || !mass_operands_on_device(z, k))
+   {
+      hypre_error_w_msg(HYPRE_ERROR_GENERIC, "hypre_SeqVectorMassDotpTwo: operand is not in device memory; host execution is not part of this library");
+      return hypre_error_flag;
+   }
+   std::vector<const double *> zd((size_t) k);
+   for (HYPRE_Int j = 0; j < k; j++) { zd[(size_t) j] = z[j]->data; }
+   const double *d_out = launch_mass_dot_two(x->data, y->data, zd.data(), k, vlen(x), stream());
+   mass_read_back(d_out, 2 * k, result_x, result_y, k);
+   return hypre_error_flag;
+}
+
+HYPRE_Int hypre_SeqVectorMassAxpy(HYPRE_Complex *alpha, hypre_Vector **x, hypre_Vector *y, HYPRE_Int k, HYPRE_Int unroll)
+{
+   (void) unroll;
+   if (k <= 0) { return hypre_error_flag; }
+   if (y->memory_location != HYPRE_MEMORY_DEVICE || !mass_operands_on_device(x, k))
+   {
+      hypre_error_w_msg(HYPRE_ERROR_GENERIC, "hypre_SeqVectorMassAxpy: operand is not in device memory; host execution is not part of this library");
+      return hypre_error_flag;
+   }
+   std::vector<const double *> xd((size_t) k);
+   for (HYPRE_Int j = 0; j < k; j++) { xd[(size_t) j] = x[j]->data; }
+   launch_mass_axpy(alpha, xd.data(), y->data, k, vlen(y), stream());
+   maybe_sync();
+   return hypre_error_flag;
+}
+
 HYPRE_Int hypre_SeqVectorElmdivpyDevice(hypre_Vector *x, hypre_Vector *b, hypre_Vector *y,
                                         HYPRE_Int *marker, HYPRE_Int marker_val)
 {

@@ -25,10 +25,12 @@ class IJOptions:
         self.sys_num_fun = 1          # -sysL <num functions>: systems version of the 7-point operator
         self.c = (1.0, 1.0, 1.0)      # -c cx cy cz
         self.a = (1.0, 1.0, 1.0)      # -a ax ay az (difconv)
-        self.solver = 0               # 0 AMG, 1 AMG-PCG, 2 DS-PCG (diagonal scaling), 3 AMG-GMRES, 4 DS-GMRES
+        self.solver = 0               # 0 AMG, 1 AMG-PCG, 2 DS-PCG (diagonal scaling), 3 AMG-GMRES, 4 DS-GMRES, 16 AMG-COGMRES, 17 DS-COGMRES
         self.neg_a = 0                # -negA 1: solve with -A (test/ij.c:4014-4017)
         self.num_components = 1       # -nc: columns of b and x (multivectors; test/ij.c:874-878, 3400-3404)
         self.k_dim = 5                # -k (GMRES restart length, test/ij.c:1731)
+        self.cgs = 1                  # -cgs (COGMRES: 1 classical Gram-Schmidt, 2 with reorthogonalisation; test/ij.c:1746-1750)
+        self.unroll = 0               # -unroll (COGMRES: host loop unrolling of the reference; accepted, no effect; test/ij.c:1751-1755)
         self.flex = 0                 # -flex (flexible PCG: Polak-Ribiere beta)
         self.rhs = "one"              # one (-rhsisone default) | rand (-rhsrand) | xisone
         self.fromfile = None          # -fromfile <name>: matrix from IJ text files <name>.<rank %05d>
@@ -306,7 +308,7 @@ _VALUE_FLAGS = {
     "-tr": ("trunc_factor", float, 1), "-Pmx": ("P_max_elmts", int, 1), "-interptype": ("interp_type", int, 1),
     "-tol": ("tol", float, 1), "-max_iter": ("max_iter", int, 1), "-mg_max_iter": ("mg_max_iter", int, 1),
     "-mxl": ("max_levels", int, 1), "-coarse_th": ("coarse_threshold", int, 1), "-keepT": ("keep_transpose", int, 1),
-    "-precon_cycles": ("precon_cycles", int, 1), "-k": ("k_dim", int, 1), "-nc": ("num_components", int, 1), "-negA": ("neg_a", int, 1), "-nf": ("num_functions", int, 1), "-flex": ("flex", int, 1),
+    "-precon_cycles": ("precon_cycles", int, 1), "-k": ("k_dim", int, 1), "-cgs": ("cgs", int, 1), "-unroll": ("unroll", int, 1), "-nc": ("num_components", int, 1), "-negA": ("neg_a", int, 1), "-nf": ("num_functions", int, 1), "-flex": ("flex", int, 1),
     "-alpha": ("alpha", float, 1), "-eps": ("eps", float, 1), "-sysL": ("sys_num_fun", int, 1), "-ff": ("filter_functions", int, 1),
     "-cheby_order": ("cheby_order", int, 1), "-cheby_eig_est": ("cheby_eig_est", int, 1),
     "-cheby_variant": ("cheby_variant", int, 1), "-cheby_scale": ("cheby_scale", int, 1),
@@ -358,11 +360,15 @@ def parse_cli(argv):
             i += 3
         else:
             raise SystemExit("ij: option %s is outside the scope of this driver" % flag)
-    if opt.solver not in (0, 1, 2, 3, 4):
-        raise SystemExit("ij: -solver %d is outside the scope of this driver (0 AMG, 1 AMG-PCG, 2 DS-PCG, 3 AMG-GMRES, 4 DS-GMRES)" % opt.solver)
+    if opt.solver not in (0, 1, 2, 3, 4, 16, 17):
+        raise SystemExit("ij: -solver %d is outside the scope of this driver (0 AMG, 1 AMG-PCG, 2 DS-PCG, 3 AMG-GMRES, 4 DS-GMRES, "
+                         "16 AMG-COGMRES, 17 DS-COGMRES)" % opt.solver)
     if opt.num_components < 1 or (opt.num_components > 1 and (opt.rhs != "one" or opt.rhsfromfile)):
         # test/ij.c:3400-3404 takes several components with the constant right-hand sides only
         raise SystemExit("ij: -nc %d needs -rhsisone in this driver" % opt.num_components)
+    if opt.num_components > 1 and opt.solver in (16, 17):
+        raise SystemExit("ij: -nc %d with -solver %d: COGMRES doesn't take multicomponent vectors in this driver (GMRES, -solver 3 | 4, does)"
+                         % (opt.num_components, opt.solver))
     if opt.num_components > 1 and opt.solver in (0, 1, 3):
         # BoomerAMG on multivectors (hypre_BoomerAMGSolve with num_vectors > 1) serves l1-Jacobi / Jacobi 7 / 18 and two-stage
         # Gauss-Seidel 11 / 12 over all points with a direct coarsest-level solve; the reference refuses hybrid Gauss-Seidel
@@ -415,7 +421,7 @@ def run(opt, comm=0, rank=0, nprocs=1, allreduce=None, out=None):
     out = out or sys.stdout
     L = B.load_library()
     A = build_matrix(opt, comm=comm, rank=rank, nprocs=nprocs)
-    if opt.solver in (2, 4):
+    if opt.solver in (2, 4, 17):
         return run_ds_pcg(opt, A, comm=comm, rank=rank, allreduce=allreduce, out=out)
     s = create_amg(opt, memory_location=DEVICE)
     L.HYPRE_BoomerAMGSetup(s, A, None, None)
@@ -471,6 +477,9 @@ def run(opt, comm=0, rank=0, nprocs=1, allreduce=None, out=None):
     elif opt.solver == 3:
         its.value, rel.value = solve_gmres(opt, s, A, db, dx, comm=comm)
         lines += ["", "GMRES Iterations = %d" % its.value, "Final GMRES Relative Residual Norm = %e" % rel.value, ""]
+    elif opt.solver == 16:
+        its.value, rel.value = solve_cogmres(opt, A, db, dx, comm=comm, amg=s)
+        lines += ["", "COGMRES Iterations = %d" % its.value, "Final COGMRES Relative Residual Norm = %e" % rel.value, ""]
     else:
         L.HYPRE_BoomerAMGSetTol(s, 0.0)
         L.HYPRE_BoomerAMGSetMaxIter(s, opt.precon_cycles)
@@ -556,12 +565,12 @@ def run_ds_pcg(opt, A, comm=0, rank=0, allreduce=None, out=None):
     else:
         db = B.parvec_from_numpy(b, comm=comm, global_size=nglob, first=first)
         dx = B.parvec_from_numpy(x0, comm=comm, global_size=nglob, first=first)
-    its, rel = (solve_ds_gmres if opt.solver == 4 else solve_ds_pcg)(opt, A, db, dx, comm=comm)
+    its, rel = {2: solve_ds_pcg, 4: solve_ds_gmres, 17: solve_cogmres}[opt.solver](opt, A, db, dx, comm=comm)
     L.HYPRE_ClearError(256)
     B.check()
     L.hypre_ParVectorDestroy(db); L.hypre_ParVectorDestroy(dx)
     if rank == 0:
-        tag = "GMRES " if opt.solver == 4 else ""
+        tag = {4: "GMRES ", 17: "COGMRES "}.get(opt.solver, "")
         out.write("\n".join(["", "%sIterations = %d" % (tag, its), "Final %sRelative Residual Norm = %e" % (tag, rel), ""]) + "\n")
         out.flush()
     return its, rel
@@ -585,6 +594,36 @@ def solve_gmres(opt, amg, A, b, x, comm=0):
     L.HYPRE_GMRESGetNumIterations(g, C.byref(its))
     L.HYPRE_GMRESGetFinalRelativeResidualNorm(g, C.byref(rel))
     L.HYPRE_ParCSRGMRESDestroy(g)
+    return its.value, rel.value
+
+
+def solve_cogmres(opt, A, b, x, comm=0, amg=None):
+    """test/ij.c:8426-8440, 8583-8598, 8710-8722: COGMRES behind BoomerAMG (solver 16, `amg` the set-up hierarchy) or behind the
+    diagonal scaling preconditioner (solver 17)."""
+    L = B.load_library()
+    g = C.c_void_p()
+    L.HYPRE_ParCSRCOGMRESCreate(comm, C.byref(g))
+    L.HYPRE_COGMRESSetKDim(g, opt.k_dim)
+    L.HYPRE_COGMRESSetUnroll(g, opt.unroll)
+    L.HYPRE_COGMRESSetCGS(g, opt.cgs)
+    L.HYPRE_COGMRESSetMaxIter(g, opt.max_iter)
+    L.HYPRE_COGMRESSetTol(g, opt.tol)
+    L.HYPRE_COGMRESSetAbsoluteTol(g, 0.0)
+    L.HYPRE_COGMRESSetLogging(g, 3)            # ioutdat (test/ij.c:686); inert here
+    L.HYPRE_COGMRESSetPrintLevel(g, 3)
+    if amg is not None:
+        L.HYPRE_BoomerAMGSetTol(amg, 0.0)
+        L.HYPRE_BoomerAMGSetMaxIter(amg, opt.precon_cycles)
+        L.HYPRE_COGMRESSetMaxIter(g, opt.mg_max_iter)
+        L.HYPRE_COGMRESSetPrecond(g, C.cast(L.HYPRE_BoomerAMGSolve, C.c_void_p), None, amg)
+    else:
+        L.HYPRE_COGMRESSetPrecond(g, C.cast(L.HYPRE_ParCSRDiagScale, C.c_void_p), C.cast(L.HYPRE_ParCSRDiagScaleSetup, C.c_void_p), None)
+    L.HYPRE_ParCSRCOGMRESSetup(g, A, b, x)
+    L.HYPRE_ParCSRCOGMRESSolve(g, A, b, x)
+    its, rel = C.c_int(), C.c_double()
+    L.HYPRE_COGMRESGetNumIterations(g, C.byref(its))
+    L.HYPRE_COGMRESGetFinalRelativeResidualNorm(g, C.byref(rel))
+    L.HYPRE_ParCSRCOGMRESDestroy(g)
     return its.value, rel.value
 
 

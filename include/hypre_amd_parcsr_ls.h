@@ -491,6 +491,34 @@ HYPRE_Int HYPRE_GMRESGetNumIterations(HYPRE_Solver solver, HYPRE_Int *num_iterat
 HYPRE_Int HYPRE_GMRESGetFinalRelativeResidualNorm(HYPRE_Solver solver, HYPRE_Real *norm);
 HYPRE_Int HYPRE_GMRESGetConverged(HYPRE_Solver solver, HYPRE_Int *converged);
 
+/* ---- COGMRES: restarted GMRES whose Gram-Schmidt step is batched (`ij -solver 16 | 17`) ----
+ * krylov/cogmres.c:274-900, krylov/HYPRE_cogmres.c, parcsr_ls/HYPRE_parcsr_cogmres.c; defaults of hypre_COGMRESCreate
+ * (cogmres.c:85-111): k_dim 5, cgs 1, unroll 0, tol 1e-6, max_iter 1000.  Step i of a restart cycle orthogonalises with
+ * one hypre_ParVectorMassInnerProd and one hypre_ParVectorMassAxpy over the i basis vectors (classical Gram-Schmidt,
+ * cgs 1), or with hypre_ParVectorMassDotpTwo and the reorthogonalising correction of cogmres.c:550-566 (cgs 2): two
+ * read-backs a step instead of i + 1.  SetUnroll is kept for the reference's callers and changes nothing (see
+ * hypre_SeqVectorMassInnerProd).  SetKDim must precede Setup; the relative-change and convergence-factor exits are not
+ * carried, as for GMRES. */
+HYPRE_Int HYPRE_ParCSRCOGMRESCreate(MPI_Comm comm, HYPRE_Solver *solver);
+HYPRE_Int HYPRE_ParCSRCOGMRESDestroy(HYPRE_Solver solver);
+HYPRE_Int HYPRE_COGMRESSetKDim(HYPRE_Solver solver, HYPRE_Int k_dim);
+HYPRE_Int HYPRE_COGMRESSetUnroll(HYPRE_Solver solver, HYPRE_Int unroll);
+HYPRE_Int HYPRE_COGMRESSetCGS(HYPRE_Solver solver, HYPRE_Int cgs);
+HYPRE_Int HYPRE_COGMRESSetTol(HYPRE_Solver solver, HYPRE_Real tol);
+HYPRE_Int HYPRE_COGMRESSetAbsoluteTol(HYPRE_Solver solver, HYPRE_Real a_tol);
+HYPRE_Int HYPRE_COGMRESSetMinIter(HYPRE_Solver solver, HYPRE_Int min_iter);
+HYPRE_Int HYPRE_COGMRESSetMaxIter(HYPRE_Solver solver, HYPRE_Int max_iter);
+HYPRE_Int HYPRE_COGMRESSetSkipRealResidualCheck(HYPRE_Solver solver, HYPRE_Int skip_real_r_check);
+HYPRE_Int HYPRE_COGMRESSetLogging(HYPRE_Solver solver, HYPRE_Int logging);         /* accepted, inert */
+HYPRE_Int HYPRE_COGMRESSetPrintLevel(HYPRE_Solver solver, HYPRE_Int level);        /* accepted, inert */
+HYPRE_Int HYPRE_COGMRESSetPrecond(HYPRE_Solver solver, HYPRE_PtrToSolverFcn precond,
+                                  HYPRE_PtrToSolverFcn precond_setup, HYPRE_Solver precond_solver);
+HYPRE_Int HYPRE_ParCSRCOGMRESSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_ParCSRCOGMRESSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_COGMRESGetNumIterations(HYPRE_Solver solver, HYPRE_Int *num_iterations);
+HYPRE_Int HYPRE_COGMRESGetFinalRelativeResidualNorm(HYPRE_Solver solver, HYPRE_Real *norm);
+HYPRE_Int HYPRE_COGMRESGetConverged(HYPRE_Solver solver, HYPRE_Int *converged);
+
 #ifdef __cplusplus
 }
 #endif

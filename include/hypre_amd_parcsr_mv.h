@@ -243,6 +243,12 @@ HYPRE_Int  hypre_ParVectorAxpy(HYPRE_Complex alpha, hypre_ParVector *x, hypre_Pa
 HYPRE_Int  hypre_ParVectorAxpyz(HYPRE_Complex alpha, hypre_ParVector *x, HYPRE_Complex beta,
                                 hypre_ParVector *y, hypre_ParVector *z);
 HYPRE_Real hypre_ParVectorInnerProd(hypre_ParVector *x, hypre_ParVector *y);
+/* batched forms (parcsr_mv/par_vector_batched.c:21-140): the local kernels of hypre_SeqVectorMass*, then one reduction
+ * over the ranks of all k (MassDotpTwo: 2 k) sums; `unroll` is accepted and ignored */
+HYPRE_Int  hypre_ParVectorMassInnerProd(hypre_ParVector *x, hypre_ParVector **y, HYPRE_Int k, HYPRE_Int unroll, HYPRE_Real *result);
+HYPRE_Int  hypre_ParVectorMassDotpTwo(hypre_ParVector *x, hypre_ParVector *y, hypre_ParVector **z, HYPRE_Int k, HYPRE_Int unroll,
+                                      HYPRE_Real *result_x, HYPRE_Real *result_y);
+HYPRE_Int  hypre_ParVectorMassAxpy(HYPRE_Complex *alpha, hypre_ParVector **x, hypre_ParVector *y, HYPRE_Int k, HYPRE_Int unroll);
 HYPRE_Int  hypre_ParVectorElmdivpy(hypre_ParVector *x, hypre_ParVector *b, hypre_ParVector *y);
 HYPRE_Int  hypre_ParVectorElmdivpyMarked(hypre_ParVector *x, hypre_ParVector *b, hypre_ParVector *y,
                                          HYPRE_Int *marker, HYPRE_Int marker_val);

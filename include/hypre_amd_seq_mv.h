@@ -246,6 +246,15 @@ HYPRE_Int hypre_SeqVectorAxpy(HYPRE_Complex alpha, hypre_Vector *x, hypre_Vector
 HYPRE_Int hypre_SeqVectorAxpyz(HYPRE_Complex alpha, hypre_Vector *x, HYPRE_Complex beta,
                                hypre_Vector *y, hypre_Vector *z);
 HYPRE_Real hypre_SeqVectorInnerProd(hypre_Vector *x, hypre_Vector *y);
+/* Batched forms (seq_mv/vector_batched.c), device operands only: result[j] = <x, y[j]>; result_x[j] = <x, z[j]> and
+ * result_y[j] = <y, z[j]>; y += alpha[0] x[0] + ... + alpha[k-1] x[k-1], the terms applied in that order.  Every vector
+ * is read once per chunk of 8, the sums come back to the host arrays in one copy, and each result has the bits of the
+ * one-at-a-time call (hypre_SeqVectorInnerProd / k calls of hypre_SeqVectorAxpy).  k = 0 does nothing.  `unroll` is
+ * accepted and ignored: it selects host loop unrollings in the reference; the device kernels have their own blocking. */
+HYPRE_Int hypre_SeqVectorMassInnerProd(hypre_Vector *x, hypre_Vector **y, HYPRE_Int k, HYPRE_Int unroll, HYPRE_Real *result);
+HYPRE_Int hypre_SeqVectorMassDotpTwo(hypre_Vector *x, hypre_Vector *y, hypre_Vector **z, HYPRE_Int k, HYPRE_Int unroll,
+                                     HYPRE_Real *result_x, HYPRE_Real *result_y);
+HYPRE_Int hypre_SeqVectorMassAxpy(HYPRE_Complex *alpha, hypre_Vector **x, hypre_Vector *y, HYPRE_Int k, HYPRE_Int unroll);
 HYPRE_Int hypre_SeqVectorElmdivpy(hypre_Vector *x, hypre_Vector *b, hypre_Vector *y);
 HYPRE_Int hypre_SeqVectorElmdivpyMarked(hypre_Vector *x, hypre_Vector *b, hypre_Vector *y,
                                         HYPRE_Int *marker, HYPRE_Int marker_val);
