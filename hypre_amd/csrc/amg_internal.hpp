@@ -231,6 +231,6 @@ void launch_cheby_step(const double *r, const double *v, const double *ds, const
 void launch_jacobi_update(const double *u_in, const double *r, const double *d, const int *marker, int mval,
                           double *u_out, size_t n, hipStream_t s);
 void launch_diag_first(const int *Ai, const double *Aa, double *d, int n, hipStream_t s);
-void launch_coarse_solve(const double *lu, double *x, int n, hipStream_t s);
+void launch_coarse_solve(const double *lu, double *x, int n, hipStream_t s, int form = 0);
 
 }  // namespace hamd

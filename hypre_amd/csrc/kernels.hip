@@ -396,13 +396,16 @@ __global__ void diag_first_kernel(const int *__restrict__ Ai, const double *__re
 // Coarsest level (<= a few dozen unknowns): forward elimination / back
 // substitution with the factors of the reference's pivot-free elimination
 // (utilities/gselim.h), one lane, operations in the reference's order and
-// without fused multiply-adds so the result matches the host loop bit for bit.
+// without fused multiply-adds so the result matches the host loop bit for bit
+// (contraction switched off around plain operators: the __dmul_rn / __dsub_rn of
+// the HIP headers inline as a product and a difference the compiler fuses again).
 // Systems of at most 32 unknowns: the factors staged in LDS, lane j of the wave holds x[j]; step k of the elimination
 // updates every j > k at once (x[k] from lane k), the back substitution every j < k — each x[j] sees the operations of the
 // one-lane loop below in its order, so the bits are the same; 2 n steps of an LDS read instead of n^2 dependent trips to
 // memory (16 us -> 3 us for the 8 unknowns of the benchmark hierarchy).
 __global__ __launch_bounds__(64) void coarse_solve_wave_kernel(const double *__restrict__ lu_g, double *__restrict__ xg, int n)
 {
+#pragma clang fp contract(off)
    __shared__ double lu[32 * 32];
    const int j = threadIdx.x;
    for (int i = j; i < n * n; i += 64) { lu[i] = lu_g[i]; }
@@ -417,7 +420,7 @@ __global__ __launch_bounds__(64) void coarse_solve_wave_kernel(const double *__r
          if (lu[k * n + k] != 0.0 && j > k && j < n)
          {
             const double factor = lu[j * n + k];
-            if (factor != 0.0) { x = __dsub_rn(x, __dmul_rn(factor, xk)); }
+            if (factor != 0.0) { x = x - factor * xk; }
          }
       }
       for (int k = n - 1; k > 0; --k)
@@ -428,7 +431,7 @@ __global__ __launch_bounds__(64) void coarse_solve_wave_kernel(const double *__r
          if (piv != 0.0 && j < k)
          {
             const double c = lu[j * n + k];
-            if (c != 0.0) { x = __dsub_rn(x, __dmul_rn(xk, c)); }
+            if (c != 0.0) { x = x - xk * c; }
          }
       }
       if (j == 0 && lu[0] != 0.0) { x = x / lu[0]; }
@@ -438,6 +441,7 @@ __global__ __launch_bounds__(64) void coarse_solve_wave_kernel(const double *__r
 
 __global__ void coarse_solve_kernel(const double *__restrict__ lu, double *__restrict__ x, int n)
 {
+#pragma clang fp contract(off)
    if (threadIdx.x != 0 || blockIdx.x != 0) { return; }
    if (n == 1) { if (lu[0] != 0.0) { x[0] = x[0] / lu[0]; } return; }
    for (int k = 0; k < n - 1; k++)
@@ -447,7 +451,7 @@ __global__ void coarse_solve_kernel(const double *__restrict__ lu, double *__res
          for (int j = k + 1; j < n; j++)
          {
             const double factor = lu[j * n + k];        // multiplier stored below the diagonal
-            if (factor != 0.0) { x[j] = __dsub_rn(x[j], __dmul_rn(factor, x[k])); }
+            if (factor != 0.0) { x[j] = x[j] - factor * x[k]; }
          }
       }
    }
@@ -458,7 +462,7 @@ __global__ void coarse_solve_kernel(const double *__restrict__ lu, double *__res
          x[k] = x[k] / lu[k * n + k];
          for (int j = 0; j < k; j++)
          {
-            if (lu[j * n + k] != 0.0) { x[j] = __dsub_rn(x[j], __dmul_rn(x[k], lu[j * n + k])); }
+            if (lu[j * n + k] != 0.0) { x[j] = x[j] - x[k] * lu[j * n + k]; }
          }
       }
    }
@@ -556,10 +560,11 @@ void launch_jacobi_update(const double *u_in, const double *r, const double *d, 
 { account_bytes((32.0 + (marker ? 4.0 : 0.0)) * n); if (n) hipLaunchKernelGGL(jacobi_update_kernel, dim3(lin_grid(n)), dim3(256), 0, s, u_in, r, d, marker, mval, u_out, n); }
 void launch_diag_first(const int *Ai, const double *Aa, double *d, int n, hipStream_t s)
 { account_bytes(20.0 * n); if (n > 0) hipLaunchKernelGGL(diag_first_kernel, dim3((n + 255) / 256), dim3(256), 0, s, Ai, Aa, d, n); }
-void launch_coarse_solve(const double *lu, double *x, int n, hipStream_t s)
+// form 0: one wave for at most 32 unknowns, one lane above; 1 (tests): the one-lane kernel whatever n is
+void launch_coarse_solve(const double *lu, double *x, int n, hipStream_t s, int form)
 {
    if (n <= 0) { return; }
-   if (n <= 32) { hipLaunchKernelGGL(coarse_solve_wave_kernel, dim3(1), dim3(64), 0, s, lu, x, n); }
+   if (n <= 32 && form == 0) { hipLaunchKernelGGL(coarse_solve_wave_kernel, dim3(1), dim3(64), 0, s, lu, x, n); }
    else { hipLaunchKernelGGL(coarse_solve_kernel, dim3(1), dim3(64), 0, s, lu, x, n); }
 }
 // A (nrows x ncols, device) -> Ti[ncols + 1], tj[nnz], ta[nnz] (device, allocated by the caller); Aa / ta may be null

@@ -406,13 +406,10 @@ HYPRE_Int hypre_BoomerAMGRelax_FCFJacobi(hypre_ParCSRMatrix *A, hypre_ParVector 
 // ===========================================================================
 // Factor the dense operator once with the reference's elimination order; the
 // device kernel then replays the right-hand-side operations of hypre_gselim.
-static void ensure_coarse_factors(hypre_ParAMGData *d)
+// M (n x n, row-major) -> its factors in place: the multipliers below the diagonal (zeros below a zero pivot, whose step
+// the elimination skips: the kernels then test the pivot alone), the eliminated rows on and above it
+static void coarse_factors_in_place(std::vector<double> &M, int n)
 {
-   AmgPrivate *pv = (AmgPrivate *) d->amd_private;
-   if (pv->d_coarse_lu || !d->A_mat) { return; }
-   hypre_ParCSRMatrix *A = d->A_array[d->num_levels - 1];
-   const int n = (int) A->global_num_rows;
-   std::vector<double> M(d->A_mat, d->A_mat + (size_t) n * n);
    for (int k = 0; k < n - 1; k++)
    {
       if (M[(size_t) k * n + k] != 0.0)
@@ -433,6 +430,16 @@ static void ensure_coarse_factors(hypre_ParAMGData *d)
          for (int j = k + 1; j < n; j++) { M[(size_t) j * n + k] = 0.0; }
       }
    }
+}
+
+static void ensure_coarse_factors(hypre_ParAMGData *d)
+{
+   AmgPrivate *pv = (AmgPrivate *) d->amd_private;
+   if (pv->d_coarse_lu || !d->A_mat) { return; }
+   hypre_ParCSRMatrix *A = d->A_array[d->num_levels - 1];
+   const int n = (int) A->global_num_rows;
+   std::vector<double> M(d->A_mat, d->A_mat + (size_t) n * n);
+   coarse_factors_in_place(M, n);
    pv->coarse_n = n;
    pv->coarse_first_row = (int) A->first_row_index;
    pv->d_coarse_lu = hypre_TAlloc(double, (size_t) std::max(n * n, 1), HYPRE_MEMORY_DEVICE);
@@ -470,6 +477,26 @@ HYPRE_Int hypre_GaussElimSolve(hypre_ParAMGData *d, HYPRE_Int level, HYPRE_Int r
       launch_coarse_solve(pv->d_coarse_lu, pv->d_coarse_rhs, n, s);
       if (nloc) { HIP_CHECK(hipMemcpyAsync(ud, pv->d_coarse_rhs + pv->coarse_first_row, sizeof(double) * (size_t) nloc, hipMemcpyDeviceToDevice, s)); }
    }
+   return hypre_error_flag;
+}
+
+// Test hook: the coarsest level's solve on its own.  a (n x n, row-major) and b are host arrays; the factors are the ones
+// ensure_coarse_factors makes, the kernel the one launch_coarse_solve picks (form 0) or the one-lane kernel (form 1).
+HYPRE_Int hypre_amd_CoarseSolveTest(const HYPRE_Real *a, HYPRE_Int n, const HYPRE_Real *b, HYPRE_Int form, HYPRE_Real *x)
+{
+   if (n < 1 || !a || !b || !x || form < 0 || form > 1) { hypre_error_in_arg(n < 1 ? 2 : 4); return hypre_error_flag; }
+   std::vector<double> M(a, a + (size_t) n * n);
+   coarse_factors_in_place(M, n);
+   hipStream_t s = stream();
+   double *d_lu = hypre_TAlloc(double, (size_t) n * n, HYPRE_MEMORY_DEVICE);
+   double *d_x = hypre_TAlloc(double, (size_t) n, HYPRE_MEMORY_DEVICE);
+   hypre_TMemcpy(d_lu, M.data(), double, (size_t) n * n, HYPRE_MEMORY_DEVICE, HYPRE_MEMORY_HOST);
+   hypre_TMemcpy(d_x, b, double, (size_t) n, HYPRE_MEMORY_DEVICE, HYPRE_MEMORY_HOST);
+   launch_coarse_solve(d_lu, d_x, n, s, form);
+   HIP_CHECK(hipStreamSynchronize(s));
+   hypre_TMemcpy(x, d_x, double, (size_t) n, HYPRE_MEMORY_HOST, HYPRE_MEMORY_DEVICE);
+   hypre_TFree(d_lu, HYPRE_MEMORY_DEVICE);
+   hypre_TFree(d_x, HYPRE_MEMORY_DEVICE);
    return hypre_error_flag;
 }
 

@@ -294,6 +294,7 @@ void small_tail_kernel(SmallTailArgs t)
       // back substitution every j < k — each x[j] sees the operations of the one-lane loop in its order (the same bits)
       if (tid < 64)
       {
+#pragma clang fp contract(off)      // (as in coarse_solve_wave_kernel: product and difference rounded separately)
          const int j = tid;
          double x = j < n ? xc[j] : 0.0;
          if (n == 1) { if (j == 0 && lu[0] != 0.0) { x = x / lu[0]; } }
@@ -305,7 +306,7 @@ void small_tail_kernel(SmallTailArgs t)
                if (lu[k * n + k] != 0.0 && j > k && j < n)
                {
                   const double factor = lu[j * n + k];
-                  if (factor != 0.0) { x = __dsub_rn(x, __dmul_rn(factor, xk)); }
+                  if (factor != 0.0) { x = x - factor * xk; }
                }
             }
             for (int k = n - 1; k > 0; --k)
@@ -316,7 +317,7 @@ void small_tail_kernel(SmallTailArgs t)
                if (piv != 0.0 && j < k)
                {
                   const double c = lu[j * n + k];
-                  if (c != 0.0) { x = __dsub_rn(x, __dmul_rn(xk, c)); }
+                  if (c != 0.0) { x = x - xk * c; }
                }
             }
             if (j == 0 && lu[0] != 0.0) { x = x / lu[0]; }

@@ -329,6 +329,12 @@ HYPRE_Int hypre_amd_SetSmallTail(HYPRE_Int on);
 HYPRE_Int hypre_amd_SetSmallTailForm(HYPRE_Int form);
 /* first level of the one-workgroup tail in the last cycle of this solver (-1: none, -2: no cycle has run) */
 HYPRE_Int hypre_amd_BoomerAMGGetSmallTailLevel(HYPRE_Solver solver);
+/* Test hook: the dense solve of the coarsest level on its own.  a (n x n, row-major) and b are host arrays and stay as they
+ * are; a is factored by the routine the cycle's coarse solve factors its operator with (the reference's pivot-free
+ * elimination, utilities/gselim.h), b goes to the device, one kernel substitutes, x (host, n entries) receives the
+ * result.  form 0: the kernel the cycle launches for n unknowns (one wave up to 32, one lane above); 1: the one-lane
+ * kernel whatever n is. */
+HYPRE_Int hypre_amd_CoarseSolveTest(const HYPRE_Real *a, HYPRE_Int n, const HYPRE_Real *b, HYPRE_Int form, HYPRE_Real *x);
 /* grid / operator complexity of the last setup */
 HYPRE_Int hypre_amd_BoomerAMGGetComplexities(HYPRE_Solver solver, HYPRE_Real *grid, HYPRE_Real *op);
 /* Multi-rank device hierarchies: levels with at most `rows` global rows are gathered onto every rank at

@@ -228,6 +228,9 @@ def run_case(case, L, B, ij, O, dist, comm, rank, world):
 
     b, x = ij.build_rhs_host(opt, A, rank=rank, allreduce=allsum)
     mine = dict(h=O.export_solver(s), b=b, x=x)
+    # this rank's rows of the coarsest level (its slice of the right-hand side the dense solve gathers)
+    Ac = C.cast(L.hypre_amd_BoomerAMGGetA(s, L.hypre_amd_BoomerAMGGetNumLevels(s) - 1), C.POINTER(B.ParCSRMatrix)).contents
+    mine.update(coarse_rows=int(Ac.diag.contents.num_rows))
     if device:
         # the product path: distributed solve on the GPU (two ranks may share one card in the
         # test; halo traffic goes through the callback communicator, staged over the host)
@@ -333,7 +336,7 @@ def run_case(case, L, B, ij, O, dist, comm, rank, world):
         else:
             bg = np.concatenate([p["b"] for p in parts])
         out = {"grid": g.value, "operator": o.value, "levels": amg.c.num_levels,
-               "sizes": [a.nrows for a in amg.A_levels]}
+               "sizes": [a.nrows for a in amg.A_levels], "coarse_local_rows": [p["coarse_rows"] for p in parts]}
         if opt.solver == 0:
             its, rel, conv, hist = amg.solve(bg, xg, tol=opt.tol, max_iter=opt.mg_max_iter)
             out.update(iterations=its, rel_resid=rel, conv_factor=(hist[-1] / hist[0]) ** (1.0 / max(its, 1)))

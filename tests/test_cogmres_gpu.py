@@ -94,6 +94,59 @@ def test_reported_residual_is_the_true_one(gpu_lib, cgs):
     lib.hypre_ParVectorDestroy(db); lib.hypre_ParVectorDestroy(dx); lib.hypre_ParCSRMatrixDestroy(A)
 
 
+_big = {}
+
+
+def _past_one_grid_pass(lib, oracle):
+    """104 x 101 x 101 7-point Laplacian: 1 060 904 rows, just above the 1 048 576 elements one pass of the BLAS-1 grids
+    covers, so every vector kernel of a Krylov solve takes a partial second trip (a dot product a partial third).  The
+    operator on the device, the oracle's copy of it and a right-hand side, made once for the two solvers below."""
+    if not _big:
+        from hypre_amd import binding as B, ij
+        opt = ij.IJOptions(n=(104, 101, 101), solver=2, tol=0.0, k_dim=5)
+        A = ij.build_matrix(opt)
+        Ao = oracle.par_from_handles([A])
+        lib.hypre_ParCSRMatrixMigrate(A, B.HYPRE_MEMORY_DEVICE)
+        B.check()
+        n = 104 * 101 * 101
+        assert Ao.nrows == n > 1048576
+        b = np.random.default_rng(17).uniform(-1.0, 1.0, n)
+        b.setflags(write=False)
+        _big.update(opt=opt, A=A, Ao=Ao, b=b, n=n)
+    return _big
+
+
+@pytest.mark.parametrize("solver", ["ds_pcg", "ds_cogmres"])
+def test_krylov_iterations_past_one_pass_of_the_vector_grids(gpu_lib, oracle, solver):
+    """Diagonally scaled PCG (pcg_update_kernel, pcg_direction_kernel, the dots) and diagonally scaled COGMRES (the batched
+    dots and updates) at tol 0 for 1, 2 and 3 iterations from zero: after each count the relative residual is the
+    oracle's after as many iterations of its PCG / GMRES (1e-6 relative, the bar of test_amg_gpu.py's Krylov tests; in exact
+    arithmetic COGMRES is GMRES, and three steps without a restart lose no orthogonality to speak of), and the iterate after
+    three is the oracle's to 1e-9 of its largest entry."""
+    from hypre_amd import binding as B, ij
+    lib = gpu_lib
+    h = _past_one_grid_pass(lib, oracle)
+    opt, A, n = h["opt"], h["A"], h["n"]
+    for k in (1, 2, 3):
+        opt.max_iter = k
+        X = np.zeros((n, 1))
+        if solver == "ds_pcg":
+            oits, orel, _ = oracle.pcg_ds_multi(h["Ao"], h["b"][:, None], X, tol=0.0, max_iter=k, two_norm=opt.two_norm)
+        else:
+            oits, orel, _ = oracle.gmres_ds_multi(h["Ao"], h["b"][:, None], X, tol=0.0, max_iter=k, k_dim=opt.k_dim)
+        db, dx = B.parvec_from_numpy(h["b"]), B.parvec_from_numpy(np.zeros(n))
+        its, rel = (ij.solve_ds_pcg if solver == "ds_pcg" else ij.solve_cogmres)(opt, A, db, dx)
+        lib.HYPRE_ClearError(256)                       # (tol 0: "not converged" is the expected end)
+        B.check()
+        x = B.parvec_to_numpy(dx)
+        lib.hypre_ParVectorDestroy(db); lib.hypre_ParVectorDestroy(dx)
+        xerr = float(np.max(np.abs(x - X[:, 0])) / np.max(np.abs(X[:, 0])))
+        print(solver, "iterations", its, oits, "relative residual", rel, orel, "difference", abs(rel - orel) / orel, "iterate", xerr)
+        assert its == oits == k
+        assert 0.0 < orel < 1.0 and abs(rel - orel) <= 1e-6 * orel
+    assert xerr <= 1e-9
+
+
 def test_solve_after_set_k_dim_needs_a_new_setup(gpu_lib):
     from hypre_amd import binding as B
     lib = gpu_lib

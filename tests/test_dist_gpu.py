@@ -114,7 +114,20 @@ BASELINE_CASES = {
                                     {"mixed": 1}),
     "c5_amg_mixed_2ranks_no_tail": (2, dict(n=[20, 20, 20], P=[1, 1, 2], problem="difconv", c=[1.0, 1.0, 0.001], a=[0.0, 0.0, 0.0],
                                             relax_type=18, coarsen_type=8), {"mixed": 1, "replicate": 0}),
+    # -coarse_th 40: the dense solve of the coarsest level on more than the default 9 unknowns, its right-hand side
+    # gathered from every rank's slice (zero-fill, own slice, all-reduce: hypre_GaussElimSolve).  Coarsest level and the
+    # ranks' slices with the host setup: 25 rows (15, 10; the one-wave kernel), 39 rows (14, 12, 13; the one-lane kernel)
+    # and 10 rows of which the middle rank owns a single one (5, 1, 4).
+    "coarse40_amg_2ranks_no_tail": (2, dict(n=[16, 15, 14], P=[2, 1, 1], relax_type=18, coarsen_type=8, coarse_threshold=40),
+                                    {"replicate": 0}),
+    "coarse40_amg_3ranks_no_tail": (3, dict(n=[18, 15, 21], P=[1, 1, 3], relax_type=18, coarsen_type=8, coarse_threshold=40),
+                                    {"replicate": 0}),
+    "coarse40_amg_3ranks_one_row_slice_no_tail": (3, dict(n=[21, 19, 18], P=[3, 1, 1], relax_type=18, coarsen_type=8,
+                                                          coarse_threshold=40), {"replicate": 0}),
 }
+# rows the coarsest level of the coarse40 cases must have (lower bound, upper bound, smallest slice of a rank)
+COARSE40_ROWS = {"coarse40_amg_2ranks_no_tail": (10, 32, 2), "coarse40_amg_3ranks_no_tail": (33, 40, 2),
+                 "coarse40_amg_3ranks_one_row_slice_no_tail": (10, 32, 1)}
 _baseline = {}
 
 
@@ -153,6 +166,11 @@ def test_baseline_multi_rank_configs_on_device(name):
     # level) for all three configurations: two-stage GS keeps the triangles of the ranks' diagonal blocks there,
     # mixed precision the fp32-rounded values
     assert (out["replicated_level"] == -1) == ("no_tail" in name)
+    if name in COARSE40_ROWS:
+        # every rank owns part of a coarsest level of the intended size
+        lo, hi, smallest = COARSE40_ROWS[name]
+        rows = out["coarse_local_rows"]
+        assert lo <= out["sizes"][-1] == sum(rows) <= hi and min(rows) >= 1 and (smallest > 1 or min(rows) == 1), (out["sizes"], rows)
 
 
 # The distributed SETUP on the device (par_amg_setup_dist.cpp, the device half: the single-rank kernels on the extended

@@ -2,7 +2,10 @@
 one-at-a-time calls they replace, bit for bit: every sum equals hypre_SeqVectorInnerProd of the same pair, the update
 equals k calls of hypre_SeqVectorAxpy in the order 0 .. k-1, `unroll` changes nothing and the inputs are left alone.
 Sizes: empty, one element (tail only), one pair, an odd length below one workgroup, more than one workgroup with a tail,
-and more than one pass of the 1024 x 256 x 2 grid of a dot product; k on both sides of the chunk of 8, and three chunks."""
+196 workgroups (100 003), and the two odd lengths that pass a grid once: 524 288 + 515 takes a partial second trip through
+the 1024 x 256 x 2 grid of a dot product, 1 048 576 + 515 through the 2048 x 256 x 2 grid of the update as well (and a
+whole second trip and a partial third of the dot's) — lanes that went round once and lanes that went round twice meet in
+one sum.  k on both sides of the chunk of 8, and three chunks."""
 import ctypes as C
 
 import numpy as np
@@ -10,21 +13,30 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-SIZES = (0, 1, 2, 255, 4097, 100003)
+SIZES = (0, 1, 2, 255, 4097, 100003, 524288 + 515, 1048576 + 515)
 COUNTS = (1, 2, 7, 8, 9, 17)
 KMAX = max(COUNTS)
+SHIFT = 1021              # the z_j of the two large sizes are windows of one seed block, this far apart
 
 _cache = {}
 
 
 def _vectors(n):
-    """host data of one size, drawn once: x, y, KMAX vectors z and KMAX coefficients (fixed seed per size)"""
+    """host data of one size, drawn once: x, y, KMAX vectors z and KMAX coefficients (fixed seed per size).  Above
+    200 000 elements the z_j are overlapping windows of one block of n + KMAX * SHIFT numbers instead of KMAX x n."""
     if n not in _cache:
         rng = np.random.default_rng(20260000 + n)
-        _cache[n] = dict(x=rng.standard_normal(n), y=rng.standard_normal(n), z=rng.standard_normal((KMAX, n)),
-                         alpha=rng.standard_normal(KMAX))
-        for v in _cache[n].values():
-            v.setflags(write=False)
+        x, y = rng.standard_normal(n), rng.standard_normal(n)
+        if n > 200000:
+            block = rng.standard_normal(n + KMAX * SHIFT)
+            block.setflags(write=False)
+            z = [block[j * SHIFT:j * SHIFT + n] for j in range(KMAX)]
+        else:
+            z = rng.standard_normal((KMAX, n))
+            z.setflags(write=False)
+        _cache[n] = dict(x=x, y=y, z=z, alpha=rng.standard_normal(KMAX))
+        for k in ("x", "y", "alpha"):
+            _cache[n][k].setflags(write=False)
     return _cache[n]
 
 

@@ -130,26 +130,93 @@ def test_host_operands_fail_loudly(gpu_lib):
         B.check()
 
 
-def test_blas1(gpu_lib, oracle):
+# 0 and 1 - 3: nothing, the odd tail alone, one pair, a pair and the tail; around one and two waves' worth of pairs; the size
+# the test always had; and the two odd lengths past ONE PASS of the grids: vec_grid stops at 2048 workgroups x 256 lanes x 2
+# doubles (second trip above 1 048 576 elements, as for the one-element-a-lane kernels of lin_grid with 4096 x 256), a dot
+# product at 1024 workgroups (above 524 288).  With + 515 the second trip is partial: some lanes go round twice, most once.
+BLAS1_SIZES = (0, 1, 2, 3, 511, 512, 513, 100003, 524288 + 515, 1048576 + 515)
+
+
+def _within_one_rounding(got, t1, t2, what):
+    """|got - (t1 + t2)| <= 2^-52 (|t1| + |t2|) element by element, the terms and their sum in numpy.longdouble: one
+    rounding of a fused multiply-add, or the two of a product and a sum"""
+    L = np.longdouble
+    err = np.abs(got.astype(L) - (t1 + t2))
+    bound = L(2.0) ** -52 * (np.abs(t1) + np.abs(t2))
+    worst = float(np.max(err / np.maximum(bound, L(1e-300)))) if got.size else 0.0
+    print(what, "n", got.size, "worst error / bound", worst)
+    assert np.all(err <= bound), (what, got.size, worst)
+
+
+@pytest.mark.parametrize("n", BLAS1_SIZES)
+def test_blas1(gpu_lib, oracle, n):
+    """Every BLAS-1 call on separately allocated vectors against numpy.longdouble: Set and Copy exact, the element-wise
+    results within one rounding of their two terms, the dot within 1e-12 of the sum of the products' magnitudes."""
+    import ctypes as C
     from hypre_amd import binding as B
-    n = 100003
+    lib = gpu_lib
+    L = np.longdouble
     x, y = rand_vector(n, 1), rand_vector(n, 2)
+    xl, yl = x.astype(L), y.astype(L)
     dx, dy = B.vec_from_numpy(x), B.vec_from_numpy(y)
     dot = gpu_lib.hypre_SeqVectorInnerProd(dx, dy)
     assert abs(dot - float(np.dot(x, y))) <= 1e-12 * float(np.dot(np.abs(x), np.abs(y)))
+    assert abs(L(dot) - np.sum(xl * yl)) <= L(1e-12) * np.sum(np.abs(xl * yl))
     gpu_lib.hypre_SeqVectorAxpy(0.3, dx, dy)
-    assert np.allclose(B.vec_to_numpy(dy), y + 0.3 * x, rtol=0, atol=1e-15)
+    y1 = B.vec_to_numpy(dy)
+    assert np.allclose(y1, y + 0.3 * x, rtol=0, atol=1e-15)
+    _within_one_rounding(y1, yl, L(0.3) * xl, "Axpy")
     gpu_lib.hypre_SeqVectorScale(-2.0, dy)
-    assert np.allclose(B.vec_to_numpy(dy), -2.0 * (y + 0.3 * x), rtol=0, atol=1e-15)
+    y2 = B.vec_to_numpy(dy)
+    assert np.allclose(y2, -2.0 * (y + 0.3 * x), rtol=0, atol=1e-15)
+    _within_one_rounding(y2, L(-2.0) * y1.astype(L), np.zeros(n, dtype=L), "Scale")
+    lib.hypre_SeqVectorScale(0.7, dy)                                   # (a factor whose products round)
+    y3 = B.vec_to_numpy(dy)
+    _within_one_rounding(y3, L(0.7) * y2.astype(L), np.zeros(n, dtype=L), "Scale")
+    dc = B.vec_from_numpy(y2)
+    gpu_lib.hypre_SeqVectorCopy(dc, dy)                                 # Copy(x, y): y = x, and dy is the old test's again
+    assert B.vec_to_numpy(dy).tobytes() == y2.tobytes() and B.vec_to_numpy(dc).tobytes() == y2.tobytes()
     dz = B.vec_from_numpy(np.zeros(n))
     gpu_lib.hypre_SeqVectorAxpyz(2.0, dx, -1.0, dy, dz)
-    assert np.allclose(B.vec_to_numpy(dz), 2.0 * x + 2.0 * (y + 0.3 * x), rtol=0, atol=1e-14)
+    z = B.vec_to_numpy(dz)
+    assert np.allclose(z, 2.0 * x + 2.0 * (y + 0.3 * x), rtol=0, atol=1e-14)
+    _within_one_rounding(z, L(2.0) * xl, L(-1.0) * y2.astype(L), "Axpyz")
+    lib.hypre_SeqVectorAxpyz(0.3, dx, 0.7, dy, dz)
+    _within_one_rounding(B.vec_to_numpy(dz), L(0.3) * xl, L(0.7) * y2.astype(L), "Axpyz")
     d = np.abs(rand_vector(n, 3)) + 0.5
     dd = B.vec_from_numpy(d)
     ybefore = B.vec_to_numpy(dy)
     gpu_lib.hypre_SeqVectorElmdivpy(dx, dd, dy)
-    assert np.allclose(B.vec_to_numpy(dy), ybefore + x / d, rtol=0, atol=1e-14)
+    y4 = B.vec_to_numpy(dy)
+    assert np.allclose(y4, ybefore + x / d, rtol=0, atol=1e-14)
+    _within_one_rounding(y4, ybefore.astype(L), xl / d.astype(L), "Elmdivpy")
     B.check()
+    # the same sum where a marker says 1 (about half of the rows); the other rows keep their bytes
+    marker = (np.random.default_rng(4).random(n) < 0.5).astype(np.int32)
+    dm = lib.hypre_MAlloc(max(marker.nbytes, 4), B.HYPRE_MEMORY_DEVICE)
+    if n:
+        lib.hypre_Memcpy(dm, marker.ctypes.data_as(C.c_void_p), marker.nbytes, B.HYPRE_MEMORY_DEVICE, B.HYPRE_MEMORY_HOST)
+    lib.hypre_SeqVectorElmdivpyMarked(dx, dd, dy, C.cast(dm, B.IntP), 1)
+    y5 = B.vec_to_numpy(dy)
+    B.check()
+    on = marker == 1
+    if n > 100:
+        assert 0.4 * n < np.count_nonzero(on) < 0.6 * n
+    assert y5[~on].tobytes() == y4[~on].tobytes()
+    _within_one_rounding(y5[on], y4[on].astype(L), (xl / d.astype(L))[on], "ElmdivpyMarked")
+    assert not on.any() or not np.array_equal(y5[on], y4[on])
+    # p += a p: the aliasing GMRES forms its restart residual with
+    lib.hypre_SeqVectorAxpy(-0.3, dy, dy)
+    _within_one_rounding(B.vec_to_numpy(dy), y5.astype(L), L(-0.3) * y5.astype(L), "Axpy(a, p, p)")
+    # Set: every element the value itself
+    lib.hypre_SeqVectorSetConstantValues(dz, 0.7)
+    assert B.vec_to_numpy(dz).tobytes() == np.full(n, 0.7).tobytes()
+    # the operands are what they were
+    assert B.vec_to_numpy(dx).tobytes() == x.tobytes() and B.vec_to_numpy(dd).tobytes() == d.tobytes()
+    B.check()
+    lib.hypre_Free(dm, B.HYPRE_MEMORY_DEVICE)
+    for v in (dx, dy, dz, dd, dc):
+        lib.hypre_SeqVectorDestroy(v)
 
 
 def _multivector(B, X, par=False):
