@@ -149,6 +149,10 @@ GsSchedule *get_schedule(hypre_CSRMatrix *A, int threads)
    return g;
 }
 
+// what the last sweep call did (hypre_amd_GsSweepStats): host counters, for tests that must know which kernel they reached
+struct GsStats { int lanes = 0, threads = 0, run_launches = 0, level_launches = 0; };
+GsStats g_stats;
+
 // Levels that fit one pass of a workgroup (1024 / lanes rows) share one single-workgroup launch whose
 // steps are pipelined (gs_kernels.hip: ~2 us per level); a larger level gets a grid of its own (~5 us).
 // Measured on the 64^3 7-pt hierarchy: 1 pass 16.7 ms per V(1,1) cycle, 2: 17.0, 4: 18.8, 8: 36.5.
@@ -167,11 +171,13 @@ void run_direction(const GsDirection &D, int lanes, GsArgs a, hipStream_t s)
          int end = lev + 1;
          while (end < D.nlev && end - lev < MAX_RUN && D.lev_start[(size_t) end + 1] - D.lev_start[(size_t) end] <= small) { end++; }
          launch_gs_run(a, lanes, D.d_lev_start, lev, end, s);
+         g_stats.run_launches++;
          lev = end;
       }
       else
       {
          launch_gs_level(a, lanes, D.lev_start[(size_t) lev], cnt, s);
+         g_stats.level_launches++;
          lev++;
       }
    }
@@ -241,6 +247,7 @@ extern "C" HYPRE_Int hypre_BoomerAMGRelaxHybridGaussSeidelDevice(hypre_ParCSRMat
    // the row sum unless weights are in play (relax 8/13/14 call the core with Skip_diag = !non_scale)
    a.skip_diag = l1_norms ? (a.non_scale ? 0 : 1) : 1;
    a.n = n; a.threads = g->threads;
+   g_stats = GsStats{g->lanes, g->threads, 0, 0};
 
    // Vtemp: state at the start of the call (off-block and SOR terms read it)
    launch_copy(vt, ud, (size_t) n, s);
@@ -257,5 +264,20 @@ extern "C" HYPRE_Int hypre_BoomerAMGRelaxHybridGaussSeidelDevice(hypre_ParCSRMat
    u->all_zeros = 0;               // the sweep has written u (relax 89 calls this twice: the second sweep must fetch ghosts)
    handle().sync_compute = saved;
    maybe_sync();
+   return hypre_error_flag;
+}
+
+extern "C" HYPRE_Int hypre_amd_RelaxSetNumThreads(HYPRE_Int n)
+{
+   handle().gs_threads = std::max(1, (int) n);
+   return hypre_error_flag;
+}
+
+extern "C" HYPRE_Int hypre_amd_GsSweepStats(HYPRE_Int *lanes, HYPRE_Int *threads, HYPRE_Int *run_launches, HYPRE_Int *level_launches)
+{
+   if (lanes) { *lanes = g_stats.lanes; }
+   if (threads) { *threads = g_stats.threads; }
+   if (run_launches) { *run_launches = g_stats.run_launches; }
+   if (level_launches) { *level_launches = g_stats.level_launches; }
    return hypre_error_flag;
 }

@@ -428,6 +428,13 @@ HYPRE_Int hypre_BoomerAMGRelaxHybridGaussSeidelDevice(hypre_ParCSRMatrix *A, hyp
                                                       HYPRE_Real *l1_norms, hypre_ParVector *u,
                                                       hypre_ParVector *Vtemp, hypre_ParVector *Ztemp,
                                                       HYPRE_Int GS_order, HYPRE_Int Symm);
+/* Emulated OpenMP threads (blocks of hypre_partition1D) of the hybrid sweeps for DIRECT relaxation calls; values below 1
+ * become 1.  A solve sets its own count (hypre_amd_BoomerAMGSetNumThreads) for its duration and puts this one back. */
+HYPRE_Int hypre_amd_RelaxSetNumThreads(HYPRE_Int n);
+/* What the last hypre_BoomerAMGRelaxHybridGaussSeidelDevice call used and did: lanes per row (4, 8, 16, 32), blocks of the
+ * schedule (the thread count clamped to the row count), and the launches of the one-workgroup run kernel and of the
+ * one-grid-per-level kernel, summed over both directions of a symmetric sweep.  Host counters; any pointer may be NULL. */
+HYPRE_Int hypre_amd_GsSweepStats(HYPRE_Int *lanes, HYPRE_Int *threads, HYPRE_Int *run_launches, HYPRE_Int *level_launches);
 /* Multicolour Gauss-Seidel, relax types 21 (colours ascending) and 22 (descending) of hypre_BoomerAMGRelax.  No
  * counterpart in the reference (parcsr_ls/par_relax*.c knows no colouring): it is the hybrid Gauss-Seidel sweep of
  * par_relax.c:691-945 (Jacobi across ranks, Gauss-Seidel inside a rank) on the colour-permuted local ordering, which

@@ -164,6 +164,7 @@ def test_hybrid_gauss_seidel_sweep_is_the_sequential_sweep(gpu_lib, oracle, rela
     dict(relax_type=3, coarsen_type=10, relax_order=1),
     dict(relax_type=8, coarsen_type=8),
     dict(relax_type=13, coarsen_type=10, num_threads=3),
+    dict(relax_type=6, coarsen_type=8, num_threads=4),
     dict(relax_type=89, coarsen_type=8, problem="27pt"),
     dict(relax_type=-1, coarsen_type=10),
     dict(relax_type=16, coarsen_type=8),
