@@ -14,6 +14,7 @@
 // row folded in entry order (one lane, values read lane by lane).  The map is an open-addressing table in LDS whose slots
 // carry the row's tag.
 #include "internal.hpp"
+#include "extpi_map.hpp"
 #include <algorithm>
 
 #pragma clang fp contract(off)
@@ -21,38 +22,6 @@
 namespace hamd {
 
 namespace {
-
-constexpr int ABSENT = -1, STRONG_F = -2;
-
-__device__ __forceinline__ int map_get(const unsigned long long *tab, const int *val, int mask, unsigned tag, int key)
-{
-   unsigned h = ((unsigned) key * 2654435761u) >> 7;
-   while (true)
-   {
-      const unsigned long long e = tab[h & mask];
-      if ((unsigned) (e >> 32) != tag) { return ABSENT; }
-      if ((int) (unsigned) e == key) { return val[h & mask]; }
-      h++;
-   }
-}
-
-// insert a key known to be absent, or overwrite the value of a present one (lanes work on distinct keys)
-__device__ __forceinline__ void map_set(unsigned long long *tab, int *val, int mask, unsigned tag, int key, int v)
-{
-   unsigned h = ((unsigned) key * 2654435761u) >> 7;
-   const unsigned long long mine = ((unsigned long long) tag << 32) | (unsigned) key;
-   while (true)
-   {
-      const unsigned long long e = tab[h & mask];
-      if ((unsigned) (e >> 32) != tag)
-      {
-         if (atomicCAS(&tab[h & mask], e, mine) == e) { val[h & mask] = v; return; }
-         continue;
-      }
-      if ((int) (unsigned) e == key) { val[h & mask] = v; return; }
-      h++;
-   }
-}
 
 __device__ __forceinline__ int below(unsigned long long ballot, int lane) { return __popcll(ballot & ((1ull << lane) - 1ull)); }
 
@@ -161,6 +130,9 @@ void extpi_rows_kernel(int n, const int *__restrict__ Ai, const int *__restrict_
          // in entry order — runs over what sits in registers and LDS, in the host's order.
          // ---- the interpolatory set, in first-touch order
          const int s0 = Si[i], s1 = Si[i + 1];
+         // every strong F neighbour becomes an entry of the map, beside the set's (at most capR): the probes end only
+         // while a slot stays free (extpi_map.hpp), so a row that could fill the map is left to the next rung
+         bad = !extpi_map_has_room(s1 - s0, capR, capM);
          for (int sb = s0; sb < s1 && !bad; sb += 64)
          {
             const int jj = sb + lane;
@@ -412,7 +384,12 @@ __global__ void compact_rows_kernel(int n, int stride, const int *__restrict__ P
    if (i < n && k < Pi[i + 1] - Pi[i]) { Pj[Pi[i] + k] = sj[t]; Pa[Pi[i] + k] = sa[t]; }
 }
 
-static int pow2_ge(int v) { int p = 16; while (p < v) { p <<= 1; } return p; }
+// How the last device_extpi call went (hypre_amd_GetDeviceInterpPath) and the test switch for the number of waves
+// (hypre_amd_SetDeviceInterpWaves; 0: one per row up to 32 a CU): tests walk the ladder and make one wave own many rows
+enum { INTERP_NOT_DECLINED = 0, INTERP_THRESHOLD_ONLY = 1, INTERP_TABLES_EXHAUSTED = 2, INTERP_ALLOCATION = 3 };
+struct InterpPath { int first_rung, rung, attempts, count_then_write, declined; };
+static InterpPath g_interp_path = {-1, -1, 0, 0, INTERP_NOT_DECLINED};
+static int g_interp_waves = 0;
 
 void device_split_strided(int n, int stride, int *len, int *nd, const int *sj, const double *sa, int split,
                           int **Di_out, int **Dj_out, double **Da_out, int *dnnz, int **Oi_out, int **Oj_out, double **Oa_out, int *onnz,
@@ -427,8 +404,11 @@ bool device_extpi(int n, const int *Ai, const int *Aj, const double *Aa, const i
                   const int *f2c, double trunc_tol, int max_elmts, int first_rung, int **Pi_out, int **Pj_out, double **Pa_out,
                   int *nnz_out, hipStream_t s, int split, int **Oi_out, int **Oj_out, double **Oa_out, int *onnz_out)
 {
-   if (max_elmts <= 0 && trunc_tol > 0.0) { return false; }     // lengths would depend on the weights: not built here
    const bool dist = split >= 0;
+   const bool fixed = max_elmts > 0 || dist;
+   InterpPath &path = g_interp_path;
+   path = {std::min(std::max(first_rung, 0), EXTPI_RUNGS - 1), -1, 0, fixed ? 0 : 1, INTERP_NOT_DECLINED};
+   if (max_elmts <= 0 && trunc_tol > 0.0) { path.declined = INTERP_THRESHOLD_ONLY; return false; }     // lengths would depend on the weights: not built here
    if (dist && n <= 0)
    {
       int *Pi = nullptr, *Oi = nullptr;
@@ -448,10 +428,9 @@ bool device_extpi(int n, const int *Ai, const int *Aj, const double *Aa, const i
    HIP_CHECK(hipMalloc((void **) &d_flag, sizeof(int)));
    HIP_CHECK(hipMalloc((void **) &rowlen, sizeof(int) * ((size_t) n + 1)));
    if (dist) { HIP_CHECK(hipMalloc((void **) &rowlen_d, sizeof(int) * ((size_t) n + 1))); }
-   const int waves = std::min(n, handle().num_cus * 32);
-   // rows have at most max_elmts entries: one pass into strided storage (a distributed level always works that way, with
-   // room for a whole table's worth of entries per row when the rows are not cut)
-   const bool fixed = max_elmts > 0 || dist;
+   const int waves = std::min(n, g_interp_waves > 0 ? g_interp_waves : handle().num_cus * 32);
+   // fixed: rows have at most max_elmts entries: one pass into strided storage (a distributed level always works that
+   // way, with room for a whole table's worth of entries per row when the rows are not cut)
    int *sj = nullptr;
    double *sa = nullptr;
    int stride = max_elmts;
@@ -464,34 +443,35 @@ bool device_extpi(int n, const int *Ai, const int *Aj, const double *Aa, const i
       if (hipMalloc((void **) &sa, sizeof(double) * (size_t) n * (size_t) st) != hipSuccess) { sa = nullptr; (void) hipGetLastError(); return false; }
       return true;
    };
-   auto give_up = [&]()
+   auto give_up = [&](int why)
    {
+      path.declined = why; path.rung = -1;
       HIP_CHECK(hipFree(d_flag)); HIP_CHECK(hipFree(rowlen));
       if (rowlen_d) { HIP_CHECK(hipFree(rowlen_d)); }
       if (sj) { HIP_CHECK(hipFree(sj)); }
       if (sa) { HIP_CHECK(hipFree(sa)); }
       return false;
    };
-   if (fixed && max_elmts > 0 && !alloc_strided(max_elmts)) { return give_up(); }
+   if (fixed && max_elmts > 0 && !alloc_strided(max_elmts)) { return give_up(INTERP_ALLOCATION); }
    // Tables sized by what rows of such operators need, smallest first: the kernel lives on the number of rows in flight
    // (tables for 64 entries: 23 waves a CU; for 256: 7), and the interpolatory sets of the benchmark hierarchy stay below
    // 64 points on every level although the rows of A grow to 134 entries.  An overflowing row sends everyone to the next
    // rung (the waves leave the lost attempt at their next row).
-   const int room[4] = {64, 128, 256, 1024};
    int capR = 0, capM = 0, h_flag = 1;
    const bool verbose = getenv("HYPRE_AMD_SETUP_TIMING") != nullptr;
    const int maxA = verbose ? device_max_row_nnz(Ai, n, s) : 0;
-   for (int attempt = std::min(std::max(first_rung, 0), 3); attempt < 4 && h_flag; attempt++)
+   for (int attempt = path.first_rung; attempt < EXTPI_RUNGS && h_flag; attempt++)
    {
-      capR = room[attempt];
+      capR = EXTPI_ROOM[attempt];
       if (verbose) { fprintf(stderr, "   interpolation: %d rows, longest row of A %d, tables for %d entries\n", n, maxA, capR); }
       // the map also holds the strong F neighbours of the row
-      capM = pow2_ge(4 * capR);
+      capM = extpi_map_slots(capR);
       if (lds(capM, capR) > budget) { break; }
+      path.attempts++; path.rung = attempt;
       HIP_CHECK(hipMemsetAsync(d_flag, 0, sizeof(int), s));
       if (fixed)
       {
-         if (max_elmts <= 0 && !alloc_strided(capR)) { return give_up(); }
+         if (max_elmts <= 0 && !alloc_strided(capR)) { return give_up(INTERP_ALLOCATION); }
          hipLaunchKernelGGL((extpi_rows_kernel<2>), dim3(waves), dim3(64), lds(capM, capR), s, n, Ai, Aj, Aa, Si, Sj, CF, f2c, trunc_tol,
                             max_elmts, capM, capR, (const int *) nullptr, stride, rowlen, sj, sa, d_flag, split, rowlen_d);
       }
@@ -503,11 +483,13 @@ bool device_extpi(int n, const int *Ai, const int *Aj, const double *Aa, const i
       HIP_CHECK(hipMemcpyAsync(&h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));
    }
-   if (h_flag) { return give_up(); }
+   if (h_flag) { return give_up(INTERP_TABLES_EXHAUSTED); }
    if (dist)
    {
       device_split_strided(n, stride, rowlen, rowlen_d, sj, sa, split, Pi_out, Pj_out, Pa_out, nnz_out, Oi_out, Oj_out, Oa_out, onnz_out, s);
-      (void) give_up();       // frees the work arrays
+      const int rung = path.rung;
+      (void) give_up(INTERP_NOT_DECLINED);       // frees the work arrays
+      path.rung = rung;
       return true;
    }
    // row pointers: exclusive scan of the lengths, in place
@@ -515,7 +497,7 @@ bool device_extpi(int n, const int *Ai, const int *Aj, const double *Aa, const i
    int nnz = 0;
    HIP_CHECK(hipMemcpyAsync(&nnz, rowlen + n, sizeof(int), hipMemcpyDeviceToHost, s));
    HIP_CHECK(hipStreamSynchronize(s));
-   if (nnz < 0) { return give_up(); }
+   if (nnz < 0) { return give_up(INTERP_ALLOCATION); }
    int *Pi = rowlen, *Pj = nullptr;
    double *Pa = nullptr;
    HIP_CHECK(hipMalloc((void **) &Pj, sizeof(int) * (size_t) std::max(nnz, 1)));
@@ -544,3 +526,16 @@ bool device_extpi(int n, const int *Ai, const int *Aj, const double *Aa, const i
 void preload_interp_kernels() { hipFuncAttributes at; (void) hipFuncGetAttributes(&at, (const void *) extpi_rows_kernel<2>); (void) hipGetLastError(); }
 
 }  // namespace hamd
+
+extern "C" HYPRE_Int hypre_amd_SetDeviceInterpWaves(HYPRE_Int waves)
+{
+   hamd::g_interp_waves = waves > 0 ? waves : 0;
+   return 0;
+}
+
+extern "C" HYPRE_Int hypre_amd_GetDeviceInterpPath(HYPRE_Int *out)
+{
+   const hamd::InterpPath &p = hamd::g_interp_path;
+   if (out) { out[0] = p.first_rung; out[1] = p.rung; out[2] = p.attempts; out[3] = p.count_then_write; out[4] = p.declined; }
+   return 0;
+}

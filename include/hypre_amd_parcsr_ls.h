@@ -269,6 +269,17 @@ HYPRE_Int hypre_amd_GetDeviceRapPath(HYPRE_Int *pilot, HYPRE_Int *attempts, HYPR
  * the number built on the device since the previous call.  The reference's device routine:
  * parcsr_ls/par_lr_interp_device.c:1001. */
 HYPRE_Int hypre_amd_SetSetupDeviceInterp(HYPRE_Int on);
+/* How the last call of the device interpolation kernel went, five numbers: out[0] the first rung tried, out[1] the rung
+ * that held every row (-1: none), out[2] the attempts made, out[3] the storage mode (0: one pass into rows of fixed
+ * stride, P_max_elmts > 0 or a distributed level; 1: lengths first, then columns and values), out[4] why the kernel
+ * declined and left the level to the host loop (0: it did not; 1: truncation by threshold alone, P_max_elmts = 0 with
+ * trunc_factor > 0; 2: a row fits no rung — more than 1024 points in its interpolatory set, or so many strong
+ * neighbours that they and the set could fill the row's map; 3: an allocation failed). */
+HYPRE_Int hypre_amd_GetDeviceInterpPath(HYPRE_Int *out);
+/* Test switch: the number of waves (one per row in flight) the interpolation kernel is launched with; 0 restores the
+ * default, min(rows, 32 per compute unit).  With a few waves over many rows one wave walks many rows, each under a new
+ * tag, past the slots its earlier rows left in the map. */
+HYPRE_Int hypre_amd_SetDeviceInterpWaves(HYPRE_Int waves);
 /* And for strength of connection, PMIS coarsening and the smoother diagonals (setup_kernels.hip; the HOST routines'
  * measures and results, not the reference's device variant with its own random numbers): with all three switches on, a
  * single-rank scalar level of at least min_rows rows is set up without leaving the device — the coarse operator is not

@@ -18,6 +18,8 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+from util import parcsr
+
 pytestmark = pytest.mark.gpu
 
 EPS = np.finfo(np.float64).eps
@@ -108,19 +110,6 @@ def row_lengths(A, P):
 # ---------------------------------------------------------------------------------------------------------------------
 # the library's side
 # ---------------------------------------------------------------------------------------------------------------------
-def parcsr(L, B, M, location):
-    """one-rank ParCSR matrix whose diagonal block is M in its stored order (empty ghost block)"""
-    n, m = M.shape
-    par = L.hypre_ParCSRMatrixCreate(0, n, m, None, None, 0, 0, 0)
-    L.hypre_ParCSRMatrixInitialize_v2(par, B.HYPRE_MEMORY_HOST)
-    L.hypre_CSRMatrixDestroy(par.contents.diag)
-    par.contents.diag = B.csr_from_arrays(n, m, M.indptr, M.indices, M.data, B.HYPRE_MEMORY_HOST)
-    if location != B.HYPRE_MEMORY_HOST:
-        L.hypre_ParCSRMatrixMigrate(par, location)
-    B.check()
-    return par
-
-
 def galerkin(L, B, A, P, device, keepT=1, on_device=False):
     """hypre_BoomerAMGBuildCoarseOperatorKT(P, A, P) -> (arrays of the product, arrays of P's stored transpose or None,
     products the device formed, path report)"""

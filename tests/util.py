@@ -50,6 +50,19 @@ def laplace_3d(nx, ny, nz, stencil=7):
     return A
 
 
+def parcsr(L, B, M, location):
+    """one-rank ParCSR matrix whose diagonal block is M in its stored order (empty ghost block)"""
+    n, m = M.shape
+    par = L.hypre_ParCSRMatrixCreate(0, n, m, None, None, 0, 0, 0)
+    L.hypre_ParCSRMatrixInitialize_v2(par, B.HYPRE_MEMORY_HOST)
+    L.hypre_CSRMatrixDestroy(par.contents.diag)
+    par.contents.diag = B.csr_from_arrays(n, m, M.indptr, M.indices, M.data, B.HYPRE_MEMORY_HOST)
+    if location != B.HYPRE_MEMORY_HOST:
+        L.hypre_ParCSRMatrixMigrate(par, location)
+    B.check()
+    return par
+
+
 def random_csr(nrows, ncols, min_nnz, max_nnz, seed=0, empty_frac=0.0):
     """Rows with a uniformly random number of entries in [min_nnz, max_nnz], unsorted columns."""
     rng = np.random.default_rng(seed)
