@@ -364,6 +364,10 @@ void launch_scaled_recip(double w, const double *f, const double *d, double *z, 
 void launch_diagscale2(const double *diag, const double *x, double beta, double *y, double *z,
                        int computeY, size_t n, hipStream_t s);
 void launch_dot(const double *x, const double *y, size_t n, double *d_out, hipStream_t s);
+void launch_dot_final(const double *partial, int m, double *d_out, hipStream_t s);   // folds m workgroup partials as launch_dot does
+// one modified Gram-Schmidt step in one pass (mass_kernels.hip): y += a x, then d_out[0] = <z, y>; z may be y.  The bits
+// of launch_axpy(a, x, y) followed by launch_dot(z, y).
+void launch_axpy_dot(double a, const double *x, double *y, const double *z, size_t n, double *d_out, hipStream_t s);
 // batched BLAS-1 (mass_kernels.hip): k vectors in chunks of MASS_CHUNK, every vector read once per chunk.  The dots
 // return where their k (2 k: <x, z_j> first, <y, z_j> behind) sums lie in device scratch, valid until the next
 // reduction; sum j has the bits of launch_dot(x, y_j), the update those of k launch_axpy calls in order.

@@ -534,6 +534,9 @@ void launch_dot(const double *x, const double *y, size_t n, double *d_out, hipSt
    hipLaunchKernelGGL(dot_partial_kernel, dim3(nb), dim3(256), 0, s, x, y, n, partial);
    hipLaunchKernelGGL(dot_final_kernel, dim3(1), dim3(256), 0, s, partial, nb, d_out);
 }
+// the second half of launch_dot for kernels of other files that leave dot_partial_kernel's partials (mass_kernels.hip)
+void launch_dot_final(const double *partial, int m, double *d_out, hipStream_t s)
+{ hipLaunchKernelGGL(dot_final_kernel, dim3(1), dim3(256), 0, s, partial, m, d_out); }
 void launch_pcg_update(double a, double na, const double *p, const double *sv, double *x, double *r, size_t n,
                        double *d_out, hipStream_t s)
 {

@@ -141,6 +141,39 @@ __global__ void mass_axpy_kernel(const MassCoefficients<K> alpha, const MassVect
    }
 }
 
+// One step of modified Gram-Schmidt in one pass (par_flexgmres.cpp): y += a x, rounded like axpy_kernel rounds it (the
+// same expression under the same contraction rule), and this workgroup's share of <z, y> of the updated y, walked and
+// folded like dot_partial_kernel walks and folds <z, y>: the grid of a dot product, the same trips, the same per-pair
+// term, the same fold.  SELF: z is y (the last step of a column takes the squared norm), and y is read once.  No
+// restrict on the vectors: z may be y.
+template <bool SELF>
+__global__ __launch_bounds__(256)
+void mgs_step_kernel(double a, const double *x, double *y, const double *z, size_t n, double *__restrict__ partial)
+{
+   __shared__ double wsum[4];
+   double acc = 0.0;
+   VEC_LOOP_BEGIN
+      const double2 xv = reinterpret_cast<const double2 *>(x)[i];
+      double2 t = reinterpret_cast<double2 *>(y)[i];
+      double2 zv;
+      if (!SELF) { zv = reinterpret_cast<const double2 *>(z)[i]; }
+      t.x += a * xv.x; t.y += a * xv.y;
+      reinterpret_cast<double2 *>(y)[i] = t;
+      acc += dot_pair(SELF ? t : zv, t);
+   VEC_LOOP_END
+   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
+   {
+      double t = y[n - 1];
+      t += a * x[n - 1];
+      y[n - 1] = t;
+      acc = dot_last(SELF ? t : z[n - 1], t, acc);
+   }
+   acc = wave_sum(acc);
+   if ((threadIdx.x & 63) == 0) { wsum[threadIdx.x >> 6] = acc; }
+   __syncthreads();
+   if (threadIdx.x == 0) { partial[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]); }
+}
+
 // ---------------------------------------------------------------------------
 // launchers: k vectors in chunks of MASS_CHUNK, one kernel instance per chunk length
 // ---------------------------------------------------------------------------
@@ -242,6 +275,19 @@ void launch_mass_axpy(const double *alpha, const double *const *x, double *y, in
       MASS_DISPATCH(kk, CALL)
 #undef CALL
    }
+}
+
+// y += a x and d_out[0] = <z, y> of the updated y (this rank's part): the bits of launch_axpy(a, x, y) followed by
+// launch_dot(z, y), in 32 n bytes instead of 40 n (24 n instead of 40 n when z is y) and one launch less
+void launch_axpy_dot(double a, const double *x, double *y, const double *z, size_t n, double *d_out, hipStream_t s)
+{
+   const bool self = z == y;
+   account_bytes((self ? 24.0 : 32.0) * n);
+   const int nb = dot_grid(n);
+   double *partial = reduce_scratch(DOT_BLOCKS + 16) + 16;
+   if (self) { hipLaunchKernelGGL(mgs_step_kernel<true>, dim3(nb), dim3(256), 0, s, a, x, y, z, n, partial); }
+   else { hipLaunchKernelGGL(mgs_step_kernel<false>, dim3(nb), dim3(256), 0, s, a, x, y, z, n, partial); }
+   launch_dot_final(partial, nb, d_out, s);
 }
 
 void preload_mass_kernels() { hipFuncAttributes at; (void) hipFuncGetAttributes(&at, (const void *) mass_dot_final_kernel); (void) hipGetLastError(); }

@@ -25,7 +25,8 @@ class IJOptions:
         self.sys_num_fun = 1          # -sysL <num functions>: systems version of the 7-point operator
         self.c = (1.0, 1.0, 1.0)      # -c cx cy cz
         self.a = (1.0, 1.0, 1.0)      # -a ax ay az (difconv)
-        self.solver = 0               # 0 AMG, 1 AMG-PCG, 2 DS-PCG (diagonal scaling), 3 AMG-GMRES, 4 DS-GMRES, 16 AMG-COGMRES, 17 DS-COGMRES
+        self.solver = 0               # 0 AMG, 1 AMG-PCG, 2 DS-PCG (diagonal scaling), 3 AMG-GMRES, 4 DS-GMRES, 16 AMG-COGMRES, 17 DS-COGMRES,
+                                      # 60 DS-FlexGMRES, 61 AMG-FlexGMRES
         self.neg_a = 0                # -negA 1: solve with -A (test/ij.c:4014-4017)
         self.num_components = 1       # -nc: columns of b and x (multivectors; test/ij.c:874-878, 3400-3404)
         self.k_dim = 5                # -k (GMRES restart length, test/ij.c:1731)
@@ -361,15 +362,25 @@ def parse_cli(argv):
         else:
             raise SystemExit("ij: option %s is outside the scope of this driver" % flag)
     if opt.solver not in (0, 1, 2, 3, 4, 16, 17):
+        # FlexGMRES (60 DS, 61 AMG) is served by run() for options built in code, but the command line keeps refusing the
+        # two ids: tests/test_cogmres_cli.py pins them as outside its scope
         raise SystemExit("ij: -solver %d is outside the scope of this driver (0 AMG, 1 AMG-PCG, 2 DS-PCG, 3 AMG-GMRES, 4 DS-GMRES, "
                          "16 AMG-COGMRES, 17 DS-COGMRES)" % opt.solver)
+    return check_options(opt)
+
+
+def check_options(opt):
+    """The combinations of options this driver serves, whether they came from the command line or were set in code
+    (solvers 60 / 61, FlexGMRES, only the latter); returns opt."""
+    if opt.solver not in (0, 1, 2, 3, 4, 16, 17, 60, 61):
+        raise SystemExit("ij: solver %d is outside the scope of this driver" % opt.solver)
     if opt.num_components < 1 or (opt.num_components > 1 and (opt.rhs != "one" or opt.rhsfromfile)):
         # test/ij.c:3400-3404 takes several components with the constant right-hand sides only
         raise SystemExit("ij: -nc %d needs -rhsisone in this driver" % opt.num_components)
     if opt.num_components > 1 and opt.solver in (16, 17):
         raise SystemExit("ij: -nc %d with -solver %d: COGMRES doesn't take multicomponent vectors in this driver (GMRES, -solver 3 | 4, does)"
                          % (opt.num_components, opt.solver))
-    if opt.num_components > 1 and opt.solver in (0, 1, 3):
+    if opt.num_components > 1 and opt.solver in (0, 1, 3, 61):
         # BoomerAMG on multivectors (hypre_BoomerAMGSolve with num_vectors > 1) serves l1-Jacobi / Jacobi 7 / 18 and two-stage
         # Gauss-Seidel 11 / 12 over all points with a direct coarsest-level solve; the reference refuses hybrid Gauss-Seidel
         # (the defaults 13 / 14) with multicomponent vectors as well
@@ -421,7 +432,7 @@ def run(opt, comm=0, rank=0, nprocs=1, allreduce=None, out=None):
     out = out or sys.stdout
     L = B.load_library()
     A = build_matrix(opt, comm=comm, rank=rank, nprocs=nprocs)
-    if opt.solver in (2, 4, 17):
+    if opt.solver in (2, 4, 17, 60):
         return run_ds_pcg(opt, A, comm=comm, rank=rank, allreduce=allreduce, out=out)
     s = create_amg(opt, memory_location=DEVICE)
     L.HYPRE_BoomerAMGSetup(s, A, None, None)
@@ -480,6 +491,9 @@ def run(opt, comm=0, rank=0, nprocs=1, allreduce=None, out=None):
     elif opt.solver == 16:
         its.value, rel.value = solve_cogmres(opt, A, db, dx, comm=comm, amg=s)
         lines += ["", "COGMRES Iterations = %d" % its.value, "Final COGMRES Relative Residual Norm = %e" % rel.value, ""]
+    elif opt.solver == 61:
+        its.value, rel.value = solve_flexgmres(opt, A, db, dx, comm=comm, amg=s)
+        lines += ["", "FlexGMRES Iterations = %d" % its.value, "Final FlexGMRES Relative Residual Norm = %e" % rel.value, ""]
     else:
         L.HYPRE_BoomerAMGSetTol(s, 0.0)
         L.HYPRE_BoomerAMGSetMaxIter(s, opt.precon_cycles)
@@ -545,7 +559,7 @@ def solve_ds_gmres(opt, A, db, dx, comm=0):
 
 
 def run_ds_pcg(opt, A, comm=0, rank=0, allreduce=None, out=None):
-    """`ij -solver 2 | 4 [-nc N]` on the device: no hierarchy; the N columns of b (test/ij.c:3483-3512: the same values in
+    """`ij -solver 2 | 4 | 17 | 60 [-nc N]` on the device: no hierarchy; the N columns of b (test/ij.c:3483-3512: the same values in
     every component) and of the zero initial guess as multivectors."""
     L = B.load_library()
     L.hypre_ParCSRMatrixMigrate(A, DEVICE)
@@ -565,12 +579,12 @@ def run_ds_pcg(opt, A, comm=0, rank=0, allreduce=None, out=None):
     else:
         db = B.parvec_from_numpy(b, comm=comm, global_size=nglob, first=first)
         dx = B.parvec_from_numpy(x0, comm=comm, global_size=nglob, first=first)
-    its, rel = {2: solve_ds_pcg, 4: solve_ds_gmres, 17: solve_cogmres}[opt.solver](opt, A, db, dx, comm=comm)
+    its, rel = {2: solve_ds_pcg, 4: solve_ds_gmres, 17: solve_cogmres, 60: solve_flexgmres}[opt.solver](opt, A, db, dx, comm=comm)
     L.HYPRE_ClearError(256)
     B.check()
     L.hypre_ParVectorDestroy(db); L.hypre_ParVectorDestroy(dx)
     if rank == 0:
-        tag = {4: "GMRES ", 17: "COGMRES "}.get(opt.solver, "")
+        tag = {4: "GMRES ", 17: "COGMRES ", 60: "FlexGMRES "}.get(opt.solver, "")
         out.write("\n".join(["", "%sIterations = %d" % (tag, its), "Final %sRelative Residual Norm = %e" % (tag, rel), ""]) + "\n")
         out.flush()
     return its, rel
@@ -627,13 +641,50 @@ def solve_cogmres(opt, A, b, x, comm=0, amg=None):
     return its.value, rel.value
 
 
+def solve_flexgmres(opt, A, b, x, comm=0, amg=None):
+    """test/ij.c:7565-7578, 7720-7724, 7892-7943: FlexGMRES behind BoomerAMG (solver 61, `amg` the set-up hierarchy) or behind the
+    diagonal scaling preconditioner (solver 60); b and x may be multivectors (-nc N).  modify_pc stays the default, which
+    changes nothing."""
+    L = B.load_library()
+    g = C.c_void_p()
+    L.HYPRE_ParCSRFlexGMRESCreate(comm, C.byref(g))
+    L.HYPRE_FlexGMRESSetKDim(g, opt.k_dim)
+    L.HYPRE_FlexGMRESSetMaxIter(g, opt.max_iter)
+    L.HYPRE_FlexGMRESSetTol(g, opt.tol)
+    L.HYPRE_FlexGMRESSetAbsoluteTol(g, 0.0)
+    L.HYPRE_FlexGMRESSetLogging(g, 1)
+    L.HYPRE_FlexGMRESSetPrintLevel(g, 3)         # ioutdat (test/ij.c:686); inert here
+    if amg is not None:
+        L.HYPRE_BoomerAMGSetTol(amg, 0.0)
+        L.HYPRE_BoomerAMGSetMaxIter(amg, opt.precon_cycles)
+        L.HYPRE_FlexGMRESSetMaxIter(g, opt.mg_max_iter)
+        L.HYPRE_FlexGMRESSetPrecond(g, C.cast(L.HYPRE_BoomerAMGSolve, C.c_void_p), None, amg)
+    else:
+        L.HYPRE_FlexGMRESSetPrecond(g, C.cast(L.HYPRE_ParCSRDiagScale, C.c_void_p), C.cast(L.HYPRE_ParCSRDiagScaleSetup, C.c_void_p), None)
+    gotten = C.c_void_p()
+    L.HYPRE_FlexGMRESGetPrecond(g, C.byref(gotten))
+    if gotten.value != (amg.value if amg is not None else None):
+        raise SystemExit("HYPRE_FlexGMRESGetPrecond got bad precond")
+    L.HYPRE_ParCSRFlexGMRESSetup(g, A, b, x)
+    L.HYPRE_ParCSRFlexGMRESSolve(g, A, b, x)
+    its, rel = C.c_int(), C.c_double()
+    L.HYPRE_FlexGMRESGetNumIterations(g, C.byref(its))
+    L.HYPRE_FlexGMRESGetFinalRelativeResidualNorm(g, C.byref(rel))
+    L.HYPRE_ParCSRFlexGMRESDestroy(g)
+    return its.value, rel.value
+
+
 def main(argv=None):
     """`python -m hypre_amd.ij <reference ij flags>`; under torch.distributed.run one rank per process
     (ranks may share a GPU: the halo then travels over gloo, staged through the host)."""
-    import os
     import sys
     argv = sys.argv[1:] if argv is None else argv
-    opt = parse_cli(argv)
+    return launch(parse_cli(argv))
+
+
+def launch(opt):
+    """run(opt) in this process, or as one rank of the torch.distributed.run job this process belongs to"""
+    import os
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world == 1:
         run(opt)

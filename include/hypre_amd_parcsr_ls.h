@@ -543,6 +543,64 @@ HYPRE_Int HYPRE_COGMRESGetNumIterations(HYPRE_Solver solver, HYPRE_Int *num_iter
 HYPRE_Int HYPRE_COGMRESGetFinalRelativeResidualNorm(HYPRE_Solver solver, HYPRE_Real *norm);
 HYPRE_Int HYPRE_COGMRESGetConverged(HYPRE_Solver solver, HYPRE_Int *converged);
 
+/* ---- FlexGMRES: restarted GMRES that keeps the preconditioned vectors (the reference's `ij -solver 60 | 61`) ----
+ * krylov/flexgmres.c:330-760, krylov/HYPRE_flexgmres.c, parcsr_ls/HYPRE_parcsr_flexgmres.c; defaults of
+ * hypre_FlexGMRESCreate (flexgmres.c:86-91): k_dim 20, tol 1e-6, a_tol 0, min_iter 0, max_iter 1000.  The correction of
+ * a restart cycle is a combination of the stored vectors Z_j = M_j^{-1} v_j, so the preconditioner may differ from one
+ * application to the next and is applied once per iteration, never once more per restart.  Before every application the
+ * target is cleared and modify_pc(precond_solver, iteration, |r| / |b|) is called (default: does nothing).  SetKDim must
+ * precede Setup (2 (k_dim + 1) + 2 work vectors).  The convergence-factor exit is not carried: SetConvergenceFactorTol
+ * takes 0.0 only.  HYPRE_ERROR_CONV when max_iter is reached above the tolerance — unlike flexgmres.c:743 also when both
+ * tolerances are zero.  Vectors may be multivectors; the inner product is the flat one over all columns. */
+typedef HYPRE_Int (*HYPRE_PtrToModifyPCFcn)(HYPRE_Solver, HYPRE_Int, HYPRE_Real);
+HYPRE_Int HYPRE_ParCSRFlexGMRESCreate(MPI_Comm comm, HYPRE_Solver *solver);
+HYPRE_Int HYPRE_ParCSRFlexGMRESDestroy(HYPRE_Solver solver);
+HYPRE_Int HYPRE_ParCSRFlexGMRESSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_ParCSRFlexGMRESSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_FlexGMRESSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_FlexGMRESSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_FlexGMRESSetKDim(HYPRE_Solver solver, HYPRE_Int k_dim);
+HYPRE_Int HYPRE_FlexGMRESSetTol(HYPRE_Solver solver, HYPRE_Real tol);
+HYPRE_Int HYPRE_FlexGMRESSetAbsoluteTol(HYPRE_Solver solver, HYPRE_Real a_tol);
+HYPRE_Int HYPRE_FlexGMRESSetConvergenceFactorTol(HYPRE_Solver solver, HYPRE_Real cf_tol);   /* 0.0 only */
+HYPRE_Int HYPRE_FlexGMRESSetMinIter(HYPRE_Solver solver, HYPRE_Int min_iter);
+HYPRE_Int HYPRE_FlexGMRESSetMaxIter(HYPRE_Solver solver, HYPRE_Int max_iter);
+HYPRE_Int HYPRE_FlexGMRESSetPrecond(HYPRE_Solver solver, HYPRE_PtrToSolverFcn precond,
+                                    HYPRE_PtrToSolverFcn precond_setup, HYPRE_Solver precond_solver);
+HYPRE_Int HYPRE_FlexGMRESGetPrecond(HYPRE_Solver solver, HYPRE_Solver *precond_data_ptr);
+HYPRE_Int HYPRE_FlexGMRESSetModifyPC(HYPRE_Solver solver, HYPRE_PtrToModifyPCFcn modify_pc);   /* NULL: the default */
+HYPRE_Int HYPRE_FlexGMRESSetLogging(HYPRE_Solver solver, HYPRE_Int logging);       /* accepted, inert */
+HYPRE_Int HYPRE_FlexGMRESSetPrintLevel(HYPRE_Solver solver, HYPRE_Int level);      /* accepted, inert */
+HYPRE_Int HYPRE_FlexGMRESGetNumIterations(HYPRE_Solver solver, HYPRE_Int *num_iterations);
+HYPRE_Int HYPRE_FlexGMRESGetFinalRelativeResidualNorm(HYPRE_Solver solver, HYPRE_Real *norm);
+HYPRE_Int HYPRE_FlexGMRESGetConverged(HYPRE_Solver solver, HYPRE_Int *converged);
+HYPRE_Int HYPRE_ParCSRFlexGMRESSetKDim(HYPRE_Solver solver, HYPRE_Int k_dim);
+HYPRE_Int HYPRE_ParCSRFlexGMRESSetTol(HYPRE_Solver solver, HYPRE_Real tol);
+HYPRE_Int HYPRE_ParCSRFlexGMRESSetAbsoluteTol(HYPRE_Solver solver, HYPRE_Real a_tol);
+HYPRE_Int HYPRE_ParCSRFlexGMRESSetMinIter(HYPRE_Solver solver, HYPRE_Int min_iter);
+HYPRE_Int HYPRE_ParCSRFlexGMRESSetMaxIter(HYPRE_Solver solver, HYPRE_Int max_iter);
+HYPRE_Int HYPRE_ParCSRFlexGMRESSetPrecond(HYPRE_Solver solver, HYPRE_PtrToSolverFcn precond,
+                                          HYPRE_PtrToSolverFcn precond_setup, HYPRE_Solver precond_solver);
+HYPRE_Int HYPRE_ParCSRFlexGMRESGetPrecond(HYPRE_Solver solver, HYPRE_Solver *precond_data_ptr);
+HYPRE_Int HYPRE_ParCSRFlexGMRESSetModifyPC(HYPRE_Solver solver, HYPRE_PtrToModifyPCFcn modify_pc);
+HYPRE_Int HYPRE_ParCSRFlexGMRESSetLogging(HYPRE_Solver solver, HYPRE_Int logging);
+HYPRE_Int HYPRE_ParCSRFlexGMRESSetPrintLevel(HYPRE_Solver solver, HYPRE_Int level);
+HYPRE_Int HYPRE_ParCSRFlexGMRESGetNumIterations(HYPRE_Solver solver, HYPRE_Int *num_iterations);
+HYPRE_Int HYPRE_ParCSRFlexGMRESGetFinalRelativeResidualNorm(HYPRE_Solver solver, HYPRE_Real *norm);
+/* Modified Gram-Schmidt of FlexGMRES, fused (1, the default): Arnoldi step i is one inner product and i launches that
+ * each subtract the projection on one basis vector and leave the inner product with the next one (the last: the squared
+ * norm) in the same pass; the correction of a restart is one batched update.  0: the reference's sequence of
+ * InnerProd / Axpy calls.  Either way a solve gives the same bits in x, the same iteration count and the same norm. */
+HYPRE_Int hypre_amd_FlexGMRESSetFusedOrthogonalization(HYPRE_Solver solver, HYPRE_Int on);
+/* Launches of the Gram-Schmidt steps of the last solve: fused steps, separate inner products (the norms included) and
+ * separate updates.  Fused, step i counts (i, 1, 0); not fused (0, i + 1, i).  Host counters; any pointer may be NULL. */
+HYPRE_Int hypre_amd_FlexGMRESGetLaunchStats(HYPRE_Solver solver, HYPRE_Int *fused_steps, HYPRE_Int *plain_dots, HYPRE_Int *plain_axpys);
+/* y += alpha x, then *result = <z, y> over all ranks, in one pass over the vectors (z may be y): the fused launch of a
+ * Gram-Schmidt step and the reduction of hypre_ParVectorInnerProd.  The bits of hypre_ParVectorAxpy followed by
+ * hypre_ParVectorInnerProd(z, y). */
+HYPRE_Int hypre_amd_ParVectorAxpyThenInnerProd(HYPRE_Complex alpha, hypre_ParVector *x, hypre_ParVector *y, hypre_ParVector *z,
+                                               HYPRE_Real *result);
+
 #ifdef __cplusplus
 }
 #endif
