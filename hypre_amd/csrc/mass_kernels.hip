@@ -1,5 +1,5 @@
 // hypre_amd — batched vector kernels for gfx950 (CDNA4): many dot products against one vector, and one vector updated
-// with many, in one pass over HBM each.  They are what the classical Gram-Schmidt of COGMRES (par_cogmres.cpp) is built
+// with many, in one pass over HBM each.  They are what the classical Gram-Schmidt of COGMRES (par_gmres.cpp) is built
 // on: step i of a restart cycle needs <p_i, p_j> for all j < i and p_i -= sum_j h_j p_j, which as separate dots and
 // axpys is 5 i vector passes and i read-backs; batched it is 2 i + 2 passes and one read-back.
 //
@@ -141,7 +141,7 @@ __global__ void mass_axpy_kernel(const MassCoefficients<K> alpha, const MassVect
    }
 }
 
-// One step of modified Gram-Schmidt in one pass (par_flexgmres.cpp): y += a x, rounded like axpy_kernel rounds it (the
+// One step of modified Gram-Schmidt in one pass (par_gmres.cpp): y += a x, rounded like axpy_kernel rounds it (the
 // same expression under the same contraction rule), and this workgroup's share of <z, y> of the updated y, walked and
 // folded like dot_partial_kernel walks and folds <z, y>: the grid of a dot product, the same trips, the same per-pair
 // term, the same fold.  SELF: z is y (the last step of a column takes the squared norm), and y is read once.  No

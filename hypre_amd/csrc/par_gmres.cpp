@@ -1,16 +1,21 @@
-// hypre_amd — right-preconditioned restarted GMRES, the second Krylov caller of the
-// BoomerAMG solve phase (`ij -solver 3`).
+// hypre_amd — the three right-preconditioned restarted GMRES solvers on ParVectors on the device:
+//    GMRES      HYPRE_ParCSRGMRES*  / HYPRE_GMRES*       `ij -solver 3 | 4`     krylov/gmres.c, parcsr_ls/HYPRE_parcsr_gmres.c
+//    COGMRES    HYPRE_ParCSRCOGMRES* / HYPRE_COGMRES*    `ij -solver 16 | 17`   krylov/cogmres.c, parcsr_ls/HYPRE_parcsr_cogmres.c
+//    FlexGMRES  HYPRE_ParCSRFlexGMRES* / HYPRE_FlexGMRES* `ij -solver 60 | 61`  krylov/flexgmres.c, parcsr_ls/HYPRE_parcsr_flexgmres.c
+// The iteration itself (Hessenberg matrix, Givens rotations, every decision) is gmres_core.hpp; this file gives it the
+// vectors, every inner product ending in one scalar read-back, and the entry points.  The three differ in the GMRESParams
+// their Create fills in (the table is in DESIGN.md) and in two refusals: COGMRES Setup takes no multivectors, FlexGMRES
+// Solve no host operands.  The relative-change and convergence-factor exits of the reference (rel_change, cf_tol) are not
+// carried.
 //
-// Reference: krylov/gmres.c:274-1000 (hypre_GMRESSolve) with parcsr_ls/HYPRE_parcsr_gmres.c and
-// krylov/HYPRE_gmres.c for the entry points; defaults of hypre_GMRESCreate (gmres.c:68-110):
-// k_dim 5, tol 1e-6, a_tol 0, min_iter 0, max_iter 1000, rel_change 0, skip_real_r_check 0.
-// Modified Gram-Schmidt, Givens rotations on the host, the true residual is recomputed before
-// convergence is accepted; the relative-change and convergence-factor exits of the reference
-// (rel_change, cf_tol) are not carried.  Vectors stay on the device; every inner product ends in
-// one scalar read-back, as in the reference.
+// Modified Gram-Schmidt, fused (the FlexGMRES default): step i is one hypre_ParVectorInnerProd and i launches of
+// launch_axpy_dot, each subtracting the projection on p[j] and leaving <p[j + 1], p[i]> (the last one |p[i]|^2) in the
+// same pass: 32 i + 8 bytes per element in i + 1 launches, where the dot / axpy sequence of the reference moves 40 i + 8
+// in 2 i + 1.  Same order of operations and same roundings, so a solve has the same bits either way
+// (hypre_amd_FlexGMRESSetFusedOrthogonalization).  Classical Gram-Schmidt (COGMRES) reads every basis vector twice per
+// step and ends in two read-backs (the batch and the norm) where the modified one needs i + 1.
 #include "amg_internal.hpp"
-#include <algorithm>
-#include <cmath>
+#include "gmres_core.hpp"
 #include <cstring>
 #include <vector>
 
@@ -20,64 +25,163 @@ struct hypre_amd_GMRESData
 {
    hypre_Solver base;
    MPI_Comm comm;
-   HYPRE_Int k_dim = 5, min_iter = 0, max_iter = 1000, skip_real_r_check = 0;
-   HYPRE_Real tol = 1e-6, a_tol = 0.0;
+   GMRESParams prm;
    HYPRE_PtrToSolverFcn precond = nullptr, precond_setup = nullptr;
    HYPRE_Solver precond_data = nullptr;
+   HYPRE_PtrToModifyPCFcn modify_pc = nullptr;          // nullptr: hypre_FlexGMRESModifyPCDefault, which does nothing
    hypre_ParVector *r = nullptr, *w = nullptr;
-   std::vector<hypre_ParVector *> p;
+   std::vector<hypre_ParVector *> p, pre_vecs;          // pre_vecs only if prm.flexible
    HYPRE_Int num_iterations = 0, converged = 0;
    HYPRE_Real rel_residual_norm = 0.0;
+   HYPRE_Int fused_steps = 0, plain_dots = 0, plain_axpys = 0;
 };
 
 namespace {
+hypre_amd_GMRESData *D(HYPRE_Solver s) { return (hypre_amd_GMRESData *) s; }
+
 void free_vectors(hypre_amd_GMRESData *d)
 {
    hypre_ParVectorDestroy(d->r); hypre_ParVectorDestroy(d->w);
    d->r = d->w = nullptr;
    for (hypre_ParVector *v : d->p) { hypre_ParVectorDestroy(v); }
-   d->p.clear();
+   for (hypre_ParVector *v : d->pre_vecs) { hypre_ParVectorDestroy(v); }
+   d->p.clear(); d->pre_vecs.clear();
+}
+
+HYPRE_Int create(MPI_Comm comm, HYPRE_Solver *solver, const GMRESParams &prm)
+{
+   hypre_amd_GMRESData *d = new hypre_amd_GMRESData();
+   memset(&d->base, 0, sizeof(d->base));
+   d->comm = comm;
+   d->prm = prm;
+   *solver = (HYPRE_Solver) d;
+   return hypre_error_flag;
+}
+
+HYPRE_Int destroy(HYPRE_Solver solver)
+{
+   if (!solver) { return hypre_error_flag; }
+   free_vectors(D(solver));
+   delete D(solver);
+   return hypre_error_flag;
+}
+
+HYPRE_Int set_k_dim(HYPRE_Solver s, HYPRE_Int v)
+{
+   if (v < 1) { hypre_error_in_arg(2); return hypre_error_flag; }
+   D(s)->prm.k_dim = v;
+   return hypre_error_flag;
+}
+
+HYPRE_Int set_precond(HYPRE_Solver s, HYPRE_PtrToSolverFcn precond, HYPRE_PtrToSolverFcn precond_setup, HYPRE_Solver precond_solver)
+{
+   hypre_amd_GMRESData *d = D(s);
+   d->precond = precond; d->precond_setup = precond_setup; d->precond_data = precond_solver;
+   return hypre_error_flag;
+}
+
+bool on_device(hypre_ParVector *v) { return v->local_vector->memory_location == HYPRE_MEMORY_DEVICE; }
+
+// work vectors shaped like x (gmres.c:204-215, cogmres.c:220-231, flexgmres.c:230-250 CreateVector / CreateVectorArray):
+// the columns of a multivector x
+HYPRE_Int setup(HYPRE_Solver solver, hypre_ParCSRMatrix *A, hypre_ParVector *b, hypre_ParVector *x)
+{
+   hypre_amd_GMRESData *d = D(solver);
+   free_vectors(d);
+   const HYPRE_MemoryLocation loc = x->local_vector->memory_location;
+   const HYPRE_Int nv = x->local_vector->num_vectors;
+   auto mk = [&]() { hypre_ParVector *v = hypre_ParMultiVectorCreate(A->comm, A->global_num_rows, A->row_starts, nv); hypre_ParVectorInitialize_v2(v, loc); return v; };
+   d->r = mk(); d->w = mk();
+   for (HYPRE_Int i = 0; i <= d->prm.k_dim; i++)
+   {
+      d->p.push_back(mk());
+      if (d->prm.flexible) { d->pre_vecs.push_back(mk()); }
+   }
+   if (d->precond_setup) { d->precond_setup(d->precond_data, A, b, x); }
+   return hypre_error_flag;
+}
+
+// y += alpha x, then <z, y> over all ranks: the fused launch and the reduction of hypre_ParVectorInnerProd
+HYPRE_Real axpy_then_inner_prod(HYPRE_Complex alpha, hypre_ParVector *x, hypre_ParVector *y, hypre_ParVector *z)
+{
+   hypre_Vector *xl = x->local_vector, *yl = y->local_vector, *zl = z->local_vector;
+   double *d_out = reduce_scratch(2048);
+   launch_axpy_dot(alpha, xl->data, yl->data, zl->data, (size_t) yl->size * (size_t) yl->num_vectors, d_out, stream());
+   double r = 0.0;
+   dev_global_sums(y->comm, d_out, 1, &r);
+   return r;
+}
+
+// the vector operations gmres_iterate asks for
+struct ParOps
+{
+   hypre_amd_GMRESData *d;
+   hypre_ParCSRMatrix *A;
+   void matvec(double alpha, hypre_ParVector *x, double beta, hypre_ParVector *y) { hypre_ParCSRMatrixMatvec(alpha, A, x, beta, y); }
+   double inner(hypre_ParVector *x, hypre_ParVector *y) { return hypre_ParVectorInnerProd(x, y); }
+   void copy(hypre_ParVector *x, hypre_ParVector *y) { hypre_ParVectorCopy(x, y); }
+   void scale(double a, hypre_ParVector *y) { hypre_ParVectorScale(a, y); }
+   void axpy(double a, hypre_ParVector *x, hypre_ParVector *y) { hypre_ParVectorAxpy(a, x, y); }
+   double axpy_dot(double a, hypre_ParVector *x, hypre_ParVector *y, hypre_ParVector *z) { return axpy_then_inner_prod(a, x, y, z); }
+   void mass_axpy(double *a, hypre_ParVector **xs, hypre_ParVector *y, int k, int unroll) { hypre_ParVectorMassAxpy(a, xs, y, k, unroll); }
+   void mass_inner(hypre_ParVector *x, hypre_ParVector **ys, int k, int unroll, double *out) { hypre_ParVectorMassInnerProd(x, ys, k, unroll, out); }
+   void mass_dot_two(hypre_ParVector *x, hypre_ParVector *y, hypre_ParVector **zs, int k, int unroll, double *outx, double *outy)
+   { hypre_ParVectorMassDotpTwo(x, y, zs, k, unroll, outx, outy); }
+   void precond(int iter, double rel_norm, hypre_ParVector *rhs, hypre_ParVector *sol)
+   {
+      hypre_ParVectorSetZeros(sol);        // ClearVector (gmres.c:538, cogmres.c:541, flexgmres.c:549): all_zeros = 1
+      if (d->modify_pc) { d->modify_pc(d->precond_data, iter, rel_norm); }
+      if (d->precond) { d->precond(d->precond_data, A, rhs, sol); }
+      else { hypre_ParVectorCopy(rhs, sol); }
+   }
+   void solution_changed(hypre_ParVector *x) { x->all_zeros = 0; }
+};
+
+// the work vectors are those of another k_dim: msg is the entry point's "...Solve: call ...Setup after ...SetKDim"
+bool stale(HYPRE_Solver solver, const char *msg)
+{
+   if ((HYPRE_Int) D(solver)->p.size() == D(solver)->prm.k_dim + 1) { return false; }
+   hypre_error_w_msg(HYPRE_ERROR_GENERIC, msg);
+   return true;
+}
+
+HYPRE_Int solve(HYPRE_Solver solver, hypre_ParCSRMatrix *A, hypre_ParVector *b, hypre_ParVector *x)
+{
+   hypre_amd_GMRESData *d = D(solver);
+   d->converged = 0;
+   d->fused_steps = d->plain_dots = d->plain_axpys = 0;
+   const int saved_sync = handle().sync_compute;
+   handle().sync_compute = 0;
+   verify_par_plans(A);                    // a solve never starts from a plan its matrix has moved away from
+   ParOps ops{d, A};
+   const GMRESResult res = gmres_iterate<hypre_ParVector *>(d->prm, ops, b, x, d->r, d->w, d->p.data(), d->pre_vecs.data());
+   if (res.iterations_set) { d->num_iterations = res.iterations; }
+   d->converged = res.converged;
+   if (res.norm_set) { d->rel_residual_norm = res.rel_residual_norm; }
+   d->fused_steps = (HYPRE_Int) res.fused_steps; d->plain_dots = (HYPRE_Int) res.plain_dots; d->plain_axpys = (HYPRE_Int) res.plain_axpys;
+   if (res.status == GMRES_NOT_A_NUMBER) { hypre_error(HYPRE_ERROR_GENERIC); }
+   if (res.status == GMRES_NOT_CONVERGED) { hypre_error(HYPRE_ERROR_CONV); }
+   handle().sync_compute = saved_sync;
+   maybe_sync();
+   return hypre_error_flag;
 }
 }  // namespace
 
 extern "C" {
 
-HYPRE_Int HYPRE_ParCSRGMRESCreate(MPI_Comm comm, HYPRE_Solver *solver)
-{
-   hypre_amd_GMRESData *d = new hypre_amd_GMRESData();
-   memset(&d->base, 0, sizeof(d->base));
-   d->comm = comm;
-   *solver = (HYPRE_Solver) d;
-   return hypre_error_flag;
-}
-
-HYPRE_Int HYPRE_ParCSRGMRESDestroy(HYPRE_Solver solver)
-{
-   hypre_amd_GMRESData *d = (hypre_amd_GMRESData *) solver;
-   if (!d) { return hypre_error_flag; }
-   free_vectors(d);
-   delete d;
-   return hypre_error_flag;
-}
-
-HYPRE_Int HYPRE_GMRESSetKDim(HYPRE_Solver s, HYPRE_Int v)
-{
-   if (v < 1) { hypre_error_in_arg(2); return hypre_error_flag; }
-   ((hypre_amd_GMRESData *) s)->k_dim = v;
-   return hypre_error_flag;
-}
-HYPRE_Int HYPRE_GMRESSetTol(HYPRE_Solver s, HYPRE_Real v) { ((hypre_amd_GMRESData *) s)->tol = v; return hypre_error_flag; }
-HYPRE_Int HYPRE_GMRESSetAbsoluteTol(HYPRE_Solver s, HYPRE_Real v) { ((hypre_amd_GMRESData *) s)->a_tol = v; return hypre_error_flag; }
-HYPRE_Int HYPRE_GMRESSetMinIter(HYPRE_Solver s, HYPRE_Int v) { ((hypre_amd_GMRESData *) s)->min_iter = v; return hypre_error_flag; }
-HYPRE_Int HYPRE_GMRESSetMaxIter(HYPRE_Solver s, HYPRE_Int v) { ((hypre_amd_GMRESData *) s)->max_iter = v; return hypre_error_flag; }
-HYPRE_Int HYPRE_GMRESSetSkipRealResidualCheck(HYPRE_Solver s, HYPRE_Int v) { ((hypre_amd_GMRESData *) s)->skip_real_r_check = v; return hypre_error_flag; }
+// ---- GMRES: defaults of hypre_GMRESCreate (gmres.c:68-110): k_dim 5, tol 1e-6, a_tol 0, min_iter 0, max_iter 1000,
+// rel_change 0, skip_real_r_check 0; modified Gram-Schmidt, plain
+HYPRE_Int HYPRE_ParCSRGMRESCreate(MPI_Comm comm, HYPRE_Solver *solver) { return create(comm, solver, GMRESParams()); }
+HYPRE_Int HYPRE_ParCSRGMRESDestroy(HYPRE_Solver solver) { return destroy(solver); }
+HYPRE_Int HYPRE_GMRESSetKDim(HYPRE_Solver s, HYPRE_Int v) { return set_k_dim(s, v); }
+HYPRE_Int HYPRE_GMRESSetTol(HYPRE_Solver s, HYPRE_Real v) { D(s)->prm.tol = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_GMRESSetAbsoluteTol(HYPRE_Solver s, HYPRE_Real v) { D(s)->prm.a_tol = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_GMRESSetMinIter(HYPRE_Solver s, HYPRE_Int v) { D(s)->prm.min_iter = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_GMRESSetMaxIter(HYPRE_Solver s, HYPRE_Int v) { D(s)->prm.max_iter = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_GMRESSetSkipRealResidualCheck(HYPRE_Solver s, HYPRE_Int v) { D(s)->prm.skip_real_r_check = v; return hypre_error_flag; }
 HYPRE_Int HYPRE_GMRESSetPrecond(HYPRE_Solver s, HYPRE_PtrToSolverFcn precond, HYPRE_PtrToSolverFcn precond_setup,
                                 HYPRE_Solver precond_solver)
-{
-   hypre_amd_GMRESData *d = (hypre_amd_GMRESData *) s;
-   d->precond = precond; d->precond_setup = precond_setup; d->precond_data = precond_solver;
-   return hypre_error_flag;
-}
+{ return set_precond(s, precond, precond_setup, precond_solver); }
 HYPRE_Int HYPRE_GMRESSetLogging(HYPRE_Solver s, HYPRE_Int v) { (void) s; (void) v; return hypre_error_flag; }       // accepted, inert
 HYPRE_Int HYPRE_GMRESSetPrintLevel(HYPRE_Solver s, HYPRE_Int v) { (void) s; (void) v; return hypre_error_flag; }
 HYPRE_Int HYPRE_GMRESSetRelChange(HYPRE_Solver s, HYPRE_Int v)
@@ -86,161 +190,170 @@ HYPRE_Int HYPRE_GMRESSetRelChange(HYPRE_Solver s, HYPRE_Int v)
    if (v != 0) { hypre_error_in_arg(2); hypre_error_w_msg(HYPRE_ERROR_GENERIC, "HYPRE_GMRESSetRelChange: the relative-change stopping test is not built (0 only)"); }
    return hypre_error_flag;
 }
-HYPRE_Int HYPRE_GMRESGetNumIterations(HYPRE_Solver s, HYPRE_Int *v) { *v = ((hypre_amd_GMRESData *) s)->num_iterations; return hypre_error_flag; }
-HYPRE_Int HYPRE_GMRESGetFinalRelativeResidualNorm(HYPRE_Solver s, HYPRE_Real *v) { *v = ((hypre_amd_GMRESData *) s)->rel_residual_norm; return hypre_error_flag; }
-HYPRE_Int HYPRE_GMRESGetConverged(HYPRE_Solver s, HYPRE_Int *v) { *v = ((hypre_amd_GMRESData *) s)->converged; return hypre_error_flag; }
+HYPRE_Int HYPRE_GMRESGetNumIterations(HYPRE_Solver s, HYPRE_Int *v) { *v = D(s)->num_iterations; return hypre_error_flag; }
+HYPRE_Int HYPRE_GMRESGetFinalRelativeResidualNorm(HYPRE_Solver s, HYPRE_Real *v) { *v = D(s)->rel_residual_norm; return hypre_error_flag; }
+HYPRE_Int HYPRE_GMRESGetConverged(HYPRE_Solver s, HYPRE_Int *v) { *v = D(s)->converged; return hypre_error_flag; }
 
 HYPRE_Int HYPRE_ParCSRGMRESSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x)
 {
-   hypre_amd_GMRESData *d = (hypre_amd_GMRESData *) solver;
-   free_vectors(d);
-   const HYPRE_MemoryLocation loc = x->local_vector->memory_location;
-   // work vectors shaped like x (gmres.c:204-215 CreateVector / CreateVectorArray): the columns of a multivector x
-   const HYPRE_Int nv = x->local_vector->num_vectors;
-   auto mk = [&]() { hypre_ParVector *v = hypre_ParMultiVectorCreate(A->comm, A->global_num_rows, A->row_starts, nv); hypre_ParVectorInitialize_v2(v, loc); return v; };
-   d->r = mk(); d->w = mk();
-   for (HYPRE_Int i = 0; i <= d->k_dim; i++) { d->p.push_back(mk()); }
-   if (d->precond_setup) { d->precond_setup(d->precond_data, A, b, x); }
+   return setup(solver, A, b, x);
+}
+HYPRE_Int HYPRE_ParCSRGMRESSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x)
+{
+   if (stale(solver, "HYPRE_ParCSRGMRESSolve: call HYPRE_ParCSRGMRESSetup after HYPRE_GMRESSetKDim")) { return hypre_error_flag; }
+   return solve(solver, A, b, x);
+}
+
+// ---- COGMRES: defaults of hypre_COGMRESCreate (cogmres.c:85-111): k_dim 5, cgs 1, unroll 0, tol 1e-6, a_tol 0,
+// min_iter 0, max_iter 1000, skip_real_r_check 0
+HYPRE_Int HYPRE_ParCSRCOGMRESCreate(MPI_Comm comm, HYPRE_Solver *solver)
+{
+   GMRESParams prm;
+   prm.ortho = GMRESOrtho::CGS;
+   prm.count_at_zero_residual = false;
+   return create(comm, solver, prm);
+}
+HYPRE_Int HYPRE_ParCSRCOGMRESDestroy(HYPRE_Solver solver) { return destroy(solver); }
+HYPRE_Int HYPRE_COGMRESSetKDim(HYPRE_Solver s, HYPRE_Int v) { return set_k_dim(s, v); }
+HYPRE_Int HYPRE_COGMRESSetUnroll(HYPRE_Solver s, HYPRE_Int v) { D(s)->prm.unroll = v; return hypre_error_flag; }   // handed on, ignored by the kernels
+HYPRE_Int HYPRE_COGMRESSetCGS(HYPRE_Solver s, HYPRE_Int v) { D(s)->prm.ortho = v > 1 ? GMRESOrtho::CGS2 : GMRESOrtho::CGS; return hypre_error_flag; }
+HYPRE_Int HYPRE_COGMRESSetTol(HYPRE_Solver s, HYPRE_Real v) { D(s)->prm.tol = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_COGMRESSetAbsoluteTol(HYPRE_Solver s, HYPRE_Real v) { D(s)->prm.a_tol = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_COGMRESSetMinIter(HYPRE_Solver s, HYPRE_Int v) { D(s)->prm.min_iter = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_COGMRESSetMaxIter(HYPRE_Solver s, HYPRE_Int v) { D(s)->prm.max_iter = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_COGMRESSetSkipRealResidualCheck(HYPRE_Solver s, HYPRE_Int v) { D(s)->prm.skip_real_r_check = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_COGMRESSetPrecond(HYPRE_Solver s, HYPRE_PtrToSolverFcn precond, HYPRE_PtrToSolverFcn precond_setup,
+                                  HYPRE_Solver precond_solver)
+{ return set_precond(s, precond, precond_setup, precond_solver); }
+HYPRE_Int HYPRE_COGMRESSetLogging(HYPRE_Solver s, HYPRE_Int v) { (void) s; (void) v; return hypre_error_flag; }       // accepted, inert
+HYPRE_Int HYPRE_COGMRESSetPrintLevel(HYPRE_Solver s, HYPRE_Int v) { (void) s; (void) v; return hypre_error_flag; }
+HYPRE_Int HYPRE_COGMRESGetNumIterations(HYPRE_Solver s, HYPRE_Int *v) { *v = D(s)->num_iterations; return hypre_error_flag; }
+HYPRE_Int HYPRE_COGMRESGetFinalRelativeResidualNorm(HYPRE_Solver s, HYPRE_Real *v) { *v = D(s)->rel_residual_norm; return hypre_error_flag; }
+HYPRE_Int HYPRE_COGMRESGetConverged(HYPRE_Solver s, HYPRE_Int *v) { *v = D(s)->converged; return hypre_error_flag; }
+
+HYPRE_Int HYPRE_ParCSRCOGMRESSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x)
+{
+   free_vectors(D(solver));
+   if (x->local_vector->num_vectors > 1)
+   {
+      hypre_error_w_msg(HYPRE_ERROR_GENERIC, "HYPRE_ParCSRCOGMRESSetup: multivectors are not served by COGMRES (use HYPRE_ParCSRGMRES)");
+      return hypre_error_flag;
+   }
+   return setup(solver, A, b, x);
+}
+HYPRE_Int HYPRE_ParCSRCOGMRESSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x)
+{
+   if (stale(solver, "HYPRE_ParCSRCOGMRESSolve: call HYPRE_ParCSRCOGMRESSetup after HYPRE_COGMRESSetKDim")) { return hypre_error_flag; }
+   return solve(solver, A, b, x);
+}
+
+// ---- FlexGMRES: defaults of hypre_FlexGMRESCreate (flexgmres.c:86-91): k_dim 20, tol 1e-6, a_tol 0, min_iter 0,
+// max_iter 1000; modified Gram-Schmidt, fused.  Before every preconditioner call the target is cleared and
+// modify_pc(precond_data, iter, r_norm / den_norm) is called.
+HYPRE_Int HYPRE_ParCSRFlexGMRESCreate(MPI_Comm comm, HYPRE_Solver *solver)
+{
+   GMRESParams prm;
+   prm.k_dim = 20;
+   prm.ortho = GMRESOrtho::MGS_FUSED;
+   prm.flexible = true;
+   prm.stop_when_residual_grows = false;
+   prm.conv_error_at_zero_tol = true;
+   return create(comm, solver, prm);
+}
+HYPRE_Int HYPRE_ParCSRFlexGMRESDestroy(HYPRE_Solver solver) { return destroy(solver); }
+HYPRE_Int HYPRE_FlexGMRESSetKDim(HYPRE_Solver s, HYPRE_Int v) { return set_k_dim(s, v); }
+HYPRE_Int HYPRE_FlexGMRESSetTol(HYPRE_Solver s, HYPRE_Real v) { D(s)->prm.tol = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_FlexGMRESSetAbsoluteTol(HYPRE_Solver s, HYPRE_Real v) { D(s)->prm.a_tol = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_FlexGMRESSetConvergenceFactorTol(HYPRE_Solver s, HYPRE_Real v)
+{
+   (void) s;
+   if (v != 0.0)
+   {
+      hypre_error_in_arg(2);
+      hypre_error_w_msg(HYPRE_ERROR_GENERIC, "HYPRE_FlexGMRESSetConvergenceFactorTol: the convergence-factor stopping test is not built (0.0 only)");
+   }
+   return hypre_error_flag;
+}
+HYPRE_Int HYPRE_FlexGMRESSetMinIter(HYPRE_Solver s, HYPRE_Int v) { D(s)->prm.min_iter = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_FlexGMRESSetMaxIter(HYPRE_Solver s, HYPRE_Int v) { D(s)->prm.max_iter = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_FlexGMRESSetPrecond(HYPRE_Solver s, HYPRE_PtrToSolverFcn precond, HYPRE_PtrToSolverFcn precond_setup,
+                                    HYPRE_Solver precond_solver)
+{ return set_precond(s, precond, precond_setup, precond_solver); }
+HYPRE_Int HYPRE_FlexGMRESGetPrecond(HYPRE_Solver s, HYPRE_Solver *precond_data_ptr) { *precond_data_ptr = D(s)->precond_data; return hypre_error_flag; }
+HYPRE_Int HYPRE_FlexGMRESSetModifyPC(HYPRE_Solver s, HYPRE_PtrToModifyPCFcn modify_pc) { D(s)->modify_pc = modify_pc; return hypre_error_flag; }
+HYPRE_Int HYPRE_FlexGMRESSetLogging(HYPRE_Solver s, HYPRE_Int v) { (void) s; (void) v; return hypre_error_flag; }       // accepted, inert
+HYPRE_Int HYPRE_FlexGMRESSetPrintLevel(HYPRE_Solver s, HYPRE_Int v) { (void) s; (void) v; return hypre_error_flag; }
+HYPRE_Int HYPRE_FlexGMRESGetNumIterations(HYPRE_Solver s, HYPRE_Int *v) { *v = D(s)->num_iterations; return hypre_error_flag; }
+HYPRE_Int HYPRE_FlexGMRESGetFinalRelativeResidualNorm(HYPRE_Solver s, HYPRE_Real *v) { *v = D(s)->rel_residual_norm; return hypre_error_flag; }
+HYPRE_Int HYPRE_FlexGMRESGetConverged(HYPRE_Solver s, HYPRE_Int *v) { *v = D(s)->converged; return hypre_error_flag; }
+
+HYPRE_Int hypre_amd_FlexGMRESSetFusedOrthogonalization(HYPRE_Solver s, HYPRE_Int on)
+{
+   if (on != 0 && on != 1) { hypre_error_in_arg(2); return hypre_error_flag; }
+   D(s)->prm.ortho = on ? GMRESOrtho::MGS_FUSED : GMRESOrtho::MGS;
+   return hypre_error_flag;
+}
+HYPRE_Int hypre_amd_FlexGMRESGetLaunchStats(HYPRE_Solver s, HYPRE_Int *fused_steps, HYPRE_Int *plain_dots, HYPRE_Int *plain_axpys)
+{
+   hypre_amd_GMRESData *d = D(s);
+   if (fused_steps) { *fused_steps = d->fused_steps; }
+   if (plain_dots) { *plain_dots = d->plain_dots; }
+   if (plain_axpys) { *plain_axpys = d->plain_axpys; }
    return hypre_error_flag;
 }
 
-HYPRE_Int HYPRE_ParCSRGMRESSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x)
+HYPRE_Int hypre_amd_ParVectorAxpyThenInnerProd(HYPRE_Complex alpha, hypre_ParVector *x, hypre_ParVector *y, hypre_ParVector *z,
+                                               HYPRE_Real *result)
 {
-   hypre_amd_GMRESData *d = (hypre_amd_GMRESData *) solver;
-   if ((HYPRE_Int) d->p.size() != d->k_dim + 1)
+   if (!on_device(x) || !on_device(y) || !on_device(z))
    {
-      hypre_error_w_msg(HYPRE_ERROR_GENERIC, "HYPRE_ParCSRGMRESSolve: call HYPRE_ParCSRGMRESSetup after HYPRE_GMRESSetKDim");
+      hypre_error_w_msg(HYPRE_ERROR_GENERIC, "hypre_amd_ParVectorAxpyThenInnerProd: operand is not in device memory; host execution is not part of this library");
       return hypre_error_flag;
    }
-   const HYPRE_Int k_dim = d->k_dim, min_iter = d->min_iter, max_iter = d->max_iter;
-   hypre_ParVector *r = d->r, *w = d->w;
-   std::vector<hypre_ParVector *> &p = d->p;
-   const HYPRE_Real epsmac = 1.e-16;
-   std::vector<HYPRE_Real> rs((size_t) k_dim + 1, 0.0), c((size_t) k_dim, 0.0), s((size_t) k_dim, 0.0);
-   std::vector<std::vector<HYPRE_Real>> hh((size_t) k_dim + 1, std::vector<HYPRE_Real>((size_t) k_dim, 0.0));
-   HYPRE_Int i = 0, j, k, iter = 0;
-   HYPRE_Real t, gamma, r_norm, b_norm, den_norm, epsilon, ieee_check = 0., real_r_norm_old, real_r_norm_new;
-   d->converged = 0;
-   const int saved_sync = handle().sync_compute;
-   handle().sync_compute = 0;
-   verify_par_plans(A);                    // a solve never starts from a plan its matrix has moved away from
-   auto leave = [&]() { handle().sync_compute = saved_sync; maybe_sync(); return hypre_error_flag; };
-   auto precond = [&](hypre_ParVector *rhs, hypre_ParVector *sol)
+   const size_t n = (size_t) y->local_vector->size * (size_t) y->local_vector->num_vectors;
+   if ((size_t) x->local_vector->size * (size_t) x->local_vector->num_vectors != n ||
+       (size_t) z->local_vector->size * (size_t) z->local_vector->num_vectors != n)
    {
-      hypre_ParVectorSetZeros(sol);       // ClearVector (gmres.c:569): all_zeros = 1
-      if (d->precond) { d->precond(d->precond_data, A, rhs, sol); }
-      else { hypre_ParVectorCopy(rhs, sol); }
-   };
-   auto norm = [&](hypre_ParVector *v) { return std::sqrt(hypre_ParVectorInnerProd(v, v)); };
-
-   hypre_ParVectorCopy(b, p[0]);
-   hypre_ParCSRMatrixMatvec(-1.0, A, x, 1.0, p[0]);
-   b_norm = norm(b);
-   real_r_norm_old = b_norm;
-   if (b_norm != 0.) { ieee_check = b_norm / b_norm; }
-   if (ieee_check != ieee_check) { hypre_error(HYPRE_ERROR_GENERIC); return leave(); }
-   r_norm = norm(p[0]);
-   if (r_norm != 0.) { ieee_check = r_norm / r_norm; }
-   if (ieee_check != ieee_check) { hypre_error(HYPRE_ERROR_GENERIC); return leave(); }
-   den_norm = (b_norm > 0.0) ? b_norm : r_norm;
-   epsilon = std::max(d->a_tol, d->tol * den_norm);
-
-   while (iter < max_iter)
-   {
-      rs[0] = r_norm;
-      if (r_norm == 0.0)
-      {
-         d->num_iterations = iter;            // gmres.c:500-512 returns here, rel_residual_norm untouched
-         return leave();
-      }
-      if (r_norm <= epsilon && iter >= min_iter)
-      {
-         hypre_ParVectorCopy(b, r);
-         hypre_ParCSRMatrixMatvec(-1.0, A, x, 1.0, r);
-         r_norm = norm(r);
-         if (r_norm <= epsilon) { break; }
-      }
-      t = 1.0 / r_norm;
-      hypre_ParVectorScale(t, p[0]);
-      i = 0;
-      while (i < k_dim && iter < max_iter)
-      {
-         i++;
-         iter++;
-         precond(p[(size_t) i - 1], r);
-         hypre_ParCSRMatrixMatvec(1.0, A, r, 0.0, p[(size_t) i]);
-         for (j = 0; j < i; j++)
-         {
-            hh[(size_t) j][(size_t) i - 1] = hypre_ParVectorInnerProd(p[(size_t) j], p[(size_t) i]);
-            hypre_ParVectorAxpy(-hh[(size_t) j][(size_t) i - 1], p[(size_t) j], p[(size_t) i]);
-         }
-         t = norm(p[(size_t) i]);
-         hh[(size_t) i][(size_t) i - 1] = t;
-         if (t != 0.0) { t = 1.0 / t; hypre_ParVectorScale(t, p[(size_t) i]); }
-         for (j = 1; j < i; j++)
-         {
-            t = hh[(size_t) j - 1][(size_t) i - 1];
-            hh[(size_t) j - 1][(size_t) i - 1] = s[(size_t) j - 1] * hh[(size_t) j][(size_t) i - 1] + c[(size_t) j - 1] * t;
-            hh[(size_t) j][(size_t) i - 1] = -s[(size_t) j - 1] * t + c[(size_t) j - 1] * hh[(size_t) j][(size_t) i - 1];
-         }
-         t = hh[(size_t) i][(size_t) i - 1] * hh[(size_t) i][(size_t) i - 1];
-         t += hh[(size_t) i - 1][(size_t) i - 1] * hh[(size_t) i - 1][(size_t) i - 1];
-         gamma = std::sqrt(t);
-         if (gamma == 0.0) { gamma = epsmac; }
-         c[(size_t) i - 1] = hh[(size_t) i - 1][(size_t) i - 1] / gamma;
-         s[(size_t) i - 1] = hh[(size_t) i][(size_t) i - 1] / gamma;
-         rs[(size_t) i] = -hh[(size_t) i][(size_t) i - 1] * rs[(size_t) i - 1];
-         rs[(size_t) i] /= gamma;
-         rs[(size_t) i - 1] = c[(size_t) i - 1] * rs[(size_t) i - 1];
-         hh[(size_t) i - 1][(size_t) i - 1] = s[(size_t) i - 1] * hh[(size_t) i][(size_t) i - 1] + c[(size_t) i - 1] * hh[(size_t) i - 1][(size_t) i - 1];
-         r_norm = std::fabs(rs[(size_t) i]);
-         if (r_norm <= epsilon && iter >= min_iter) { break; }
-      }
-      // upper triangular solve, then the update through the preconditioner
-      rs[(size_t) i - 1] = rs[(size_t) i - 1] / hh[(size_t) i - 1][(size_t) i - 1];
-      for (k = i - 2; k >= 0; k--)
-      {
-         t = 0.0;
-         for (j = k + 1; j < i; j++) { t -= hh[(size_t) k][(size_t) j] * rs[(size_t) j]; }
-         t += rs[(size_t) k];
-         rs[(size_t) k] = t / hh[(size_t) k][(size_t) k];
-      }
-      hypre_ParVectorCopy(p[(size_t) i - 1], w);
-      hypre_ParVectorScale(rs[(size_t) i - 1], w);
-      for (j = i - 2; j >= 0; j--) { hypre_ParVectorAxpy(rs[(size_t) j], p[(size_t) j], w); }
-      precond(w, r);
-      hypre_ParVectorAxpy(1.0, r, x);
-      x->all_zeros = 0;
-      if (r_norm <= epsilon && iter >= min_iter)
-      {
-         if (d->skip_real_r_check) { d->converged = 1; break; }
-         hypre_ParVectorCopy(b, r);
-         hypre_ParCSRMatrixMatvec(-1.0, A, x, 1.0, r);
-         real_r_norm_new = r_norm = norm(r);
-         if (r_norm <= epsilon) { d->converged = 1; break; }
-         if (real_r_norm_new >= real_r_norm_old) { d->converged = 1; break; }     // gmres.c:903-912
-         hypre_ParVectorCopy(r, p[0]);
-         i = 0;
-         real_r_norm_old = real_r_norm_new;
-      }
-      // residual vector of the restart (gmres.c:930-950)
-      for (j = i; j > 0; j--)
-      {
-         rs[(size_t) j - 1] = -s[(size_t) j - 1] * rs[(size_t) j];
-         rs[(size_t) j] = c[(size_t) j - 1] * rs[(size_t) j];
-      }
-      if (i) { hypre_ParVectorAxpy(rs[(size_t) i] - 1.0, p[(size_t) i], p[(size_t) i]); }
-      for (j = i - 1; j > 0; j--) { hypre_ParVectorAxpy(rs[(size_t) j], p[(size_t) j], p[(size_t) i]); }
-      if (i)
-      {
-         hypre_ParVectorAxpy(rs[0] - 1.0, p[0], p[0]);
-         hypre_ParVectorAxpy(1.0, p[(size_t) i], p[0]);
-      }
+      hypre_error_w_msg(HYPRE_ERROR_GENERIC, "hypre_amd_ParVectorAxpyThenInnerProd: the three vectors differ in length");
+      return hypre_error_flag;
    }
-   d->num_iterations = iter;
-   d->rel_residual_norm = (b_norm > 0.0) ? r_norm / b_norm : r_norm;
-   if (iter >= max_iter && r_norm > epsilon && epsilon > 0) { hypre_error(HYPRE_ERROR_CONV); }
-   return leave();
+   *result = axpy_then_inner_prod(alpha, x, y, z);
+   return hypre_error_flag;
 }
+
+HYPRE_Int HYPRE_ParCSRFlexGMRESSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x)
+{
+   return setup(solver, A, b, x);
+}
+HYPRE_Int HYPRE_ParCSRFlexGMRESSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x)
+{
+   hypre_amd_GMRESData *d = D(solver);
+   if (stale(solver, "HYPRE_ParCSRFlexGMRESSolve: call HYPRE_ParCSRFlexGMRESSetup after HYPRE_FlexGMRESSetKDim")) { return hypre_error_flag; }
+   if (!on_device(b) || !on_device(x) || !on_device(d->r))
+   {
+      hypre_error_w_msg(HYPRE_ERROR_GENERIC, "HYPRE_ParCSRFlexGMRESSolve: operand is not in device memory; host execution is not part of this library");
+      return hypre_error_flag;
+   }
+   d->num_iterations = 0;                  // also a solve that ends at the not-a-number check reports 0 iterations here
+   return solve(solver, A, b, x);
+}
+
+// the spellings of parcsr_ls/HYPRE_parcsr_flexgmres.c and the generic Setup / Solve of krylov/HYPRE_flexgmres.c
+HYPRE_Int HYPRE_FlexGMRESSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x) { return HYPRE_ParCSRFlexGMRESSetup(s, A, b, x); }
+HYPRE_Int HYPRE_FlexGMRESSolve(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x) { return HYPRE_ParCSRFlexGMRESSolve(s, A, b, x); }
+HYPRE_Int HYPRE_ParCSRFlexGMRESSetKDim(HYPRE_Solver s, HYPRE_Int v) { return HYPRE_FlexGMRESSetKDim(s, v); }
+HYPRE_Int HYPRE_ParCSRFlexGMRESSetTol(HYPRE_Solver s, HYPRE_Real v) { return HYPRE_FlexGMRESSetTol(s, v); }
+HYPRE_Int HYPRE_ParCSRFlexGMRESSetAbsoluteTol(HYPRE_Solver s, HYPRE_Real v) { return HYPRE_FlexGMRESSetAbsoluteTol(s, v); }
+HYPRE_Int HYPRE_ParCSRFlexGMRESSetMinIter(HYPRE_Solver s, HYPRE_Int v) { return HYPRE_FlexGMRESSetMinIter(s, v); }
+HYPRE_Int HYPRE_ParCSRFlexGMRESSetMaxIter(HYPRE_Solver s, HYPRE_Int v) { return HYPRE_FlexGMRESSetMaxIter(s, v); }
+HYPRE_Int HYPRE_ParCSRFlexGMRESSetPrecond(HYPRE_Solver s, HYPRE_PtrToSolverFcn precond, HYPRE_PtrToSolverFcn precond_setup,
+                                          HYPRE_Solver precond_solver)
+{ return HYPRE_FlexGMRESSetPrecond(s, precond, precond_setup, precond_solver); }
+HYPRE_Int HYPRE_ParCSRFlexGMRESGetPrecond(HYPRE_Solver s, HYPRE_Solver *precond_data_ptr) { return HYPRE_FlexGMRESGetPrecond(s, precond_data_ptr); }
+HYPRE_Int HYPRE_ParCSRFlexGMRESSetModifyPC(HYPRE_Solver s, HYPRE_PtrToModifyPCFcn modify_pc) { return HYPRE_FlexGMRESSetModifyPC(s, modify_pc); }
+HYPRE_Int HYPRE_ParCSRFlexGMRESSetLogging(HYPRE_Solver s, HYPRE_Int v) { return HYPRE_FlexGMRESSetLogging(s, v); }
+HYPRE_Int HYPRE_ParCSRFlexGMRESSetPrintLevel(HYPRE_Solver s, HYPRE_Int v) { return HYPRE_FlexGMRESSetPrintLevel(s, v); }
+HYPRE_Int HYPRE_ParCSRFlexGMRESGetNumIterations(HYPRE_Solver s, HYPRE_Int *v) { return HYPRE_FlexGMRESGetNumIterations(s, v); }
+HYPRE_Int HYPRE_ParCSRFlexGMRESGetFinalRelativeResidualNorm(HYPRE_Solver s, HYPRE_Real *v) { return HYPRE_FlexGMRESGetFinalRelativeResidualNorm(s, v); }
 
 }  // extern "C"

@@ -539,23 +539,49 @@ def solve_ds_pcg(opt, A, db, dx, comm=0):
     return its.value, rel.value
 
 
+def _solve_gmres_family(name, opt, A, b, x, comm, amg, early=(), late=(), amg_first=False, amg_max_iter=None, check_precond=False):
+    """Create, set, Setup, Solve, read back and Destroy one HYPRE_ParCSR<name> solver (GMRES, COGMRES, FlexGMRES), in the
+    order of library calls the reference driver makes: KDim, the `early` setters, MaxIter, Tol, AbsoluteTol, the `late`
+    setters; then BoomerAMG (`amg`, tuned as a preconditioner: SetTol 0, SetMaxIter precon_cycles; before Create if
+    `amg_first`, MaxIter set once more to `amg_max_iter` if given) or the diagonal scaling preconditioner."""
+    L = B.load_library()
+    fn = lambda stem: getattr(L, "HYPRE_%s%s" % (name, stem))
+    par = lambda stem: getattr(L, "HYPRE_ParCSR%s%s" % (name, stem))
+
+    def tune_amg():
+        L.HYPRE_BoomerAMGSetTol(amg, 0.0)
+        L.HYPRE_BoomerAMGSetMaxIter(amg, opt.precon_cycles)
+    if amg is not None and amg_first:
+        tune_amg()
+    g = C.c_void_p()
+    par("Create")(comm, C.byref(g))
+    for stem, value in (("KDim", opt.k_dim),) + tuple(early) + (("MaxIter", opt.max_iter), ("Tol", opt.tol), ("AbsoluteTol", 0.0)) + tuple(late):
+        fn("Set" + stem)(g, value)
+    if amg is not None:
+        if not amg_first:
+            tune_amg()
+        if amg_max_iter is not None:
+            fn("SetMaxIter")(g, amg_max_iter)
+        fn("SetPrecond")(g, C.cast(L.HYPRE_BoomerAMGSolve, C.c_void_p), None, amg)
+    else:
+        fn("SetPrecond")(g, C.cast(L.HYPRE_ParCSRDiagScale, C.c_void_p), C.cast(L.HYPRE_ParCSRDiagScaleSetup, C.c_void_p), None)
+    if check_precond:
+        gotten = C.c_void_p()
+        fn("GetPrecond")(g, C.byref(gotten))
+        if gotten.value != (amg.value if amg is not None else None):
+            raise SystemExit("HYPRE_%sGetPrecond got bad precond" % name)
+    par("Setup")(g, A, b, x)
+    par("Solve")(g, A, b, x)
+    its, rel = C.c_int(), C.c_double()
+    fn("GetNumIterations")(g, C.byref(its))
+    fn("GetFinalRelativeResidualNorm")(g, C.byref(rel))
+    par("Destroy")(g)
+    return its.value, rel.value
+
+
 def solve_ds_gmres(opt, A, db, dx, comm=0):
     """test/ij.c:6710-6727, 6932-6942: GMRES(k) with the diagonal scaling preconditioner (solver 4); multivectors as above."""
-    L = B.load_library()
-    g = C.c_void_p()
-    L.HYPRE_ParCSRGMRESCreate(comm, C.byref(g))
-    L.HYPRE_GMRESSetKDim(g, opt.k_dim)
-    L.HYPRE_GMRESSetMaxIter(g, opt.max_iter)
-    L.HYPRE_GMRESSetTol(g, opt.tol)
-    L.HYPRE_GMRESSetAbsoluteTol(g, 0.0)
-    L.HYPRE_GMRESSetPrecond(g, C.cast(L.HYPRE_ParCSRDiagScale, C.c_void_p), C.cast(L.HYPRE_ParCSRDiagScaleSetup, C.c_void_p), None)
-    L.HYPRE_ParCSRGMRESSetup(g, A, db, dx)
-    L.HYPRE_ParCSRGMRESSolve(g, A, db, dx)
-    its, rel = C.c_int(), C.c_double()
-    L.HYPRE_GMRESGetNumIterations(g, C.byref(its))
-    L.HYPRE_GMRESGetFinalRelativeResidualNorm(g, C.byref(rel))
-    L.HYPRE_ParCSRGMRESDestroy(g)
-    return its.value, rel.value
+    return _solve_gmres_family("GMRES", opt, A, db, dx, comm, None)
 
 
 def run_ds_pcg(opt, A, comm=0, rank=0, allreduce=None, out=None):
@@ -592,86 +618,23 @@ def run_ds_pcg(opt, A, comm=0, rank=0, allreduce=None, out=None):
 
 def solve_gmres(opt, amg, A, b, x, comm=0):
     """test/ij.c:6715-6790, 6919-6925, 7190-7215: AMG-GMRES (solver 3)."""
-    L = B.load_library()
-    L.HYPRE_BoomerAMGSetTol(amg, 0.0)
-    L.HYPRE_BoomerAMGSetMaxIter(amg, opt.precon_cycles)
-    g = C.c_void_p()
-    L.HYPRE_ParCSRGMRESCreate(comm, C.byref(g))
-    L.HYPRE_GMRESSetKDim(g, opt.k_dim)
-    L.HYPRE_GMRESSetMaxIter(g, opt.max_iter)
-    L.HYPRE_GMRESSetTol(g, opt.tol)
-    L.HYPRE_GMRESSetAbsoluteTol(g, 0.0)
-    L.HYPRE_GMRESSetPrecond(g, C.cast(L.HYPRE_BoomerAMGSolve, C.c_void_p), None, amg)
-    L.HYPRE_ParCSRGMRESSetup(g, A, b, x)
-    L.HYPRE_ParCSRGMRESSolve(g, A, b, x)
-    its, rel = C.c_int(), C.c_double()
-    L.HYPRE_GMRESGetNumIterations(g, C.byref(its))
-    L.HYPRE_GMRESGetFinalRelativeResidualNorm(g, C.byref(rel))
-    L.HYPRE_ParCSRGMRESDestroy(g)
-    return its.value, rel.value
+    return _solve_gmres_family("GMRES", opt, A, b, x, comm, amg, amg_first=True)
 
 
 def solve_cogmres(opt, A, b, x, comm=0, amg=None):
     """test/ij.c:8426-8440, 8583-8598, 8710-8722: COGMRES behind BoomerAMG (solver 16, `amg` the set-up hierarchy) or behind the
     diagonal scaling preconditioner (solver 17)."""
-    L = B.load_library()
-    g = C.c_void_p()
-    L.HYPRE_ParCSRCOGMRESCreate(comm, C.byref(g))
-    L.HYPRE_COGMRESSetKDim(g, opt.k_dim)
-    L.HYPRE_COGMRESSetUnroll(g, opt.unroll)
-    L.HYPRE_COGMRESSetCGS(g, opt.cgs)
-    L.HYPRE_COGMRESSetMaxIter(g, opt.max_iter)
-    L.HYPRE_COGMRESSetTol(g, opt.tol)
-    L.HYPRE_COGMRESSetAbsoluteTol(g, 0.0)
-    L.HYPRE_COGMRESSetLogging(g, 3)            # ioutdat (test/ij.c:686); inert here
-    L.HYPRE_COGMRESSetPrintLevel(g, 3)
-    if amg is not None:
-        L.HYPRE_BoomerAMGSetTol(amg, 0.0)
-        L.HYPRE_BoomerAMGSetMaxIter(amg, opt.precon_cycles)
-        L.HYPRE_COGMRESSetMaxIter(g, opt.mg_max_iter)
-        L.HYPRE_COGMRESSetPrecond(g, C.cast(L.HYPRE_BoomerAMGSolve, C.c_void_p), None, amg)
-    else:
-        L.HYPRE_COGMRESSetPrecond(g, C.cast(L.HYPRE_ParCSRDiagScale, C.c_void_p), C.cast(L.HYPRE_ParCSRDiagScaleSetup, C.c_void_p), None)
-    L.HYPRE_ParCSRCOGMRESSetup(g, A, b, x)
-    L.HYPRE_ParCSRCOGMRESSolve(g, A, b, x)
-    its, rel = C.c_int(), C.c_double()
-    L.HYPRE_COGMRESGetNumIterations(g, C.byref(its))
-    L.HYPRE_COGMRESGetFinalRelativeResidualNorm(g, C.byref(rel))
-    L.HYPRE_ParCSRCOGMRESDestroy(g)
-    return its.value, rel.value
+    return _solve_gmres_family("COGMRES", opt, A, b, x, comm, amg, early=(("Unroll", opt.unroll), ("CGS", opt.cgs)),
+                               late=(("Logging", 3), ("PrintLevel", 3)),            # ioutdat (test/ij.c:686); inert here
+                               amg_max_iter=opt.mg_max_iter)
 
 
 def solve_flexgmres(opt, A, b, x, comm=0, amg=None):
     """test/ij.c:7565-7578, 7720-7724, 7892-7943: FlexGMRES behind BoomerAMG (solver 61, `amg` the set-up hierarchy) or behind the
     diagonal scaling preconditioner (solver 60); b and x may be multivectors (-nc N).  modify_pc stays the default, which
     changes nothing."""
-    L = B.load_library()
-    g = C.c_void_p()
-    L.HYPRE_ParCSRFlexGMRESCreate(comm, C.byref(g))
-    L.HYPRE_FlexGMRESSetKDim(g, opt.k_dim)
-    L.HYPRE_FlexGMRESSetMaxIter(g, opt.max_iter)
-    L.HYPRE_FlexGMRESSetTol(g, opt.tol)
-    L.HYPRE_FlexGMRESSetAbsoluteTol(g, 0.0)
-    L.HYPRE_FlexGMRESSetLogging(g, 1)
-    L.HYPRE_FlexGMRESSetPrintLevel(g, 3)         # ioutdat (test/ij.c:686); inert here
-    if amg is not None:
-        L.HYPRE_BoomerAMGSetTol(amg, 0.0)
-        L.HYPRE_BoomerAMGSetMaxIter(amg, opt.precon_cycles)
-        L.HYPRE_FlexGMRESSetMaxIter(g, opt.mg_max_iter)
-        L.HYPRE_FlexGMRESSetPrecond(g, C.cast(L.HYPRE_BoomerAMGSolve, C.c_void_p), None, amg)
-    else:
-        L.HYPRE_FlexGMRESSetPrecond(g, C.cast(L.HYPRE_ParCSRDiagScale, C.c_void_p), C.cast(L.HYPRE_ParCSRDiagScaleSetup, C.c_void_p), None)
-    gotten = C.c_void_p()
-    L.HYPRE_FlexGMRESGetPrecond(g, C.byref(gotten))
-    if gotten.value != (amg.value if amg is not None else None):
-        raise SystemExit("HYPRE_FlexGMRESGetPrecond got bad precond")
-    L.HYPRE_ParCSRFlexGMRESSetup(g, A, b, x)
-    L.HYPRE_ParCSRFlexGMRESSolve(g, A, b, x)
-    its, rel = C.c_int(), C.c_double()
-    L.HYPRE_FlexGMRESGetNumIterations(g, C.byref(its))
-    L.HYPRE_FlexGMRESGetFinalRelativeResidualNorm(g, C.byref(rel))
-    L.HYPRE_ParCSRFlexGMRESDestroy(g)
-    return its.value, rel.value
+    return _solve_gmres_family("FlexGMRES", opt, A, b, x, comm, amg, late=(("Logging", 1), ("PrintLevel", 3)),   # ioutdat; inert here
+                               amg_max_iter=opt.mg_max_iter, check_precond=True)
 
 
 def main(argv=None):
