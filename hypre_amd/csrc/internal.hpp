@@ -368,6 +368,10 @@ void launch_dot_final(const double *partial, int m, double *d_out, hipStream_t s
 // one modified Gram-Schmidt step in one pass (mass_kernels.hip): y += a x, then d_out[0] = <z, y>; z may be y.  The bits
 // of launch_axpy(a, x, y) followed by launch_dot(z, y).
 void launch_axpy_dot(double a, const double *x, double *y, const double *z, size_t n, double *d_out, hipStream_t s);
+// the end of an LGMRES restart cycle (mass_kernels.hip): y = x with d_out[0] = <x, x>, the bits of launch_copy then
+// launch_dot(y, y); z = a (x - y), the bits of launch_copy(z, x), launch_scale(z, -1), launch_axpy(1, y, z), launch_scale(z, -a)
+void launch_copy_norm2(const double *x, double *y, size_t n, double *d_out, hipStream_t s);
+void launch_scaled_diff(double a, const double *x, const double *y, double *z, size_t n, hipStream_t s);
 // batched BLAS-1 (mass_kernels.hip): k vectors in chunks of MASS_CHUNK, every vector read once per chunk.  The dots
 // return where their k (2 k: <x, z_j> first, <y, z_j> behind) sums lie in device scratch, valid until the next
 // reduction; sum j has the bits of launch_dot(x, y_j), the update those of k launch_axpy calls in order.

@@ -174,6 +174,45 @@ void mgs_step_kernel(double a, const double *x, double *y, const double *z, size
    if (threadIdx.x == 0) { partial[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]); }
 }
 
+// The end of an LGMRES restart cycle (par_gmres.cpp, lgmres_core.hpp), each of the two in one pass.
+//
+// y = x and this workgroup's share of <x, x>: the copy of copy_kernel, and the partials dot_partial_kernel leaves for
+// <y, y> of the copy (the grid of a dot product, the same trips, the same per-pair term, the same fold).
+__global__ __launch_bounds__(256)
+void copy_norm2_kernel(const double *__restrict__ x, double *__restrict__ y, size_t n, double *__restrict__ partial)
+{
+   __shared__ double wsum[4];
+   double acc = 0.0;
+   VEC_LOOP_BEGIN
+      const double2 xv = reinterpret_cast<const double2 *>(x)[i];
+      reinterpret_cast<double2 *>(y)[i] = xv;
+      acc += dot_pair(xv, xv);
+   VEC_LOOP_END
+   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
+   {
+      const double t = x[n - 1];
+      y[n - 1] = t;
+      acc = dot_last(t, t, acc);
+   }
+   acc = wave_sum(acc);
+   if ((threadIdx.x & 63) == 0) { wsum[threadIdx.x >> 6] = acc; }
+   __syncthreads();
+   if (threadIdx.x == 0) { partial[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]); }
+}
+
+// z = (y - x) na, two roundings spelled out so that nothing is contracted: what copy (z = x), scale by -1, axpy with
+// coefficient 1 (z = y - x, one rounding whether or not the product with 1 is fused) and scale by na leave.  The caller
+// hands na = -a for z = a (x - y); the difference is taken as y - x so that equal elements give the zero of that sequence.
+__global__ void scaled_diff_kernel(double na, const double *__restrict__ x, const double *__restrict__ y, double *__restrict__ z, size_t n)
+{
+   VEC_LOOP_BEGIN
+      const double2 xv = reinterpret_cast<const double2 *>(x)[i];
+      const double2 yv = reinterpret_cast<const double2 *>(y)[i];
+      reinterpret_cast<double2 *>(z)[i] = make_double2(__dmul_rn(__dsub_rn(yv.x, xv.x), na), __dmul_rn(__dsub_rn(yv.y, xv.y), na));
+   VEC_LOOP_END
+   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) { z[n - 1] = __dmul_rn(__dsub_rn(y[n - 1], x[n - 1]), na); }
+}
+
 // ---------------------------------------------------------------------------
 // launchers: k vectors in chunks of MASS_CHUNK, one kernel instance per chunk length
 // ---------------------------------------------------------------------------
@@ -288,6 +327,25 @@ void launch_axpy_dot(double a, const double *x, double *y, const double *z, size
    if (self) { hipLaunchKernelGGL(mgs_step_kernel<true>, dim3(nb), dim3(256), 0, s, a, x, y, z, n, partial); }
    else { hipLaunchKernelGGL(mgs_step_kernel<false>, dim3(nb), dim3(256), 0, s, a, x, y, z, n, partial); }
    launch_dot_final(partial, nb, d_out, s);
+}
+
+// y = x and d_out[0] = <x, x> (this rank's part): the bits of launch_copy(y, x) followed by launch_dot(y, y), in 16 n
+// bytes instead of 32 n
+void launch_copy_norm2(const double *x, double *y, size_t n, double *d_out, hipStream_t s)
+{
+   account_bytes(16.0 * n);
+   const int nb = dot_grid(n);
+   double *partial = reduce_scratch(DOT_BLOCKS + 16) + 16;
+   hipLaunchKernelGGL(copy_norm2_kernel, dim3(nb), dim3(256), 0, s, x, y, n, partial);
+   launch_dot_final(partial, nb, d_out, s);
+}
+
+// z = a (x - y); z is neither x nor y.  The bits of launch_copy(z, x), launch_scale(z, -1), launch_axpy(1, y, z),
+// launch_scale(z, -a), in 24 n bytes instead of 72 n
+void launch_scaled_diff(double a, const double *x, const double *y, double *z, size_t n, hipStream_t s)
+{
+   account_bytes(24.0 * n);
+   if (n) { hipLaunchKernelGGL(scaled_diff_kernel, dim3(vec_grid(n)), dim3(256), 0, s, -a, x, y, z, n); }
 }
 
 void preload_mass_kernels() { hipFuncAttributes at; (void) hipFuncGetAttributes(&at, (const void *) mass_dot_final_kernel); (void) hipGetLastError(); }

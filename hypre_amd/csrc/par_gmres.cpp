@@ -1,12 +1,13 @@
-// hypre_amd — the three right-preconditioned restarted GMRES solvers on ParVectors on the device:
+// hypre_amd — the four right-preconditioned restarted GMRES solvers on ParVectors on the device:
 //    GMRES      HYPRE_ParCSRGMRES*  / HYPRE_GMRES*       `ij -solver 3 | 4`     krylov/gmres.c, parcsr_ls/HYPRE_parcsr_gmres.c
 //    COGMRES    HYPRE_ParCSRCOGMRES* / HYPRE_COGMRES*    `ij -solver 16 | 17`   krylov/cogmres.c, parcsr_ls/HYPRE_parcsr_cogmres.c
 //    FlexGMRES  HYPRE_ParCSRFlexGMRES* / HYPRE_FlexGMRES* `ij -solver 60 | 61`  krylov/flexgmres.c, parcsr_ls/HYPRE_parcsr_flexgmres.c
-// The iteration itself (Hessenberg matrix, Givens rotations, every decision) is gmres_core.hpp; this file gives it the
-// vectors, every inner product ending in one scalar read-back, and the entry points.  The three differ in the GMRESParams
-// their Create fills in (the table is in DESIGN.md) and in two refusals: COGMRES Setup takes no multivectors, FlexGMRES
-// Solve no host operands.  The relative-change and convergence-factor exits of the reference (rel_change, cf_tol) are not
-// carried.
+//    LGMRES     HYPRE_ParCSRLGMRES* / HYPRE_LGMRES*       `ij -solver 50 | 51`  krylov/lgmres.c, parcsr_ls/HYPRE_parcsr_lgmres.c
+// The iteration itself (Hessenberg matrix, Givens rotations, every decision) is gmres_core.hpp, for LGMRES its sibling
+// lgmres_core.hpp; this file gives it the vectors, every inner product ending in one scalar read-back, and the entry
+// points.  The first three differ in the GMRESParams their Create fills in (the table is in DESIGN.md) and in two
+// refusals: COGMRES Setup takes no multivectors, FlexGMRES Solve no host operands (LGMRES Solve neither).  The
+// relative-change and convergence-factor exits of the reference (rel_change, cf_tol) are not carried, by none of the four.
 //
 // Modified Gram-Schmidt, fused (the FlexGMRES default): step i is one hypre_ParVectorInnerProd and i launches of
 // launch_axpy_dot, each subtracting the projection on p[j] and leaving <p[j + 1], p[i]> (the last one |p[i]|^2) in the
@@ -14,9 +15,17 @@
 // in 2 i + 1.  Same order of operations and same roundings, so a solve has the same bits either way
 // (hypre_amd_FlexGMRESSetFusedOrthogonalization).  Classical Gram-Schmidt (COGMRES) reads every basis vector twice per
 // step and ends in two read-backs (the batch and the norm) where the modified one needs i + 1.
+//
+// LGMRES, fused (its default, hypre_amd_LGMRESSetFusedUpdates): the Gram-Schmidt steps as above; the correction of a
+// cycle is one scaled copy and one hypre_ParVectorMassAxpy over the Arnoldi and augmentation terms; what ends a cycle that
+// restarts (keep the correction, rebuild r0, normalise the new augmentation vector, form A z = (r0 - r_m) / |w|) is
+// launch_copy_norm2, two launch_scale_copy and launch_scaled_diff: 4 launches and 72 bytes per element where the
+// reference's ten Copy / Scale / InnerProd / Axpy calls move 168.  The same bits either way.
 #include "amg_internal.hpp"
-#include "gmres_core.hpp"
+#include "lgmres_core.hpp"
 #include <cstring>
+#include <initializer_list>
+#include <string>
 #include <vector>
 
 using namespace hamd;
@@ -34,6 +43,10 @@ struct hypre_amd_GMRESData
    HYPRE_Int num_iterations = 0, converged = 0;
    HYPRE_Real rel_residual_norm = 0.0;
    HYPRE_Int fused_steps = 0, plain_dots = 0, plain_axpys = 0;
+   // LGMRES only: aug_dim < 0 marks the other three
+   HYPRE_Int aug_dim = -1, approx_constant = 1, fused_updates_on = 1;
+   std::vector<hypre_ParVector *> aug_vecs, a_aug_vecs;   // aug_dim + 1 (the last a temporary) and aug_dim, as lgmres.c:270-278
+   HYPRE_Int fused_updates = 0, plain_updates = 0;
 };
 
 namespace {
@@ -45,7 +58,9 @@ void free_vectors(hypre_amd_GMRESData *d)
    d->r = d->w = nullptr;
    for (hypre_ParVector *v : d->p) { hypre_ParVectorDestroy(v); }
    for (hypre_ParVector *v : d->pre_vecs) { hypre_ParVectorDestroy(v); }
-   d->p.clear(); d->pre_vecs.clear();
+   for (hypre_ParVector *v : d->aug_vecs) { hypre_ParVectorDestroy(v); }
+   for (hypre_ParVector *v : d->a_aug_vecs) { hypre_ParVectorDestroy(v); }
+   d->p.clear(); d->pre_vecs.clear(); d->aug_vecs.clear(); d->a_aug_vecs.clear();
 }
 
 HYPRE_Int create(MPI_Comm comm, HYPRE_Solver *solver, const GMRESParams &prm)
@@ -97,6 +112,11 @@ HYPRE_Int setup(HYPRE_Solver solver, hypre_ParCSRMatrix *A, hypre_ParVector *b, 
       d->p.push_back(mk());
       if (d->prm.flexible) { d->pre_vecs.push_back(mk()); }
    }
+   for (HYPRE_Int i = 0; i <= d->aug_dim; i++)
+   {
+      d->aug_vecs.push_back(mk());
+      if (i < d->aug_dim) { d->a_aug_vecs.push_back(mk()); }
+   }
    if (d->precond_setup) { d->precond_setup(d->precond_data, A, b, x); }
    return hypre_error_flag;
 }
@@ -112,7 +132,34 @@ HYPRE_Real axpy_then_inner_prod(HYPRE_Complex alpha, hypre_ParVector *x, hypre_P
    return r;
 }
 
-// the vector operations gmres_iterate asks for
+size_t flat_length(hypre_ParVector *v) { return (size_t) v->local_vector->size * (size_t) v->local_vector->num_vectors; }
+
+// y = a x: the bits of hypre_ParVectorCopy(x, y) followed by hypre_ParVectorScale(a, y), whose shortcut at a == 0 (set
+// to zero, whatever x holds) is kept; at a == 1 the product is x itself
+void scaled_copy_of(HYPRE_Complex a, hypre_ParVector *x, hypre_ParVector *y)
+{
+   if (a == 0.0) { launch_set(y->local_vector->data, 0.0, flat_length(y), stream()); }
+   else { launch_scale_copy(a, x->local_vector->data, y->local_vector->data, flat_length(y), stream()); }
+}
+
+// y = x, then <x, x> over all ranks: the fused launch and the reduction of hypre_ParVectorInnerProd(y, y)
+HYPRE_Real copy_then_inner_prod(hypre_ParVector *x, hypre_ParVector *y)
+{
+   double *d_out = reduce_scratch(2048);
+   launch_copy_norm2(x->local_vector->data, y->local_vector->data, flat_length(y), d_out, stream());
+   double r = 0.0;
+   dev_global_sums(y->comm, d_out, 1, &r);
+   return r;
+}
+
+// z = a (x - y): the bits of Copy(x, z), Scale(-1, z), Axpy(1, y, z), Scale(-a, z), the last one's shortcut at a == 0 kept
+void scaled_difference(HYPRE_Complex a, hypre_ParVector *x, hypre_ParVector *y, hypre_ParVector *z)
+{
+   if (a == 0.0) { launch_set(z->local_vector->data, 0.0, flat_length(z), stream()); }
+   else { launch_scaled_diff(a, x->local_vector->data, y->local_vector->data, z->local_vector->data, flat_length(z), stream()); }
+}
+
+// the vector operations gmres_iterate and lgmres_iterate ask for
 struct ParOps
 {
    hypre_amd_GMRESData *d;
@@ -135,6 +182,9 @@ struct ParOps
       else { hypre_ParVectorCopy(rhs, sol); }
    }
    void solution_changed(hypre_ParVector *x) { x->all_zeros = 0; }
+   void scaled_copy(double a, hypre_ParVector *x, hypre_ParVector *y) { scaled_copy_of(a, x, y); }
+   double copy_norm2(hypre_ParVector *x, hypre_ParVector *y) { return copy_then_inner_prod(x, y); }
+   void scaled_diff(double a, hypre_ParVector *x, hypre_ParVector *y, hypre_ParVector *z) { scaled_difference(a, x, y, z); }
 };
 
 // the work vectors are those of another k_dim: msg is the entry point's "...Solve: call ...Setup after ...SetKDim"
@@ -145,16 +195,18 @@ bool stale(HYPRE_Solver solver, const char *msg)
    return true;
 }
 
-HYPRE_Int solve(HYPRE_Solver solver, hypre_ParCSRMatrix *A, hypre_ParVector *b, hypre_ParVector *x)
+// one solve: `iterate` runs the loop on the ParOps it is given; the synchronisation after every vector call is off
+// meanwhile, and what the loop reports is stored for the getters and turned into the error flags of the reference
+template <class Iterate>
+HYPRE_Int solve_with(hypre_amd_GMRESData *d, hypre_ParCSRMatrix *A, Iterate iterate)
 {
-   hypre_amd_GMRESData *d = D(solver);
    d->converged = 0;
    d->fused_steps = d->plain_dots = d->plain_axpys = 0;
    const int saved_sync = handle().sync_compute;
    handle().sync_compute = 0;
    verify_par_plans(A);                    // a solve never starts from a plan its matrix has moved away from
    ParOps ops{d, A};
-   const GMRESResult res = gmres_iterate<hypre_ParVector *>(d->prm, ops, b, x, d->r, d->w, d->p.data(), d->pre_vecs.data());
+   const GMRESResult res = iterate(ops);
    if (res.iterations_set) { d->num_iterations = res.iterations; }
    d->converged = res.converged;
    if (res.norm_set) { d->rel_residual_norm = res.rel_residual_norm; }
@@ -164,6 +216,12 @@ HYPRE_Int solve(HYPRE_Solver solver, hypre_ParCSRMatrix *A, hypre_ParVector *b, 
    handle().sync_compute = saved_sync;
    maybe_sync();
    return hypre_error_flag;
+}
+
+HYPRE_Int solve(HYPRE_Solver solver, hypre_ParCSRMatrix *A, hypre_ParVector *b, hypre_ParVector *x)
+{
+   hypre_amd_GMRESData *d = D(solver);
+   return solve_with(d, A, [&](ParOps &ops) { return gmres_iterate<hypre_ParVector *>(d->prm, ops, b, x, d->r, d->w, d->p.data(), d->pre_vecs.data()); });
 }
 }  // namespace
 
@@ -355,5 +413,161 @@ HYPRE_Int HYPRE_ParCSRFlexGMRESSetLogging(HYPRE_Solver s, HYPRE_Int v) { return 
 HYPRE_Int HYPRE_ParCSRFlexGMRESSetPrintLevel(HYPRE_Solver s, HYPRE_Int v) { return HYPRE_FlexGMRESSetPrintLevel(s, v); }
 HYPRE_Int HYPRE_ParCSRFlexGMRESGetNumIterations(HYPRE_Solver s, HYPRE_Int *v) { return HYPRE_FlexGMRESGetNumIterations(s, v); }
 HYPRE_Int HYPRE_ParCSRFlexGMRESGetFinalRelativeResidualNorm(HYPRE_Solver s, HYPRE_Real *v) { return HYPRE_FlexGMRESGetFinalRelativeResidualNorm(s, v); }
+
+// ---- LGMRES: defaults of hypre_LGMRESCreate (lgmres.c:83-105): k_dim 20, aug_dim 2, approx_constant 1, tol 1e-6,
+// a_tol 0, min_iter 0, max_iter 1000; the iteration is lgmres_iterate, fused
+HYPRE_Int HYPRE_ParCSRLGMRESCreate(MPI_Comm comm, HYPRE_Solver *solver)
+{
+   GMRESParams prm;
+   prm.k_dim = 20;
+   create(comm, solver, prm);
+   D(*solver)->aug_dim = 2;
+   return hypre_error_flag;
+}
+HYPRE_Int HYPRE_ParCSRLGMRESDestroy(HYPRE_Solver solver) { return destroy(solver); }
+HYPRE_Int HYPRE_LGMRESSetKDim(HYPRE_Solver s, HYPRE_Int v) { return set_k_dim(s, v); }
+// at least 0 and at most k_dim - 1, the k_dim in force at this call (lgmres.c:970-986)
+HYPRE_Int HYPRE_LGMRESSetAugDim(HYPRE_Solver s, HYPRE_Int v)
+{
+   D(s)->aug_dim = std::max(0, std::min(v, D(s)->prm.k_dim - 1));
+   return hypre_error_flag;
+}
+HYPRE_Int HYPRE_LGMRESGetAugDim(HYPRE_Solver s, HYPRE_Int *v) { *v = D(s)->aug_dim; return hypre_error_flag; }
+HYPRE_Int HYPRE_LGMRESSetTol(HYPRE_Solver s, HYPRE_Real v) { D(s)->prm.tol = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_LGMRESSetAbsoluteTol(HYPRE_Solver s, HYPRE_Real v) { D(s)->prm.a_tol = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_LGMRESSetMinIter(HYPRE_Solver s, HYPRE_Int v) { D(s)->prm.min_iter = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_LGMRESSetMaxIter(HYPRE_Solver s, HYPRE_Int v) { D(s)->prm.max_iter = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_LGMRESSetPrecond(HYPRE_Solver s, HYPRE_PtrToSolverFcn precond, HYPRE_PtrToSolverFcn precond_setup,
+                                 HYPRE_Solver precond_solver)
+{ return set_precond(s, precond, precond_setup, precond_solver); }
+HYPRE_Int HYPRE_LGMRESGetPrecond(HYPRE_Solver s, HYPRE_Solver *precond_data_ptr) { *precond_data_ptr = D(s)->precond_data; return hypre_error_flag; }
+HYPRE_Int HYPRE_LGMRESSetLogging(HYPRE_Solver s, HYPRE_Int v) { (void) s; (void) v; return hypre_error_flag; }       // accepted, inert
+HYPRE_Int HYPRE_LGMRESSetPrintLevel(HYPRE_Solver s, HYPRE_Int v) { (void) s; (void) v; return hypre_error_flag; }
+HYPRE_Int HYPRE_LGMRESGetNumIterations(HYPRE_Solver s, HYPRE_Int *v) { *v = D(s)->num_iterations; return hypre_error_flag; }
+HYPRE_Int HYPRE_LGMRESGetFinalRelativeResidualNorm(HYPRE_Solver s, HYPRE_Real *v) { *v = D(s)->rel_residual_norm; return hypre_error_flag; }
+HYPRE_Int HYPRE_LGMRESGetConverged(HYPRE_Solver s, HYPRE_Int *v) { *v = D(s)->converged; return hypre_error_flag; }
+// the work vector that holds b - A x after a solve that checked it (lgmres.c:207-213); NULL before Setup
+HYPRE_Int HYPRE_LGMRESGetResidual(HYPRE_Solver s, void *residual) { *(hypre_ParVector **) residual = D(s)->r; return hypre_error_flag; }
+
+HYPRE_Int hypre_amd_LGMRESSetApproxConstant(HYPRE_Solver s, HYPRE_Int on)
+{
+   if (on != 0 && on != 1) { hypre_error_in_arg(2); return hypre_error_flag; }
+   D(s)->approx_constant = on;
+   return hypre_error_flag;
+}
+HYPRE_Int hypre_amd_LGMRESSetFusedUpdates(HYPRE_Solver s, HYPRE_Int on)
+{
+   if (on != 0 && on != 1) { hypre_error_in_arg(2); return hypre_error_flag; }
+   D(s)->fused_updates_on = on;
+   return hypre_error_flag;
+}
+HYPRE_Int hypre_amd_LGMRESGetLaunchStats(HYPRE_Solver s, HYPRE_Int *fused_steps, HYPRE_Int *plain_dots, HYPRE_Int *plain_axpys,
+                                         HYPRE_Int *fused_updates, HYPRE_Int *plain_updates)
+{
+   hypre_amd_GMRESData *d = D(s);
+   if (fused_updates) { *fused_updates = d->fused_updates; }
+   if (plain_updates) { *plain_updates = d->plain_updates; }
+   return hypre_amd_FlexGMRESGetLaunchStats(s, fused_steps, plain_dots, plain_axpys);
+}
+
+HYPRE_Int HYPRE_ParCSRLGMRESSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x)
+{
+   return setup(solver, A, b, x);
+}
+HYPRE_Int HYPRE_ParCSRLGMRESSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x)
+{
+   hypre_amd_GMRESData *d = D(solver);
+   if (d->aug_dim > d->prm.k_dim - 1)
+   {
+      // SetAugDim clamps against the k_dim of its day; a smaller k_dim set afterwards would leave a cycle no Arnoldi step
+      hypre_error_w_msg(HYPRE_ERROR_GENERIC, "HYPRE_ParCSRLGMRESSolve: aug_dim exceeds k_dim - 1; call HYPRE_LGMRESSetAugDim after HYPRE_LGMRESSetKDim");
+      return hypre_error_flag;
+   }
+   if (stale(solver, "HYPRE_ParCSRLGMRESSolve: call HYPRE_ParCSRLGMRESSetup after HYPRE_LGMRESSetKDim")) { return hypre_error_flag; }
+   if ((HYPRE_Int) d->aug_vecs.size() != d->aug_dim + 1)
+   {
+      hypre_error_w_msg(HYPRE_ERROR_GENERIC, "HYPRE_ParCSRLGMRESSolve: call HYPRE_ParCSRLGMRESSetup after HYPRE_LGMRESSetAugDim");
+      return hypre_error_flag;
+   }
+   if (!on_device(b) || !on_device(x) || !on_device(d->r))
+   {
+      hypre_error_w_msg(HYPRE_ERROR_GENERIC, "HYPRE_ParCSRLGMRESSolve: operand is not in device memory; host execution is not part of this library");
+      return hypre_error_flag;
+   }
+   LGMRESParams prm;
+   prm.k_dim = d->prm.k_dim; prm.aug_dim = d->aug_dim; prm.approx_constant = d->approx_constant;
+   prm.min_iter = d->prm.min_iter; prm.max_iter = d->prm.max_iter; prm.tol = d->prm.tol; prm.a_tol = d->prm.a_tol;
+   prm.fused = d->fused_updates_on != 0;
+   d->fused_updates = d->plain_updates = 0;
+   return solve_with(d, A, [&](ParOps &ops) {
+      const LGMRESResult res = lgmres_iterate<hypre_ParVector *>(prm, ops, b, x, d->r, d->w, d->p.data(), d->aug_vecs.data(), d->a_aug_vecs.data());
+      d->fused_updates = (HYPRE_Int) res.fused_updates; d->plain_updates = (HYPRE_Int) res.plain_updates;
+      return res;
+   });
+}
+
+// the spellings of parcsr_ls/HYPRE_parcsr_lgmres.c and the generic Setup / Solve of krylov/HYPRE_lgmres.c
+HYPRE_Int HYPRE_LGMRESSetup(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x) { return HYPRE_ParCSRLGMRESSetup(s, A, b, x); }
+HYPRE_Int HYPRE_LGMRESSolve(HYPRE_Solver s, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x) { return HYPRE_ParCSRLGMRESSolve(s, A, b, x); }
+HYPRE_Int HYPRE_ParCSRLGMRESSetKDim(HYPRE_Solver s, HYPRE_Int v) { return HYPRE_LGMRESSetKDim(s, v); }
+HYPRE_Int HYPRE_ParCSRLGMRESSetAugDim(HYPRE_Solver s, HYPRE_Int v) { return HYPRE_LGMRESSetAugDim(s, v); }
+HYPRE_Int HYPRE_ParCSRLGMRESSetTol(HYPRE_Solver s, HYPRE_Real v) { return HYPRE_LGMRESSetTol(s, v); }
+HYPRE_Int HYPRE_ParCSRLGMRESSetAbsoluteTol(HYPRE_Solver s, HYPRE_Real v) { return HYPRE_LGMRESSetAbsoluteTol(s, v); }
+HYPRE_Int HYPRE_ParCSRLGMRESSetMinIter(HYPRE_Solver s, HYPRE_Int v) { return HYPRE_LGMRESSetMinIter(s, v); }
+HYPRE_Int HYPRE_ParCSRLGMRESSetMaxIter(HYPRE_Solver s, HYPRE_Int v) { return HYPRE_LGMRESSetMaxIter(s, v); }
+HYPRE_Int HYPRE_ParCSRLGMRESSetPrecond(HYPRE_Solver s, HYPRE_PtrToSolverFcn precond, HYPRE_PtrToSolverFcn precond_setup,
+                                       HYPRE_Solver precond_solver)
+{ return HYPRE_LGMRESSetPrecond(s, precond, precond_setup, precond_solver); }
+HYPRE_Int HYPRE_ParCSRLGMRESGetPrecond(HYPRE_Solver s, HYPRE_Solver *precond_data_ptr) { return HYPRE_LGMRESGetPrecond(s, precond_data_ptr); }
+HYPRE_Int HYPRE_ParCSRLGMRESSetLogging(HYPRE_Solver s, HYPRE_Int v) { return HYPRE_LGMRESSetLogging(s, v); }
+HYPRE_Int HYPRE_ParCSRLGMRESSetPrintLevel(HYPRE_Solver s, HYPRE_Int v) { return HYPRE_LGMRESSetPrintLevel(s, v); }
+HYPRE_Int HYPRE_ParCSRLGMRESGetNumIterations(HYPRE_Solver s, HYPRE_Int *v) { return HYPRE_LGMRESGetNumIterations(s, v); }
+HYPRE_Int HYPRE_ParCSRLGMRESGetFinalRelativeResidualNorm(HYPRE_Solver s, HYPRE_Real *v) { return HYPRE_LGMRESGetFinalRelativeResidualNorm(s, v); }
+HYPRE_Int HYPRE_ParCSRLGMRESGetResidual(HYPRE_Solver s, HYPRE_ParVector *residual) { return HYPRE_LGMRESGetResidual(s, residual); }
+
+// the three fused vector operations of LGMRES on their own: each has the bits of the library calls it replaces
+namespace {
+bool same_device_length(const char *who, std::initializer_list<hypre_ParVector *> vs)
+{
+   const size_t n = flat_length(*vs.begin());
+   for (hypre_ParVector *v : vs)
+   {
+      if (!on_device(v))
+      {
+         hypre_error_w_msg(HYPRE_ERROR_GENERIC, (std::string(who) + ": operand is not in device memory; host execution is not part of this library").c_str());
+         return false;
+      }
+      if (flat_length(v) != n)
+      {
+         hypre_error_w_msg(HYPRE_ERROR_GENERIC, (std::string(who) + ": the vectors differ in length").c_str());
+         return false;
+      }
+   }
+   return true;
+}
+}  // namespace
+HYPRE_Int hypre_amd_ParVectorScaledCopy(HYPRE_Complex a, hypre_ParVector *x, hypre_ParVector *y)
+{
+   if (!same_device_length("hypre_amd_ParVectorScaledCopy", {x, y})) { return hypre_error_flag; }
+   if (x == y) { hypre_error_in_arg(3); return hypre_error_flag; }
+   scaled_copy_of(a, x, y);
+   maybe_sync();
+   return hypre_error_flag;
+}
+HYPRE_Int hypre_amd_ParVectorCopyThenInnerProd(hypre_ParVector *x, hypre_ParVector *y, HYPRE_Real *result)
+{
+   if (!same_device_length("hypre_amd_ParVectorCopyThenInnerProd", {x, y})) { return hypre_error_flag; }
+   if (x == y) { hypre_error_in_arg(2); return hypre_error_flag; }
+   *result = copy_then_inner_prod(x, y);
+   return hypre_error_flag;
+}
+HYPRE_Int hypre_amd_ParVectorScaledDifference(HYPRE_Complex a, hypre_ParVector *x, hypre_ParVector *y, hypre_ParVector *z)
+{
+   if (!same_device_length("hypre_amd_ParVectorScaledDifference", {x, y, z})) { return hypre_error_flag; }
+   if (z == x || z == y) { hypre_error_in_arg(4); return hypre_error_flag; }
+   scaled_difference(a, x, y, z);
+   maybe_sync();
+   return hypre_error_flag;
+}
 
 }  // extern "C"

@@ -27,9 +27,12 @@ class IJOptions:
         self.a = (1.0, 1.0, 1.0)      # -a ax ay az (difconv)
         self.solver = 0               # 0 AMG, 1 AMG-PCG, 2 DS-PCG (diagonal scaling), 3 AMG-GMRES, 4 DS-GMRES, 16 AMG-COGMRES, 17 DS-COGMRES,
                                       # 60 DS-FlexGMRES, 61 AMG-FlexGMRES
+        self.lgmres = 0               # options only: 1 runs LGMRES in place of GMRES, solver 4 as DS-LGMRES (the reference's -solver 50),
+                                      # solver 3 as AMG-LGMRES (51)
         self.neg_a = 0                # -negA 1: solve with -A (test/ij.c:4014-4017)
         self.num_components = 1       # -nc: columns of b and x (multivectors; test/ij.c:874-878, 3400-3404)
         self.k_dim = 5                # -k (GMRES restart length, test/ij.c:1731)
+        self.aug_dim = 2              # -aug (LGMRES: augmentation vectors, test/ij.c:1736, :1761); read with lgmres = 1 only
         self.cgs = 1                  # -cgs (COGMRES: 1 classical Gram-Schmidt, 2 with reorthogonalisation; test/ij.c:1746-1750)
         self.unroll = 0               # -unroll (COGMRES: host loop unrolling of the reference; accepted, no effect; test/ij.c:1751-1755)
         self.flex = 0                 # -flex (flexible PCG: Polak-Ribiere beta)
@@ -371,9 +374,14 @@ def parse_cli(argv):
 
 def check_options(opt):
     """The combinations of options this driver serves, whether they came from the command line or were set in code
-    (solvers 60 / 61, FlexGMRES, only the latter); returns opt."""
+    (solvers 60 / 61, FlexGMRES, and lgmres = 1, only the latter); returns opt."""
     if opt.solver not in (0, 1, 2, 3, 4, 16, 17, 60, 61):
         raise SystemExit("ij: solver %d is outside the scope of this driver" % opt.solver)
+    if opt.lgmres not in (0, 1) or (opt.lgmres and opt.solver not in (3, 4)):
+        raise SystemExit("ij: lgmres = %r with solver %d: LGMRES runs as solver 4 (DS-LGMRES, the reference's 50) or solver 3 "
+                         "(AMG-LGMRES, 51)" % (opt.lgmres, opt.solver))
+    if opt.aug_dim != 2 and not opt.lgmres:
+        raise SystemExit("ij: aug_dim = %r is read by LGMRES only (lgmres = 1 with solver 3 | 4)" % opt.aug_dim)
     if opt.num_components < 1 or (opt.num_components > 1 and (opt.rhs != "one" or opt.rhsfromfile)):
         # test/ij.c:3400-3404 takes several components with the constant right-hand sides only
         raise SystemExit("ij: -nc %d needs -rhsisone in this driver" % opt.num_components)
@@ -485,6 +493,9 @@ def run(opt, comm=0, rank=0, nprocs=1, allreduce=None, out=None):
                   "                   cycle = %f" % (cyc.value / nnz0 if nnz0 else 0.0), "", "", "",
                   "BoomerAMG Iterations = %d" % its.value,
                   "Final Relative Residual Norm = %e" % rel.value, ""]
+    elif opt.solver == 3 and opt.lgmres:
+        its.value, rel.value = solve_lgmres(opt, A, db, dx, comm=comm, amg=s)
+        lines += ["", "LGMRES Iterations = %d" % its.value, "Final LGMRES Relative Residual Norm = %e" % rel.value, ""]
     elif opt.solver == 3:
         its.value, rel.value = solve_gmres(opt, s, A, db, dx, comm=comm)
         lines += ["", "GMRES Iterations = %d" % its.value, "Final GMRES Relative Residual Norm = %e" % rel.value, ""]
@@ -540,7 +551,7 @@ def solve_ds_pcg(opt, A, db, dx, comm=0):
 
 
 def _solve_gmres_family(name, opt, A, b, x, comm, amg, early=(), late=(), amg_first=False, amg_max_iter=None, check_precond=False):
-    """Create, set, Setup, Solve, read back and Destroy one HYPRE_ParCSR<name> solver (GMRES, COGMRES, FlexGMRES), in the
+    """Create, set, Setup, Solve, read back and Destroy one HYPRE_ParCSR<name> solver (GMRES, COGMRES, FlexGMRES, LGMRES), in the
     order of library calls the reference driver makes: KDim, the `early` setters, MaxIter, Tol, AbsoluteTol, the `late`
     setters; then BoomerAMG (`amg`, tuned as a preconditioner: SetTol 0, SetMaxIter precon_cycles; before Create if
     `amg_first`, MaxIter set once more to `amg_max_iter` if given) or the diagonal scaling preconditioner."""
@@ -585,7 +596,7 @@ def solve_ds_gmres(opt, A, db, dx, comm=0):
 
 
 def run_ds_pcg(opt, A, comm=0, rank=0, allreduce=None, out=None):
-    """`ij -solver 2 | 4 | 17 | 60 [-nc N]` on the device: no hierarchy; the N columns of b (test/ij.c:3483-3512: the same values in
+    """`ij -solver 2 | 4 | 17 | 60 [-nc N]` (4 with lgmres = 1: DS-LGMRES) on the device: no hierarchy; the N columns of b (test/ij.c:3483-3512: the same values in
     every component) and of the zero initial guess as multivectors."""
     L = B.load_library()
     L.hypre_ParCSRMatrixMigrate(A, DEVICE)
@@ -605,12 +616,13 @@ def run_ds_pcg(opt, A, comm=0, rank=0, allreduce=None, out=None):
     else:
         db = B.parvec_from_numpy(b, comm=comm, global_size=nglob, first=first)
         dx = B.parvec_from_numpy(x0, comm=comm, global_size=nglob, first=first)
-    its, rel = {2: solve_ds_pcg, 4: solve_ds_gmres, 17: solve_cogmres, 60: solve_flexgmres}[opt.solver](opt, A, db, dx, comm=comm)
+    solve = {2: solve_ds_pcg, 4: solve_lgmres if opt.lgmres else solve_ds_gmres, 17: solve_cogmres, 60: solve_flexgmres}[opt.solver]
+    its, rel = solve(opt, A, db, dx, comm=comm)
     L.HYPRE_ClearError(256)
     B.check()
     L.hypre_ParVectorDestroy(db); L.hypre_ParVectorDestroy(dx)
     if rank == 0:
-        tag = {4: "GMRES ", 17: "COGMRES ", 60: "FlexGMRES "}.get(opt.solver, "")
+        tag = {4: "LGMRES " if opt.lgmres else "GMRES ", 17: "COGMRES ", 60: "FlexGMRES "}.get(opt.solver, "")
         out.write("\n".join(["", "%sIterations = %d" % (tag, its), "Final %sRelative Residual Norm = %e" % (tag, rel), ""]) + "\n")
         out.flush()
     return its, rel
@@ -634,6 +646,14 @@ def solve_flexgmres(opt, A, b, x, comm=0, amg=None):
     diagonal scaling preconditioner (solver 60); b and x may be multivectors (-nc N).  modify_pc stays the default, which
     changes nothing."""
     return _solve_gmres_family("FlexGMRES", opt, A, b, x, comm, amg, late=(("Logging", 1), ("PrintLevel", 3)),   # ioutdat; inert here
+                               amg_max_iter=opt.mg_max_iter, check_precond=True)
+
+
+def solve_lgmres(opt, A, b, x, comm=0, amg=None):
+    """test/ij.c:7338-7560: LGMRES behind BoomerAMG (the reference's solver 51, `amg` the set-up hierarchy) or behind the diagonal
+    scaling preconditioner (50); b and x may be multivectors (-nc N).  AugDim follows KDim, which it is clamped against."""
+    return _solve_gmres_family("LGMRES", opt, A, b, x, comm, amg, early=(("AugDim", opt.aug_dim),),
+                               late=(("Logging", 1), ("PrintLevel", 3)),            # ioutdat; inert here
                                amg_max_iter=opt.mg_max_iter, check_precond=True)
 
 

@@ -601,6 +601,76 @@ HYPRE_Int hypre_amd_FlexGMRESGetLaunchStats(HYPRE_Solver solver, HYPRE_Int *fuse
 HYPRE_Int hypre_amd_ParVectorAxpyThenInnerProd(HYPRE_Complex alpha, hypre_ParVector *x, hypre_ParVector *y, hypre_ParVector *z,
                                                HYPRE_Real *result);
 
+/* ---- LGMRES: restarted GMRES that carries corrections across restarts (the reference's `ij -solver 50 | 51`) ----
+ * krylov/lgmres.c:326-934, krylov/HYPRE_lgmres.c, parcsr_ls/HYPRE_parcsr_lgmres.c; defaults of hypre_LGMRESCreate
+ * (lgmres.c:83-105): k_dim 20, aug_dim 2, tol 1e-6, a_tol 0, min_iter 0, max_iter 1000.  A restart cycle has k_dim
+ * steps; the last ones (as many as there are augmentation vectors, aug_dim at most) are not Arnoldi steps but reuse the
+ * normalised corrections z of the cycles before, kept with A z = (r0 - r_m) / |w|, so they cost neither a matrix nor a
+ * preconditioner application.  SetAugDim clamps to 0 .. k_dim - 1 with the k_dim in force at the call; SetKDim and
+ * SetAugDim must precede Setup (k_dim + 2 aug_dim + 4 work vectors shaped like x; Solve refuses otherwise).  Operands
+ * are in device memory and may be multivectors (the flat inner product over all columns).  The relative-change and
+ * convergence-factor exits are not carried.  HYPRE_ERROR_CONV when max_iter is reached above a non-zero tolerance
+ * (lgmres.c:918).  A residual of exactly zero returns at once and leaves count and norm as they were (lgmres.c:545). */
+HYPRE_Int HYPRE_ParCSRLGMRESCreate(MPI_Comm comm, HYPRE_Solver *solver);
+HYPRE_Int HYPRE_ParCSRLGMRESDestroy(HYPRE_Solver solver);
+HYPRE_Int HYPRE_ParCSRLGMRESSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_ParCSRLGMRESSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_LGMRESSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_LGMRESSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_LGMRESSetKDim(HYPRE_Solver solver, HYPRE_Int k_dim);
+HYPRE_Int HYPRE_LGMRESSetAugDim(HYPRE_Solver solver, HYPRE_Int aug_dim);
+HYPRE_Int HYPRE_LGMRESGetAugDim(HYPRE_Solver solver, HYPRE_Int *aug_dim);
+HYPRE_Int HYPRE_LGMRESSetTol(HYPRE_Solver solver, HYPRE_Real tol);
+HYPRE_Int HYPRE_LGMRESSetAbsoluteTol(HYPRE_Solver solver, HYPRE_Real a_tol);
+HYPRE_Int HYPRE_LGMRESSetMinIter(HYPRE_Solver solver, HYPRE_Int min_iter);
+HYPRE_Int HYPRE_LGMRESSetMaxIter(HYPRE_Solver solver, HYPRE_Int max_iter);
+HYPRE_Int HYPRE_LGMRESSetPrecond(HYPRE_Solver solver, HYPRE_PtrToSolverFcn precond,
+                                 HYPRE_PtrToSolverFcn precond_setup, HYPRE_Solver precond_solver);
+HYPRE_Int HYPRE_LGMRESGetPrecond(HYPRE_Solver solver, HYPRE_Solver *precond_data_ptr);
+HYPRE_Int HYPRE_LGMRESSetLogging(HYPRE_Solver solver, HYPRE_Int logging);          /* accepted, inert */
+HYPRE_Int HYPRE_LGMRESSetPrintLevel(HYPRE_Solver solver, HYPRE_Int level);         /* accepted, inert */
+HYPRE_Int HYPRE_LGMRESGetNumIterations(HYPRE_Solver solver, HYPRE_Int *num_iterations);
+HYPRE_Int HYPRE_LGMRESGetFinalRelativeResidualNorm(HYPRE_Solver solver, HYPRE_Real *norm);
+HYPRE_Int HYPRE_LGMRESGetConverged(HYPRE_Solver solver, HYPRE_Int *converged);
+HYPRE_Int HYPRE_LGMRESGetResidual(HYPRE_Solver solver, void *residual);             /* a HYPRE_ParVector * */
+HYPRE_Int HYPRE_ParCSRLGMRESSetKDim(HYPRE_Solver solver, HYPRE_Int k_dim);
+HYPRE_Int HYPRE_ParCSRLGMRESSetAugDim(HYPRE_Solver solver, HYPRE_Int aug_dim);
+HYPRE_Int HYPRE_ParCSRLGMRESSetTol(HYPRE_Solver solver, HYPRE_Real tol);
+HYPRE_Int HYPRE_ParCSRLGMRESSetAbsoluteTol(HYPRE_Solver solver, HYPRE_Real a_tol);
+HYPRE_Int HYPRE_ParCSRLGMRESSetMinIter(HYPRE_Solver solver, HYPRE_Int min_iter);
+HYPRE_Int HYPRE_ParCSRLGMRESSetMaxIter(HYPRE_Solver solver, HYPRE_Int max_iter);
+HYPRE_Int HYPRE_ParCSRLGMRESSetPrecond(HYPRE_Solver solver, HYPRE_PtrToSolverFcn precond,
+                                       HYPRE_PtrToSolverFcn precond_setup, HYPRE_Solver precond_solver);
+HYPRE_Int HYPRE_ParCSRLGMRESGetPrecond(HYPRE_Solver solver, HYPRE_Solver *precond_data_ptr);
+HYPRE_Int HYPRE_ParCSRLGMRESSetLogging(HYPRE_Solver solver, HYPRE_Int logging);
+HYPRE_Int HYPRE_ParCSRLGMRESSetPrintLevel(HYPRE_Solver solver, HYPRE_Int level);
+HYPRE_Int HYPRE_ParCSRLGMRESGetNumIterations(HYPRE_Solver solver, HYPRE_Int *num_iterations);
+HYPRE_Int HYPRE_ParCSRLGMRESGetFinalRelativeResidualNorm(HYPRE_Solver solver, HYPRE_Real *norm);
+HYPRE_Int HYPRE_ParCSRLGMRESGetResidual(HYPRE_Solver solver, HYPRE_ParVector *residual);
+/* lgmres.c:593-600, a field the reference sets only in Create: 1 (the default) keeps a cycle at k_dim steps while fewer
+ * than aug_dim augmentation vectors exist; 0 takes k_dim - aug_dim Arnoldi steps from the first cycle on. */
+HYPRE_Int hypre_amd_LGMRESSetApproxConstant(HYPRE_Solver solver, HYPRE_Int on);
+/* 1 (the default): Gram-Schmidt steps fused as for FlexGMRES; the correction of a cycle one scaled copy and one batched
+ * update over Arnoldi and augmentation terms; the end of a cycle that restarts 4 launches (copy with squared norm, two
+ * scaled copies, scaled difference), 72 bytes per vector element.  0: the reference's Copy / Scale / InnerProd / Axpy
+ * sequence, 10 calls and 168 bytes for that end.  Either way a solve gives the same bits in x, the same iteration count
+ * and the same norm. */
+HYPRE_Int hypre_amd_LGMRESSetFusedUpdates(HYPRE_Solver solver, HYPRE_Int on);
+/* Launches of the last solve.  The first three as hypre_amd_FlexGMRESGetLaunchStats.  fused_updates: launches of the
+ * three operations below, for the correction and the end of every cycle; plain_updates: library calls made in their
+ * place.  With aug_dim > 0 a cycle that restarts counts 5 fused or 12 plain, the cycle a solve converges in 2 or 3.
+ * Host counters; any pointer may be NULL. */
+HYPRE_Int hypre_amd_LGMRESGetLaunchStats(HYPRE_Solver solver, HYPRE_Int *fused_steps, HYPRE_Int *plain_dots, HYPRE_Int *plain_axpys,
+                                         HYPRE_Int *fused_updates, HYPRE_Int *plain_updates);
+/* The vector operations LGMRES adds, each one pass with the bits of the library calls it stands for; device memory,
+ * equal lengths, the target distinct from the sources.
+ *   ScaledCopy          y = a x           hypre_ParVectorCopy(x, y); hypre_ParVectorScale(a, y)
+ *   CopyThenInnerProd   y = x, <x, x>     hypre_ParVectorCopy(x, y); hypre_ParVectorInnerProd(y, y)   (over all ranks)
+ *   ScaledDifference    z = a (x - y)     hypre_ParVectorCopy(x, z); Scale(-1, z); Axpy(1, y, z); Scale(-a, z) */
+HYPRE_Int hypre_amd_ParVectorScaledCopy(HYPRE_Complex a, hypre_ParVector *x, hypre_ParVector *y);
+HYPRE_Int hypre_amd_ParVectorCopyThenInnerProd(hypre_ParVector *x, hypre_ParVector *y, HYPRE_Real *result);
+HYPRE_Int hypre_amd_ParVectorScaledDifference(HYPRE_Complex a, hypre_ParVector *x, hypre_ParVector *y, hypre_ParVector *z);
+
 #ifdef __cplusplus
 }
 #endif
