@@ -194,6 +194,7 @@ HYPRE_Int hypre_ParCSRMaxEigEstimateCG(hypre_ParCSRMatrix *A, HYPRE_Int scale, H
    }
    const HYPRE_Int n = D->num_rows;
    if (A->global_num_rows < (HYPRE_BigInt) max_iter) { max_iter = (HYPRE_Int) A->global_num_rows; }
+   if (max_iter < 0) { max_iter = 0; }               // no steps: (0, 0) below, and no negative length for the two arrays
    if (!A->comm_pkg) { hypre_MatvecCommPkgCreate(A); }
    const size_t nn = (size_t) std::max(n, 1);
    std::vector<double> p(nn, 0.0), s(nn, 0.0), r(nn, 0.0), ds(nn, 1.0), u(nn, 0.0), ghost, sendbuf;

@@ -81,6 +81,8 @@ def load():
     L.oracle_relax_if.restype = C.c_int
     L.oracle_relax_if.argtypes = [P(OPAR), RealP, IntP, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                                   RealP, RealP, RealP, C.c_int, IntP]
+    L.oracle_cheby_solve.restype = C.c_int
+    L.oracle_cheby_solve.argtypes = [P(OPAR), RealP, RealP, RealP, C.c_int, C.c_int, RealP]
     L.oracle_gselim.restype = C.c_int
     L.oracle_gselim.argtypes = [RealP, RealP, C.c_int]
     L.oracle_amg_cycle.restype = C.c_int
@@ -331,6 +333,16 @@ def relax(A, f, cf_marker, relax_type, relax_points, w, omega, l1, u, num_thread
     err = load().oracle_relax(C.byref(A.c), _rp(f), _ip(cf) if cf is not None else None, relax_type,
                               relax_points, w, omega, _rp(l1), _rp(u), _rp(vtemp), num_threads, C.byref(az))
     return err
+
+
+def cheby_solve(A, f, ds, coefs, order, scale, u):
+    """One application of the Chebyshev smoother (relax 16) to u in place: u += p(A) (f - A u), on D^-1/2 A D^-1/2
+    when scale is set.  coefs: at least min(max(order, 1), 4) entries; ds: 1/sqrt(|a_ii|) per row, read with scale only."""
+    f = np.ascontiguousarray(f, dtype=np.float64)
+    coefs = np.ascontiguousarray(coefs, dtype=np.float64)
+    ds = None if ds is None else np.ascontiguousarray(ds, dtype=np.float64)
+    assert len(coefs) >= min(max(int(order), 1), 4) and (not scale or ds is not None)
+    return load().oracle_cheby_solve(C.byref(A.c), _rp(f), _rp(ds), _rp(coefs), int(order), int(scale), _rp(u))
 
 
 # ---------------------------------------------------------------------------
