@@ -350,20 +350,26 @@ __global__ void scatter_transpose_kernel(const int *__restrict__ Ai, const int *
 }
 
 // row c of the scattered transpose -> ascending source rows: entry i goes to slot (number of entries of the row with a
-// smaller source row); source rows are distinct within a row.  One wave per row.
+// smaller source row); source rows are distinct within a row.  One wave per row, the waves of the grid striding over the
+// rows: a launch holds fewer than 2^32 threads, so from 67 108 864 rows on a wave per row is more than one launch can have
+// (launch_transpose caps the grid at ORDER_ROWS_MAX_BLOCKS).
+constexpr size_t ORDER_ROWS_MAX_BLOCKS = (size_t) 1 << 22;      // of 256 threads: 16.7 million rows in one trip
 __global__ void order_rows_kernel(const int *__restrict__ Ti, int ncols, const int *__restrict__ tj_in, const double *__restrict__ ta_in,
                                   int *__restrict__ tj, double *__restrict__ ta)
 {
-   const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-   if (row >= ncols) { return; }
-   const int s = Ti[row], e = Ti[row + 1];
-   for (int i = s + lane; i < e; i += 64)
+   const size_t waves = ((size_t) gridDim.x * blockDim.x) >> 6;
+   const int lane = threadIdx.x & 63;
+   for (size_t row = ((size_t) blockIdx.x * blockDim.x + threadIdx.x) >> 6; row < (size_t) ncols; row += waves)
    {
-      const int mine = tj_in[i];
-      int rank = 0;
-      for (int k = s; k < e; k++) { rank += tj_in[k] < mine ? 1 : 0; }
-      tj[s + rank] = mine;
-      if (ta_in) { ta[s + rank] = ta_in[i]; }
+      const int s = Ti[row], e = Ti[row + 1];
+      for (int i = s + lane; i < e; i += 64)
+      {
+         const int mine = tj_in[i];
+         int rank = 0;
+         for (int k = s; k < e; k++) { rank += tj_in[k] < mine ? 1 : 0; }
+         tj[s + rank] = mine;
+         if (ta_in) { ta[s + rank] = ta_in[i]; }
+      }
    }
 }
 
@@ -586,7 +592,9 @@ void launch_transpose(const int *Ai, const int *Aj, const double *Aa, int nrows,
    if (Aa) { HIP_CHECK(hipMalloc((void **) &ta0, sizeof(double) * (size_t) nnz)); }
    HIP_CHECK(hipMemcpyAsync(cursor, Ti, sizeof(int) * ((size_t) ncols + 1), hipMemcpyDeviceToDevice, s));
    hipLaunchKernelGGL(scatter_transpose_kernel, dim3(((size_t) nrows * 8 + 255) / 256), dim3(256), 0, s, Ai, Aj, Aa, nrows, cursor, tj0, ta0);
-   hipLaunchKernelGGL(order_rows_kernel, dim3(((size_t) ncols * 64 + 255) / 256), dim3(256), 0, s, Ti, ncols, tj0, ta0, tj, ta);
+   const size_t order_grid = std::min(((size_t) ncols * 64 + 255) / 256, ORDER_ROWS_MAX_BLOCKS);
+   hipLaunchKernelGGL(order_rows_kernel, dim3(order_grid), dim3(256), 0, s, Ti, ncols, tj0, ta0, tj, ta);
+   HIP_CHECK(hipGetLastError());           // a launch the runtime refused (a grid too large) must not pass for a transpose
    HIP_CHECK(hipStreamSynchronize(s));
    HIP_CHECK(hipFree(cursor));
    HIP_CHECK(hipFree(tj0));

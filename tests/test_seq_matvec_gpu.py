@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from util import banded_csr, laplace_3d, random_csr, rand_vector
+from util import banded_csr, laplace_3d, random_csr, rand_vector, transpose_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -403,6 +403,10 @@ def test_device_transpose_is_the_host_transpose(gpu_lib, shape, lo, hi, empty):
     assert dT.contents.memory_location == B.HYPRE_MEMORY_DEVICE and hT.contents.memory_location == B.HYPRE_MEMORY_HOST
     for a, b in zip(B.csr_to_arrays(dT), B.csr_to_arrays(hT)):
         assert np.array_equal(a, b)
+    # ... and what plain numpy gives (a stable sort by column), so the two routines cannot be wrong alike
+    ni, nj, na = transpose_reference(A.indptr, A.indices, A.data, shape[0], shape[1])
+    ti, tj, ta = B.csr_to_arrays(dT)
+    assert np.array_equal(ti, ni) and np.array_equal(tj, nj) and ta.tobytes() == na.tobytes()
     # pattern only
     dP = C.POINTER(B.CSRMatrix)()
     lib.hypre_CSRMatrixTranspose(dA, C.byref(dP), 0)
@@ -410,6 +414,7 @@ def test_device_transpose_is_the_host_transpose(gpu_lib, shape, lo, hi, empty):
     ii, jj, _ = B.csr_to_arrays(dP)
     ri, rj, _ = B.csr_to_arrays(hT)
     assert np.array_equal(ii, ri) and np.array_equal(jj, rj)
+    assert np.array_equal(ii, ni) and np.array_equal(jj, nj)
     for m in (dA, hA, dT, hT, dP):
         lib.hypre_CSRMatrixDestroy(m)
 

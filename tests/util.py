@@ -99,3 +99,13 @@ def banded_csr(nrows, ncols, min_nnz, max_nnz, band, seed=0, empty_frac=0.0):
         indices[indptr[r]:indptr[r + 1]] = lo[r] + rng.choice(hi[r] - lo[r], counts[r], replace=False)
     data = rng.uniform(-1, 1, indptr[-1])
     return sp.csr_matrix((data, indices, indptr), shape=(nrows, ncols))
+
+
+def transpose_reference(indptr, indices, data, nrows, ncols):
+    """(ti, tj, ta) of the transpose of a CSR matrix in plain numpy: a stable sort of the row-major entries by column, so
+    row c of the transpose lists the rows holding column c in ascending order (seq_mv/csr_matop.c:1043-1270), values alongside."""
+    indptr, indices = np.asarray(indptr, dtype=np.int64), np.asarray(indices, dtype=np.int64)
+    rows = np.repeat(np.arange(nrows), np.diff(indptr))
+    order = np.argsort(indices, kind="stable")
+    ti = np.concatenate([[0], np.cumsum(np.bincount(indices, minlength=ncols))])
+    return ti, rows[order], np.asarray(data)[order]
