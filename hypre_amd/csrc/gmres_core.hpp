@@ -67,35 +67,157 @@ struct GMRESResult
    long fused_steps = 0, plain_dots = 0, plain_axpys = 0;     // launches of the modified Gram-Schmidt steps
 };
 
+// ---- the steps gmres_iterate and lgmres_iterate (lgmres_core.hpp) share: each stands here once, so that the two loops
+// cannot drift apart in a rounding or a check
+
+template <class V, class Ops> double krylov_norm(Ops &ops, V v) { return std::sqrt(ops.inner(v, v)); }
+
+// |b - A x|, the residual left in r (gmres.c:776-778, lgmres.c:798-800)
+template <class V, class Ops> double true_residual(Ops &ops, V b, V x, V r) { ops.copy(b, r); ops.matvec(-1.0, x, 1.0, r); return krylov_norm(ops, r); }
+
+// b - A x into p0, the norms, the not-a-number checks and the stopping threshold (gmres.c:359-457, cogmres.c:368-459,
+// flexgmres.c:372-463, lgmres.c:413-504); after a not-a-number in b the norm of p0 is not taken
+struct KrylovStart { double b_norm = 0.0, r_norm = 0.0, den_norm = 0.0, epsilon = 0.0; bool not_a_number = true; };
+template <class V, class Ops> KrylovStart krylov_start(Ops &ops, V b, V x, V p0, double tol, double a_tol)
+{
+   KrylovStart st;
+   double ieee_check = 0.;
+   ops.copy(b, p0);
+   ops.matvec(-1.0, x, 1.0, p0);
+   st.b_norm = krylov_norm(ops, b);
+   if (st.b_norm != 0.) { ieee_check = st.b_norm / st.b_norm; }
+   if (ieee_check != ieee_check) { return st; }
+   st.r_norm = krylov_norm(ops, p0);
+   if (st.r_norm != 0.) { ieee_check = st.r_norm / st.r_norm; }
+   if (ieee_check != ieee_check) { return st; }
+   st.not_a_number = false;
+   st.den_norm = (st.b_norm > 0.0) ? st.b_norm : st.r_norm;
+   st.epsilon = std::max(a_tol, tol * st.den_norm);
+   return st;
+}
+
+// modified Gram-Schmidt of p[i] against p[0..i-1], the products into h[0..i-1]; returns |p[i]| (gmres.c:541-547,
+// flexgmres.c:562-573, lgmres.c:642-647).  fused: the projection on p[j] leaves in the same pass the product with
+// p[j + 1], the last one the squared norm; the same sums and roundings as the plain inner / axpy sequence.
+template <class V, class Ops> double mgs_step(Ops &ops, V *p, int i, double *h, bool fused, GMRESResult &res)
+{
+   double t;
+   if (fused)
+   {
+      t = ops.inner(p[0], p[i]);
+      res.plain_dots++;
+      for (int j = 0; j < i; j++)
+      {
+         h[j] = t;
+         t = ops.axpy_dot(-t, p[j], p[i], j + 1 < i ? p[j + 1] : p[i]);
+         res.fused_steps++;
+      }
+      return std::sqrt(t);
+   }
+   for (int j = 0; j < i; j++)
+   {
+      h[j] = ops.inner(p[j], p[i]);
+      ops.axpy(-h[j], p[j], p[i]);
+   }
+   res.plain_dots += i + 1;
+   res.plain_axpys += i;
+   return krylov_norm(ops, p[i]);
+}
+
+// the Hessenberg matrix of a restart cycle of up to `cols` steps, its Givens rotations and the right-hand side rs of the
+// least-squares problem; hh(row, col) is hh[col * ld + row].  (Hidden: not a dynamic symbol of a library built from this.)
+struct __attribute__((visibility("hidden"))) Hessenberg
+{
+   size_t ld;
+   std::vector<double> hh, rs, c, s;
+   explicit Hessenberg(size_t cols) : ld(cols + 1), hh(ld * cols, 0.0), rs(ld, 0.0), c(cols, 0.0), s(cols, 0.0) {}
+   double *column(int i) { return &hh[(size_t) (i - 1) * ld]; }      // column i - 1, the one step i fills: h[j] is hh(j, i - 1)
+   // the new column's last entry is t = |p[i]|, and p[i] becomes a unit vector unless it is zero; then the rotations so far
+   // on the column and the one that clears h[i].  Returns the norm the recurrence gives the residual (gmres.c:548-576,
+   // lgmres.c:648-675)
+   template <class V, class Ops> double close_column(Ops &ops, V pi, int i, double t)
+   {
+      const double epsmac = 1.e-16;
+      double *h = column(i), gamma;
+      h[i] = t;
+      if (t != 0.0) { t = 1.0 / t; ops.scale(t, pi); }
+      for (int j = 1; j < i; j++)
+      {
+         t = h[j - 1];
+         h[j - 1] = s[j - 1] * h[j] + c[j - 1] * t;
+         h[j] = -s[j - 1] * t + c[j - 1] * h[j];
+      }
+      t = h[i] * h[i];
+      t += h[i - 1] * h[i - 1];
+      gamma = std::sqrt(t);
+      if (gamma == 0.0) { gamma = epsmac; }
+      c[i - 1] = h[i - 1] / gamma;
+      s[i - 1] = h[i] / gamma;
+      rs[i] = -h[i] * rs[i - 1];
+      rs[i] /= gamma;
+      rs[i - 1] = c[i - 1] * rs[i - 1];
+      h[i - 1] = s[i - 1] * h[i] + c[i - 1] * h[i - 1];
+      return std::fabs(rs[i]);
+   }
+   // the upper triangular solve after i steps: rs[0..i-1] become the coefficients of the correction (gmres.c:740-750,
+   // lgmres.c:724-734)
+   void solve(int i)
+   {
+      rs[i - 1] = rs[i - 1] / column(i)[i - 1];
+      for (int k = i - 2; k >= 0; k--)
+      {
+         double t = 0.0;
+         for (int j = k + 1; j < i; j++) { t -= hh[(size_t) j * ld + (size_t) k] * rs[j]; }
+         t += rs[k];
+         rs[k] = t / hh[(size_t) k * ld + (size_t) k];
+      }
+   }
+};
+
+// residual vector of the restart into p[0]: rs[0..i] become its coefficients in p[0..i], then the sum (gmres.c:864-880,
+// cogmres.c:864-881, flexgmres.c:707-723, lgmres.c:830-846); nothing to do after a restart from the true residual (i == 0)
+template <class V, class Ops> void restart_residual(Ops &ops, V *p, int i, Hessenberg &H)
+{
+   std::vector<double> &rs = H.rs;
+   for (int j = i; j > 0; j--)
+   {
+      rs[j - 1] = -H.s[j - 1] * rs[j];
+      rs[j] = H.c[j - 1] * rs[j];
+   }
+   if (!i) { return; }
+   ops.axpy(rs[i] - 1.0, p[i], p[i]);
+   for (int j = i - 1; j > 0; j--) { ops.axpy(rs[j], p[j], p[i]); }
+   ops.axpy(rs[0] - 1.0, p[0], p[0]);
+   ops.axpy(1.0, p[i], p[0]);
+}
+
+// what a solve that ran its loop reports (gmres.c:903, cogmres.c:896, flexgmres.c:743, lgmres.c:918; see GMRESParams)
+inline void krylov_finish(GMRESResult &res, int iter, double r_norm, double b_norm, double epsilon, int max_iter, bool conv_error_at_zero_tol)
+{
+   res.iterations = iter;
+   res.iterations_set = res.norm_set = true;
+   res.rel_residual_norm = (b_norm > 0.0) ? r_norm / b_norm : r_norm;
+   if (iter >= max_iter && r_norm > epsilon && (epsilon > 0 || conv_error_at_zero_tol)) { res.status = GMRES_NOT_CONVERGED; }
+}
+
 // p (and pre, if flexible) hold k_dim + 1 vectors; r and w are work vectors
 template <class V, class Ops>
 GMRESResult gmres_iterate(const GMRESParams &prm, Ops &ops, V b, V x, V r, V w, V *p, V *pre)
 {
    GMRESResult res;
    const int k_dim = prm.k_dim, min_iter = prm.min_iter, max_iter = prm.max_iter, unroll = prm.unroll;
-   const double epsmac = 1.e-16;
-   const size_t ld = (size_t) k_dim + 1;             // a column of the Hessenberg matrix: hh(row, col) is hh[col * ld + row]
-   std::vector<double> rs(ld, 0.0), c((size_t) k_dim, 0.0), s((size_t) k_dim, 0.0), coef((size_t) k_dim, 0.0), rv((size_t) k_dim, 0.0);
-   std::vector<double> hh(ld * (size_t) k_dim, 0.0), uu(prm.ortho == GMRESOrtho::CGS2 ? ld * (size_t) k_dim : 0, 0.0);
+   Hessenberg H((size_t) k_dim);
+   std::vector<double> &rs = H.rs;
+   const size_t ld = H.ld;
+   std::vector<double> coef((size_t) k_dim, 0.0), rv((size_t) k_dim, 0.0), uu(prm.ortho == GMRESOrtho::CGS2 ? ld * (size_t) k_dim : 0, 0.0);
    std::vector<V> terms((size_t) k_dim);
    V *dir = prm.flexible ? pre : p;                  // what the correction is summed from
    int i = 0, j, k, iter = 0;
-   double t, gamma, r_norm, b_norm, den_norm, epsilon, ieee_check = 0., real_r_norm_old;
-   double *h = hh.data();                            // column i - 1, the one step i fills: h[j] is hh(j, i - 1)
-   auto norm = [&](V v) { return std::sqrt(ops.inner(v, v)); };
-   auto true_residual = [&]() { ops.copy(b, r); ops.matvec(-1.0, x, 1.0, r); return norm(r); };
 
-   ops.copy(b, p[0]);
-   ops.matvec(-1.0, x, 1.0, p[0]);
-   b_norm = norm(b);
-   real_r_norm_old = b_norm;
-   if (b_norm != 0.) { ieee_check = b_norm / b_norm; }
-   if (ieee_check != ieee_check) { res.status = GMRES_NOT_A_NUMBER; return res; }
-   r_norm = norm(p[0]);
-   if (r_norm != 0.) { ieee_check = r_norm / r_norm; }
-   if (ieee_check != ieee_check) { res.status = GMRES_NOT_A_NUMBER; return res; }
-   den_norm = (b_norm > 0.0) ? b_norm : r_norm;
-   epsilon = std::max(prm.a_tol, prm.tol * den_norm);
+   const KrylovStart st = krylov_start(ops, b, x, p[0], prm.tol, prm.a_tol);
+   if (st.not_a_number) { res.status = GMRES_NOT_A_NUMBER; return res; }
+   const double b_norm = st.b_norm, den_norm = st.den_norm, epsilon = st.epsilon;
+   double t, r_norm = st.r_norm, real_r_norm_old = b_norm;
 
    while (iter < max_iter)
    {
@@ -108,7 +230,7 @@ GMRESResult gmres_iterate(const GMRESParams &prm, Ops &ops, V b, V x, V r, V w, 
       }
       if (r_norm <= epsilon && iter >= min_iter)
       {
-         r_norm = true_residual();
+         r_norm = true_residual(ops, b, x, r);
          if (r_norm <= epsilon) { break; }
       }
       t = 1.0 / r_norm;
@@ -118,33 +240,15 @@ GMRESResult gmres_iterate(const GMRESParams &prm, Ops &ops, V b, V x, V r, V w, 
       {
          i++;
          iter++;
-         h = &hh[(size_t) (i - 1) * ld];
+         double *h = H.column(i);
          V Ap = prm.flexible ? pre[i - 1] : r;
          ops.precond(iter, r_norm / den_norm, p[i - 1], Ap);
          ops.matvec(1.0, Ap, 0.0, p[i]);
          switch (prm.ortho)
          {
             case GMRESOrtho::MGS_FUSED:
-               // the projection on p[j] leaves in the same pass the product with p[j + 1], the last one the squared norm
-               t = ops.inner(p[0], p[i]);
-               res.plain_dots++;
-               for (j = 0; j < i; j++)
-               {
-                  h[j] = t;
-                  t = ops.axpy_dot(-t, p[j], p[i], j + 1 < i ? p[j + 1] : p[i]);
-                  res.fused_steps++;
-               }
-               t = std::sqrt(t);
-               break;
             case GMRESOrtho::MGS:
-               for (j = 0; j < i; j++)
-               {
-                  h[j] = ops.inner(p[j], p[i]);
-                  ops.axpy(-h[j], p[j], p[i]);
-               }
-               t = norm(p[i]);
-               res.plain_dots += i + 1;
-               res.plain_axpys += i;
+               t = mgs_step(ops, p, i, h, prm.ortho == GMRESOrtho::MGS_FUSED, res);
                break;
             case GMRESOrtho::CGS2:
             {
@@ -159,7 +263,7 @@ GMRESResult gmres_iterate(const GMRESParams &prm, Ops &ops, V b, V x, V r, V w, 
                for (j = 0; j < i; j++) { h[j] = -rv[j] - h[j]; }
                ops.mass_axpy(h, p, p[i], i, unroll);
                for (j = 0; j < i; j++) { h[j] = -h[j]; }
-               t = norm(p[i]);
+               t = krylov_norm(ops, p[i]);
                break;
             }
             case GMRESOrtho::CGS:
@@ -167,40 +271,13 @@ GMRESResult gmres_iterate(const GMRESParams &prm, Ops &ops, V b, V x, V r, V w, 
                for (j = 0; j < i; j++) { h[j] = -h[j]; }
                ops.mass_axpy(h, p, p[i], i, unroll);
                for (j = 0; j < i; j++) { h[j] = -h[j]; }
-               t = norm(p[i]);
+               t = krylov_norm(ops, p[i]);
                break;
          }
-         h[i] = t;
-         if (t != 0.0) { t = 1.0 / t; ops.scale(t, p[i]); }
-         // the rotations so far on the new column, then the one that clears h[i]
-         for (j = 1; j < i; j++)
-         {
-            t = h[j - 1];
-            h[j - 1] = s[j - 1] * h[j] + c[j - 1] * t;
-            h[j] = -s[j - 1] * t + c[j - 1] * h[j];
-         }
-         t = h[i] * h[i];
-         t += h[i - 1] * h[i - 1];
-         gamma = std::sqrt(t);
-         if (gamma == 0.0) { gamma = epsmac; }
-         c[i - 1] = h[i - 1] / gamma;
-         s[i - 1] = h[i] / gamma;
-         rs[i] = -h[i] * rs[i - 1];
-         rs[i] /= gamma;
-         rs[i - 1] = c[i - 1] * rs[i - 1];
-         h[i - 1] = s[i - 1] * h[i] + c[i - 1] * h[i - 1];
-         r_norm = std::fabs(rs[i]);
+         r_norm = H.close_column(ops, p[i], i, t);
          if (r_norm <= epsilon && iter >= min_iter) { break; }
       }
-      // upper triangular solve
-      rs[i - 1] = rs[i - 1] / h[i - 1];
-      for (k = i - 2; k >= 0; k--)
-      {
-         t = 0.0;
-         for (j = k + 1; j < i; j++) { t -= hh[(size_t) j * ld + (size_t) k] * rs[j]; }
-         t += rs[k];
-         rs[k] = t / hh[(size_t) k * ld + (size_t) k];
-      }
+      H.solve(i);
       // the correction, last direction first
       ops.copy(dir[i - 1], w);
       ops.scale(rs[i - 1], w);
@@ -223,7 +300,7 @@ GMRESResult gmres_iterate(const GMRESParams &prm, Ops &ops, V b, V x, V r, V w, 
       if (r_norm <= epsilon && iter >= min_iter)
       {
          if (prm.skip_real_r_check) { res.converged = 1; break; }
-         r_norm = true_residual();
+         r_norm = true_residual(ops, b, x, r);
          if (r_norm <= epsilon) { res.converged = 1; break; }
          if (prm.stop_when_residual_grows)
          {
@@ -233,24 +310,9 @@ GMRESResult gmres_iterate(const GMRESParams &prm, Ops &ops, V b, V x, V r, V w, 
          ops.copy(r, p[0]);             // "false convergence 2" (gmres.c:855-859, flexgmres.c:695-703): restart from the true residual
          i = 0;
       }
-      // residual vector of the restart (gmres.c:864-880, cogmres.c:864-881, flexgmres.c:707-723)
-      for (j = i; j > 0; j--)
-      {
-         rs[j - 1] = -s[j - 1] * rs[j];
-         rs[j] = c[j - 1] * rs[j];
-      }
-      if (i) { ops.axpy(rs[i] - 1.0, p[i], p[i]); }
-      for (j = i - 1; j > 0; j--) { ops.axpy(rs[j], p[j], p[i]); }
-      if (i)
-      {
-         ops.axpy(rs[0] - 1.0, p[0], p[0]);
-         ops.axpy(1.0, p[i], p[0]);
-      }
+      restart_residual(ops, p, i, H);
    }
-   res.iterations = iter;
-   res.iterations_set = res.norm_set = true;
-   res.rel_residual_norm = (b_norm > 0.0) ? r_norm / b_norm : r_norm;
-   if (iter >= max_iter && r_norm > epsilon && (epsilon > 0 || prm.conv_error_at_zero_tol)) { res.status = GMRES_NOT_CONVERGED; }
+   krylov_finish(res, iter, r_norm, b_norm, epsilon, max_iter, prm.conv_error_at_zero_tol);
    return res;
 }
 

@@ -81,6 +81,19 @@ bool    ensure_device();                 // lazily creates streams; false if no 
 int     host_cpu_share();                // cores this process may use: affinity mask cut by a cgroup CPU quota
 hipStream_t stream();                    // compute stream
 void    maybe_sync();                    // honours hypre_SetSyncCudaCompute
+// For the body of a public call that makes many: the stream synchronisation after each inner call is off while a
+// QuietSync lives, and back as the caller set it on every way out.  A call that ends in a synchronisation of its own
+// restores first: `quiet.restore(); maybe_sync();`.  (Hidden: the library's dynamic symbols stay the set they were.)
+struct __attribute__((visibility("hidden"))) QuietSync
+{
+   int  saved;
+   bool live = true;
+   QuietSync() : saved(handle().sync_compute) { handle().sync_compute = 0; }
+   void restore() { if (live) { handle().sync_compute = saved; live = false; } }
+   ~QuietSync() { restore(); }
+   QuietSync(const QuietSync &) = delete;
+   QuietSync &operator=(const QuietSync &) = delete;
+};
 double *reduce_scratch(size_t n);        // >= n doubles of device scratch
 double *reduce_host(size_t n);           // >= n doubles of pinned host memory: where read-backs of reductions land
 

@@ -2,10 +2,12 @@
 // for accelerating the convergence of restarted GMRES", 2005): right-preconditioned restarted GMRES whose restart cycle of
 // k_dim steps ends in up to aug_dim steps that are not Arnoldi steps but bring back the corrections of the cycles before
 // (the augmentation vectors z_j, kept with A z_j, so they cost no matrix and no preconditioner application).  A sibling of
-// gmres_iterate (gmres_core.hpp) in the same style: every vector operation is a callback, and the Hessenberg matrix, the
-// Givens rotations, the Arnoldi-or-augmentation decision, the order of the augmentation vectors and every exit live here,
-// on the host.  It is a loop of its own because it_arnoldi, it_aug and aug_ct thread through the whole cycle, the
-// correction and the restart included.  par_gmres.cpp runs it on ParVectors on the device,
+// gmres_iterate (gmres_core.hpp) in the same style: every vector operation is a callback, and the Arnoldi-or-augmentation
+// decision, the order of the augmentation vectors and every exit live here, on the host.  It is a loop of its own because
+// it_arnoldi, it_aug and aug_ct thread through the whole cycle, the correction and the restart included.  The steps that
+// are the same arithmetic in both loops (the start-up, the modified Gram-Schmidt step, the Hessenberg column and its
+// rotation, the triangular solve, the residual vector of the restart, the closing of the result) are the functions of
+// gmres_core.hpp, called from both.  par_gmres.cpp runs it on ParVectors on the device,
 // tests/host/lgmres_host_check.cpp on plain arrays under the sanitizers.
 //
 // What lgmres.c does differently from gmres.c, kept: no "residual did not fall" exit after a false convergence (:812-820);
@@ -23,11 +25,14 @@
 
 namespace hamd {
 
-struct LGMRESParams
+// k_dim, min_iter, max_iter, tol, a_tol and unroll (handed to mass_axpy) are those of GMRESParams; its other switches
+// (ortho, flexible, skip_real_r_check, stop_when_residual_grows, count_at_zero_residual, conv_error_at_zero_tol) are not
+// read by lgmres_iterate, whose behaviour in their place is the list above
+struct LGMRESParams : GMRESParams
 {
    // hypre_LGMRESCreate (lgmres.c:83-105)
-   int k_dim = 20, aug_dim = 2, min_iter = 0, max_iter = 1000;
-   double tol = 1e-6, a_tol = 0.0;
+   LGMRESParams() { k_dim = 20; }
+   int aug_dim = 2;
    // 1: a cycle has k_dim steps also while fewer than aug_dim augmentation vectors exist (more Arnoldi steps make up for
    // them); 0: always k_dim - aug_dim Arnoldi steps (lgmres.c:593-600)
    int approx_constant = 1;
@@ -35,7 +40,6 @@ struct LGMRESParams
    // scaled_copy, copy_norm2 and scaled_diff; false: the reference's sequence of copy / scale / inner / axpy calls.  The
    // same roundings in the same order either way.
    bool fused = true;
-   int unroll = 0;                           // handed to mass_axpy
 };
 
 struct LGMRESResult : GMRESResult
@@ -52,29 +56,20 @@ LGMRESResult lgmres_iterate(const LGMRESParams &prm, Ops &ops, V b, V x, V r, V 
 {
    LGMRESResult res;
    const int k_dim = prm.k_dim, aug_dim = prm.aug_dim, min_iter = prm.min_iter, max_iter = prm.max_iter;
-   const double epsmac = 1.e-16;
-   const size_t cols = (size_t) k_dim + (size_t) aug_dim, ld = cols + 1;      // hh(row, col) is hh[col * ld + row]
-   std::vector<double> rs(ld, 0.0), c(cols, 0.0), s(cols, 0.0), coef(cols, 0.0), hh(ld * cols, 0.0);
+   const size_t cols = (size_t) k_dim + (size_t) aug_dim;
+   Hessenberg H(cols);
+   std::vector<double> &rs = H.rs;
+   std::vector<double> coef(cols, 0.0);
    std::vector<V> terms(cols);
    std::vector<int> aug_order((size_t) aug_dim, 0);     // aug_order[spot]: how many cycles ago aug[spot] was the correction
    int i = 0, j, k, ii, iter = 0, aug_ct = 0, spot = 0, it_arnoldi, it_total, it_aug, first;
-   double t, gamma, r_norm, b_norm, den_norm, epsilon, ieee_check = 0., r_norm_last, tmp_norm, w_squared = 0.0;
-   double *h = hh.data();                               // column i - 1, the one step i fills
-   auto norm = [&](V v) { return std::sqrt(ops.inner(v, v)); };
-   auto true_residual = [&]() { ops.copy(b, r); ops.matvec(-1.0, x, 1.0, r); return norm(r); };
    // the first slot whose vector is `order` cycles old; before aug_ct reaches aug_dim the unused slots hold duplicates
    auto slot_of = [&](int order) { for (int q = 0; q < aug_dim; q++) { if (aug_order[(size_t) q] == order) { spot = q; break; } } return spot; };
 
-   ops.copy(b, p[0]);
-   ops.matvec(-1.0, x, 1.0, p[0]);
-   b_norm = norm(b);
-   if (b_norm != 0.) { ieee_check = b_norm / b_norm; }
-   if (ieee_check != ieee_check) { res.status = GMRES_NOT_A_NUMBER; return res; }
-   r_norm = norm(p[0]);
-   if (r_norm != 0.) { ieee_check = r_norm / r_norm; }
-   if (ieee_check != ieee_check) { res.status = GMRES_NOT_A_NUMBER; return res; }
-   den_norm = (b_norm > 0.0) ? b_norm : r_norm;
-   epsilon = std::max(prm.a_tol, prm.tol * den_norm);
+   const KrylovStart st = krylov_start(ops, b, x, p[0], prm.tol, prm.a_tol);
+   if (st.not_a_number) { res.status = GMRES_NOT_A_NUMBER; return res; }
+   const double b_norm = st.b_norm, den_norm = st.den_norm, epsilon = st.epsilon;
+   double t, r_norm = st.r_norm, r_norm_last, tmp_norm, w_squared = 0.0;
 
    while (iter < max_iter)
    {
@@ -82,7 +77,7 @@ LGMRESResult lgmres_iterate(const LGMRESParams &prm, Ops &ops, V b, V x, V r, V 
       if (r_norm == 0.0) { res.iterations = iter; return res; }
       if (r_norm <= epsilon && iter >= min_iter)
       {
-         r_norm = true_residual();
+         r_norm = true_residual(ops, b, x, r);
          if (r_norm <= epsilon) { break; }
       }
       t = 1.0 / r_norm;
@@ -96,7 +91,6 @@ LGMRESResult lgmres_iterate(const LGMRESParams &prm, Ops &ops, V b, V x, V r, V 
       {
          i++;
          iter++;
-         h = &hh[(size_t) (i - 1) * ld];
          if (i <= it_arnoldi)
          {
             ops.precond(iter, r_norm / den_norm, p[i - 1], r);
@@ -108,60 +102,11 @@ LGMRESResult lgmres_iterate(const LGMRESParams &prm, Ops &ops, V b, V x, V r, V 
             it_aug++;
             ops.copy(a_aug[slot_of(i - it_arnoldi - 1)], p[i]);
          }
-         // modified Gram-Schmidt, as GMRESOrtho::MGS_FUSED and MGS of gmres_iterate
-         if (prm.fused)
-         {
-            t = ops.inner(p[0], p[i]);
-            res.plain_dots++;
-            for (j = 0; j < i; j++)
-            {
-               h[j] = t;
-               t = ops.axpy_dot(-t, p[j], p[i], j + 1 < i ? p[j + 1] : p[i]);
-               res.fused_steps++;
-            }
-            t = std::sqrt(t);
-         }
-         else
-         {
-            for (j = 0; j < i; j++)
-            {
-               h[j] = ops.inner(p[j], p[i]);
-               ops.axpy(-h[j], p[j], p[i]);
-            }
-            t = norm(p[i]);
-            res.plain_dots += i + 1;
-            res.plain_axpys += i;
-         }
-         h[i] = t;
-         if (t != 0.0) { t = 1.0 / t; ops.scale(t, p[i]); }
-         for (j = 1; j < i; j++)
-         {
-            t = h[j - 1];
-            h[j - 1] = s[j - 1] * h[j] + c[j - 1] * t;
-            h[j] = -s[j - 1] * t + c[j - 1] * h[j];
-         }
-         t = h[i] * h[i];
-         t += h[i - 1] * h[i - 1];
-         gamma = std::sqrt(t);
-         if (gamma == 0.0) { gamma = epsmac; }
-         c[i - 1] = h[i - 1] / gamma;
-         s[i - 1] = h[i] / gamma;
-         rs[i] = -h[i] * rs[i - 1];
-         rs[i] /= gamma;
-         rs[i - 1] = c[i - 1] * rs[i - 1];
-         h[i - 1] = s[i - 1] * h[i] + c[i - 1] * h[i - 1];
-         r_norm = std::fabs(rs[i]);
+         t = mgs_step(ops, p, i, H.column(i), prm.fused, res);
+         r_norm = H.close_column(ops, p[i], i, t);
          if (r_norm <= epsilon && iter >= min_iter) { break; }
       }
-      // upper triangular solve
-      rs[i - 1] = rs[i - 1] / h[i - 1];
-      for (k = i - 2; k >= 0; k--)
-      {
-         t = 0.0;
-         for (j = k + 1; j < i; j++) { t -= hh[(size_t) j * ld + (size_t) k] * rs[j]; }
-         t += rs[k];
-         rs[k] = t / hh[(size_t) k * ld + (size_t) k];
-      }
+      H.solve(i);
       if (it_arnoldi > i) { it_arnoldi = i; }             // the cycle ended before all its Arnoldi steps
       // the correction w (lgmres.c:746-780): without augmentation steps the last direction first, as GMRES sums it; with
       // them p[0] first, the other Arnoldi directions upwards, then the augmentation vectors from the newest
@@ -199,7 +144,7 @@ LGMRESResult lgmres_iterate(const LGMRESParams &prm, Ops &ops, V b, V x, V r, V 
       ops.solution_changed(x);
       if (r_norm <= epsilon && iter >= min_iter)
       {
-         r_norm = true_residual();
+         r_norm = true_residual(ops, b, x, r);
          if (r_norm <= epsilon) { res.converged = 1; break; }
          ops.copy(r, p[0]);             // "false convergence 2": restart from the true residual
          i = 0;
@@ -207,18 +152,7 @@ LGMRESResult lgmres_iterate(const LGMRESParams &prm, Ops &ops, V b, V x, V r, V 
       // r0, not scaled, into w (lgmres.c:826-827); then the residual vector of the restart into p[0] as GMRES forms it
       if (prm.fused) { ops.scaled_copy(r_norm_last, p[0], w); res.fused_updates++; }
       else { ops.copy(p[0], w); ops.scale(r_norm_last, w); res.plain_updates += 2; }
-      for (j = i; j > 0; j--)
-      {
-         rs[j - 1] = -s[j - 1] * rs[j];
-         rs[j] = c[j - 1] * rs[j];
-      }
-      if (i) { ops.axpy(rs[i] - 1.0, p[i], p[i]); }
-      for (j = i - 1; j > 0; j--) { ops.axpy(rs[j], p[j], p[i]); }
-      if (i)
-      {
-         ops.axpy(rs[0] - 1.0, p[0], p[0]);
-         ops.axpy(1.0, p[i], p[0]);
-      }
+      restart_residual(ops, p, i, H);
       if (aug_dim > 0)
       {
          // where the new vector goes (lgmres.c:852-874): the next free slot, or that of the oldest one
@@ -237,7 +171,7 @@ LGMRESResult lgmres_iterate(const LGMRESParams &prm, Ops &ops, V b, V x, V r, V 
          else
          {
             ops.copy(aug[aug_dim], aug[spot]);
-            tmp_norm = 1.0 / norm(aug[spot]);
+            tmp_norm = 1.0 / krylov_norm(ops, aug[spot]);
             ops.scale(tmp_norm, aug[spot]);
             res.plain_updates += 3;
          }
@@ -255,10 +189,7 @@ LGMRESResult lgmres_iterate(const LGMRESParams &prm, Ops &ops, V b, V x, V r, V 
          }
       }
    }
-   res.iterations = iter;
-   res.iterations_set = res.norm_set = true;
-   res.rel_residual_norm = (b_norm > 0.0) ? r_norm / b_norm : r_norm;
-   if (iter >= max_iter && r_norm > epsilon && epsilon > 0) { res.status = GMRES_NOT_CONVERGED; }
+   krylov_finish(res, iter, r_norm, b_norm, epsilon, max_iter, false);       // lgmres.c:918: only when epsilon > 0
    return res;
 }
 

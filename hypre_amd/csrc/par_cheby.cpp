@@ -396,8 +396,7 @@ HYPRE_Int hypre_ParCSRRelax_Cheby_Solve(hypre_ParCSRMatrix *A, hypre_ParVector *
    order = std::min(std::max(order, 1), 4);
    const int cheby_order = order - 1;
    hipStream_t s = stream();
-   const int saved = handle().sync_compute;
-   handle().sync_compute = 0;
+   QuietSync quiet;
    double *ud = u->local_vector->data, *vd = v->local_vector->data, *rd = r->local_vector->data;
    double *od = orig_u_vec->local_vector->data;
    const double *fd = f->local_vector->data;
@@ -417,7 +416,7 @@ HYPRE_Int hypre_ParCSRRelax_Cheby_Solve(hypre_ParCSRMatrix *A, hypre_ParVector *
       launch_cheby_step(rd, vd, ds, od, coefs[i], i == 0, ud, td, (size_t) n, s);
    }
    u->all_zeros = 0;
-   handle().sync_compute = saved;
+   quiet.restore();
    maybe_sync();
    return hypre_error_flag;
 }

@@ -4,8 +4,9 @@
 //    FlexGMRES  HYPRE_ParCSRFlexGMRES* / HYPRE_FlexGMRES* `ij -solver 60 | 61`  krylov/flexgmres.c, parcsr_ls/HYPRE_parcsr_flexgmres.c
 //    LGMRES     HYPRE_ParCSRLGMRES* / HYPRE_LGMRES*       `ij -solver 50 | 51`  krylov/lgmres.c, parcsr_ls/HYPRE_parcsr_lgmres.c
 // The iteration itself (Hessenberg matrix, Givens rotations, every decision) is gmres_core.hpp, for LGMRES its sibling
-// lgmres_core.hpp; this file gives it the vectors, every inner product ending in one scalar read-back, and the entry
-// points.  The first three differ in the GMRESParams their Create fills in (the table is in DESIGN.md) and in two
+// lgmres_core.hpp, a loop of its own built from the same step functions; this file gives it the vectors, every inner
+// product ending in one scalar read-back, and the entry points (work vectors, preconditioner and the start of a solve
+// as PCG has them: krylov_common.hpp).  The first three differ in the GMRESParams their Create fills in (the table is in DESIGN.md) and in two
 // refusals: COGMRES Setup takes no multivectors, FlexGMRES Solve no host operands (LGMRES Solve neither).  The
 // relative-change and convergence-factor exits of the reference (rel_change, cf_tol) are not carried, by none of the four.
 //
@@ -21,7 +22,7 @@
 // restarts (keep the correction, rebuild r0, normalise the new augmentation vector, form A z = (r0 - r_m) / |w|) is
 // launch_copy_norm2, two launch_scale_copy and launch_scaled_diff: 4 launches and 72 bytes per element where the
 // reference's ten Copy / Scale / InnerProd / Axpy calls move 168.  The same bits either way.
-#include "amg_internal.hpp"
+#include "krylov_common.hpp"
 #include "lgmres_core.hpp"
 #include <cstring>
 #include <initializer_list>
@@ -35,8 +36,7 @@ struct hypre_amd_GMRESData
    hypre_Solver base;
    MPI_Comm comm;
    GMRESParams prm;
-   HYPRE_PtrToSolverFcn precond = nullptr, precond_setup = nullptr;
-   HYPRE_Solver precond_data = nullptr;
+   KrylovPrecond pc;
    HYPRE_PtrToModifyPCFcn modify_pc = nullptr;          // nullptr: hypre_FlexGMRESModifyPCDefault, which does nothing
    hypre_ParVector *r = nullptr, *w = nullptr;
    std::vector<hypre_ParVector *> p, pre_vecs;          // pre_vecs only if prm.flexible
@@ -88,13 +88,6 @@ HYPRE_Int set_k_dim(HYPRE_Solver s, HYPRE_Int v)
    return hypre_error_flag;
 }
 
-HYPRE_Int set_precond(HYPRE_Solver s, HYPRE_PtrToSolverFcn precond, HYPRE_PtrToSolverFcn precond_setup, HYPRE_Solver precond_solver)
-{
-   hypre_amd_GMRESData *d = D(s);
-   d->precond = precond; d->precond_setup = precond_setup; d->precond_data = precond_solver;
-   return hypre_error_flag;
-}
-
 bool on_device(hypre_ParVector *v) { return v->local_vector->memory_location == HYPRE_MEMORY_DEVICE; }
 
 // work vectors shaped like x (gmres.c:204-215, cogmres.c:220-231, flexgmres.c:230-250 CreateVector / CreateVectorArray):
@@ -103,9 +96,7 @@ HYPRE_Int setup(HYPRE_Solver solver, hypre_ParCSRMatrix *A, hypre_ParVector *b, 
 {
    hypre_amd_GMRESData *d = D(solver);
    free_vectors(d);
-   const HYPRE_MemoryLocation loc = x->local_vector->memory_location;
-   const HYPRE_Int nv = x->local_vector->num_vectors;
-   auto mk = [&]() { hypre_ParVector *v = hypre_ParMultiVectorCreate(A->comm, A->global_num_rows, A->row_starts, nv); hypre_ParVectorInitialize_v2(v, loc); return v; };
+   auto mk = [&]() { return par_vector_like(A, x); };
    d->r = mk(); d->w = mk();
    for (HYPRE_Int i = 0; i <= d->prm.k_dim; i++)
    {
@@ -117,7 +108,7 @@ HYPRE_Int setup(HYPRE_Solver solver, hypre_ParCSRMatrix *A, hypre_ParVector *b, 
       d->aug_vecs.push_back(mk());
       if (i < d->aug_dim) { d->a_aug_vecs.push_back(mk()); }
    }
-   if (d->precond_setup) { d->precond_setup(d->precond_data, A, b, x); }
+   if (d->pc.setup) { d->pc.setup(d->pc.data, A, b, x); }
    return hypre_error_flag;
 }
 
@@ -176,10 +167,7 @@ struct ParOps
    { hypre_ParVectorMassDotpTwo(x, y, zs, k, unroll, outx, outy); }
    void precond(int iter, double rel_norm, hypre_ParVector *rhs, hypre_ParVector *sol)
    {
-      hypre_ParVectorSetZeros(sol);        // ClearVector (gmres.c:538, cogmres.c:541, flexgmres.c:549): all_zeros = 1
-      if (d->modify_pc) { d->modify_pc(d->precond_data, iter, rel_norm); }
-      if (d->precond) { d->precond(d->precond_data, A, rhs, sol); }
-      else { hypre_ParVectorCopy(rhs, sol); }
+      d->pc.apply(A, rhs, sol, [&] { if (d->modify_pc) { d->modify_pc(d->pc.data, iter, rel_norm); } });
    }
    void solution_changed(hypre_ParVector *x) { x->all_zeros = 0; }
    void scaled_copy(double a, hypre_ParVector *x, hypre_ParVector *y) { scaled_copy_of(a, x, y); }
@@ -202,9 +190,7 @@ HYPRE_Int solve_with(hypre_amd_GMRESData *d, hypre_ParCSRMatrix *A, Iterate iter
 {
    d->converged = 0;
    d->fused_steps = d->plain_dots = d->plain_axpys = 0;
-   const int saved_sync = handle().sync_compute;
-   handle().sync_compute = 0;
-   verify_par_plans(A);                    // a solve never starts from a plan its matrix has moved away from
+   QuietSolve quiet(A);
    ParOps ops{d, A};
    const GMRESResult res = iterate(ops);
    if (res.iterations_set) { d->num_iterations = res.iterations; }
@@ -213,7 +199,7 @@ HYPRE_Int solve_with(hypre_amd_GMRESData *d, hypre_ParCSRMatrix *A, Iterate iter
    d->fused_steps = (HYPRE_Int) res.fused_steps; d->plain_dots = (HYPRE_Int) res.plain_dots; d->plain_axpys = (HYPRE_Int) res.plain_axpys;
    if (res.status == GMRES_NOT_A_NUMBER) { hypre_error(HYPRE_ERROR_GENERIC); }
    if (res.status == GMRES_NOT_CONVERGED) { hypre_error(HYPRE_ERROR_CONV); }
-   handle().sync_compute = saved_sync;
+   quiet.restore();
    maybe_sync();
    return hypre_error_flag;
 }
@@ -239,7 +225,7 @@ HYPRE_Int HYPRE_GMRESSetMaxIter(HYPRE_Solver s, HYPRE_Int v) { D(s)->prm.max_ite
 HYPRE_Int HYPRE_GMRESSetSkipRealResidualCheck(HYPRE_Solver s, HYPRE_Int v) { D(s)->prm.skip_real_r_check = v; return hypre_error_flag; }
 HYPRE_Int HYPRE_GMRESSetPrecond(HYPRE_Solver s, HYPRE_PtrToSolverFcn precond, HYPRE_PtrToSolverFcn precond_setup,
                                 HYPRE_Solver precond_solver)
-{ return set_precond(s, precond, precond_setup, precond_solver); }
+{ return D(s)->pc.set(precond, precond_setup, precond_solver); }
 HYPRE_Int HYPRE_GMRESSetLogging(HYPRE_Solver s, HYPRE_Int v) { (void) s; (void) v; return hypre_error_flag; }       // accepted, inert
 HYPRE_Int HYPRE_GMRESSetPrintLevel(HYPRE_Solver s, HYPRE_Int v) { (void) s; (void) v; return hypre_error_flag; }
 HYPRE_Int HYPRE_GMRESSetRelChange(HYPRE_Solver s, HYPRE_Int v)
@@ -282,7 +268,7 @@ HYPRE_Int HYPRE_COGMRESSetMaxIter(HYPRE_Solver s, HYPRE_Int v) { D(s)->prm.max_i
 HYPRE_Int HYPRE_COGMRESSetSkipRealResidualCheck(HYPRE_Solver s, HYPRE_Int v) { D(s)->prm.skip_real_r_check = v; return hypre_error_flag; }
 HYPRE_Int HYPRE_COGMRESSetPrecond(HYPRE_Solver s, HYPRE_PtrToSolverFcn precond, HYPRE_PtrToSolverFcn precond_setup,
                                   HYPRE_Solver precond_solver)
-{ return set_precond(s, precond, precond_setup, precond_solver); }
+{ return D(s)->pc.set(precond, precond_setup, precond_solver); }
 HYPRE_Int HYPRE_COGMRESSetLogging(HYPRE_Solver s, HYPRE_Int v) { (void) s; (void) v; return hypre_error_flag; }       // accepted, inert
 HYPRE_Int HYPRE_COGMRESSetPrintLevel(HYPRE_Solver s, HYPRE_Int v) { (void) s; (void) v; return hypre_error_flag; }
 HYPRE_Int HYPRE_COGMRESGetNumIterations(HYPRE_Solver s, HYPRE_Int *v) { *v = D(s)->num_iterations; return hypre_error_flag; }
@@ -336,8 +322,8 @@ HYPRE_Int HYPRE_FlexGMRESSetMinIter(HYPRE_Solver s, HYPRE_Int v) { D(s)->prm.min
 HYPRE_Int HYPRE_FlexGMRESSetMaxIter(HYPRE_Solver s, HYPRE_Int v) { D(s)->prm.max_iter = v; return hypre_error_flag; }
 HYPRE_Int HYPRE_FlexGMRESSetPrecond(HYPRE_Solver s, HYPRE_PtrToSolverFcn precond, HYPRE_PtrToSolverFcn precond_setup,
                                     HYPRE_Solver precond_solver)
-{ return set_precond(s, precond, precond_setup, precond_solver); }
-HYPRE_Int HYPRE_FlexGMRESGetPrecond(HYPRE_Solver s, HYPRE_Solver *precond_data_ptr) { *precond_data_ptr = D(s)->precond_data; return hypre_error_flag; }
+{ return D(s)->pc.set(precond, precond_setup, precond_solver); }
+HYPRE_Int HYPRE_FlexGMRESGetPrecond(HYPRE_Solver s, HYPRE_Solver *precond_data_ptr) { *precond_data_ptr = D(s)->pc.data; return hypre_error_flag; }
 HYPRE_Int HYPRE_FlexGMRESSetModifyPC(HYPRE_Solver s, HYPRE_PtrToModifyPCFcn modify_pc) { D(s)->modify_pc = modify_pc; return hypre_error_flag; }
 HYPRE_Int HYPRE_FlexGMRESSetLogging(HYPRE_Solver s, HYPRE_Int v) { (void) s; (void) v; return hypre_error_flag; }       // accepted, inert
 HYPRE_Int HYPRE_FlexGMRESSetPrintLevel(HYPRE_Solver s, HYPRE_Int v) { (void) s; (void) v; return hypre_error_flag; }
@@ -418,9 +404,7 @@ HYPRE_Int HYPRE_ParCSRFlexGMRESGetFinalRelativeResidualNorm(HYPRE_Solver s, HYPR
 // a_tol 0, min_iter 0, max_iter 1000; the iteration is lgmres_iterate, fused
 HYPRE_Int HYPRE_ParCSRLGMRESCreate(MPI_Comm comm, HYPRE_Solver *solver)
 {
-   GMRESParams prm;
-   prm.k_dim = 20;
-   create(comm, solver, prm);
+   create(comm, solver, LGMRESParams());            // kept as GMRESParams: k_dim 20, the rest of the defaults are the same
    D(*solver)->aug_dim = 2;
    return hypre_error_flag;
 }
@@ -439,8 +423,8 @@ HYPRE_Int HYPRE_LGMRESSetMinIter(HYPRE_Solver s, HYPRE_Int v) { D(s)->prm.min_it
 HYPRE_Int HYPRE_LGMRESSetMaxIter(HYPRE_Solver s, HYPRE_Int v) { D(s)->prm.max_iter = v; return hypre_error_flag; }
 HYPRE_Int HYPRE_LGMRESSetPrecond(HYPRE_Solver s, HYPRE_PtrToSolverFcn precond, HYPRE_PtrToSolverFcn precond_setup,
                                  HYPRE_Solver precond_solver)
-{ return set_precond(s, precond, precond_setup, precond_solver); }
-HYPRE_Int HYPRE_LGMRESGetPrecond(HYPRE_Solver s, HYPRE_Solver *precond_data_ptr) { *precond_data_ptr = D(s)->precond_data; return hypre_error_flag; }
+{ return D(s)->pc.set(precond, precond_setup, precond_solver); }
+HYPRE_Int HYPRE_LGMRESGetPrecond(HYPRE_Solver s, HYPRE_Solver *precond_data_ptr) { *precond_data_ptr = D(s)->pc.data; return hypre_error_flag; }
 HYPRE_Int HYPRE_LGMRESSetLogging(HYPRE_Solver s, HYPRE_Int v) { (void) s; (void) v; return hypre_error_flag; }       // accepted, inert
 HYPRE_Int HYPRE_LGMRESSetPrintLevel(HYPRE_Solver s, HYPRE_Int v) { (void) s; (void) v; return hypre_error_flag; }
 HYPRE_Int HYPRE_LGMRESGetNumIterations(HYPRE_Solver s, HYPRE_Int *v) { *v = D(s)->num_iterations; return hypre_error_flag; }
@@ -495,9 +479,8 @@ HYPRE_Int HYPRE_ParCSRLGMRESSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYP
       return hypre_error_flag;
    }
    LGMRESParams prm;
-   prm.k_dim = d->prm.k_dim; prm.aug_dim = d->aug_dim; prm.approx_constant = d->approx_constant;
-   prm.min_iter = d->prm.min_iter; prm.max_iter = d->prm.max_iter; prm.tol = d->prm.tol; prm.a_tol = d->prm.a_tol;
-   prm.fused = d->fused_updates_on != 0;
+   static_cast<GMRESParams &>(prm) = d->prm;
+   prm.aug_dim = d->aug_dim; prm.approx_constant = d->approx_constant; prm.fused = d->fused_updates_on != 0;
    d->fused_updates = d->plain_updates = 0;
    return solve_with(d, A, [&](ParOps &ops) {
       const LGMRESResult res = lgmres_iterate<hypre_ParVector *>(prm, ops, b, x, d->r, d->w, d->p.data(), d->aug_vecs.data(), d->a_aug_vecs.data());

@@ -217,8 +217,7 @@ extern "C" HYPRE_Int hypre_BoomerAMGRelaxHybridGaussSeidelDevice(hypre_ParCSRMat
       return hypre_error_flag;
    }
    hipStream_t s = stream();
-   const int saved = handle().sync_compute;
-   handle().sync_compute = 0;
+   QuietSync quiet;
    double *ud = u->local_vector->data;
    double *vt = Vtemp->local_vector->data, *zt = Ztemp->local_vector->data;
    HYPRE_Int nprocs;
@@ -262,7 +261,7 @@ extern "C" HYPRE_Int hypre_BoomerAMGRelaxHybridGaussSeidelDevice(hypre_ParCSRMat
       run_direction(g->dir[dirn > 0 ? 0 : 1], g->lanes, a, s);
    }
    u->all_zeros = 0;               // the sweep has written u (relax 89 calls this twice: the second sweep must fetch ghosts)
-   handle().sync_compute = saved;
+   quiet.restore();
    maybe_sync();
    return hypre_error_flag;
 }

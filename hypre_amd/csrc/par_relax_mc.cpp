@@ -247,8 +247,7 @@ HYPRE_Int hypre_BoomerAMGRelaxMultiColorGaussSeidelDevice(hypre_ParCSRMatrix *A,
       return hypre_error_flag;
    }
    hipStream_t s = stream();
-   const int saved = handle().sync_compute;
-   handle().sync_compute = 0;
+   QuietSync quiet;
    double *ud = u->local_vector->data;
    const double *fd = f->local_vector->data;
    HYPRE_Int nprocs;
@@ -330,7 +329,7 @@ HYPRE_Int hypre_BoomerAMGRelaxMultiColorGaussSeidelDevice(hypre_ParCSRMatrix *A,
    if (direction > 0) { sweep_tail(); }
    }
    u->all_zeros = 0;
-   handle().sync_compute = saved;
+   quiet.restore();
    maybe_sync();
    return hypre_error_flag;
 }

@@ -1,5 +1,5 @@
 // hypre_amd — the BoomerAMG solve phase on the device: relaxation sweeps, the
-// V/W/F cycle, the outer solve loop and the PCG caller.
+// V/W/F cycle and the outer solve loop.
 //
 // Reference counterparts (behaviour; the structure is MI355X-first):
 //   parcsr_ls/par_relax.c:24-173,1178-1254,1506-1666   relaxation dispatcher, Jacobi, two-stage GS
@@ -8,7 +8,6 @@
 //   parcsr_ls/par_gauss_elim.c:457-697                 coarsest-level solve
 //   parcsr_ls/par_cycle.c:23-803                       cycle state machine
 //   parcsr_ls/par_amg_solve.c:22-424                   outer loop, convergence test
-//   krylov/pcg.c:318-1000                              PCG
 //
 // What is different from the reference's device path:
 //   * a Jacobi / l1-Jacobi sweep is ONE pass over the matrix (SpMV with the
@@ -200,8 +199,7 @@ HYPRE_Int hypre_BoomerAMGRelaxTwoStageGaussSeidelDevice(hypre_ParCSRMatrix *A, h
    hypre_CSRMatrix *diag = A->diag;
    const int n = diag->num_rows;
    double *ud = u->local_vector->data, *rd = r->local_vector->data, *zd = z->local_vector->data;
-   const int saved = handle().sync_compute;
-   handle().sync_compute = 0;
+   QuietSync quiet;
    // 0) r = w (f - A u)     1) z = r./D ; u += z
    // u known to be zero (par_vector.h all_zeros; set by SetZeros and by the cycle on the way down):
    // A u = 0 exactly, so r = w f without touching the matrix.  The reference uses the flag this way
@@ -277,7 +275,7 @@ HYPRE_Int hypre_BoomerAMGRelaxTwoStageGaussSeidelDevice(hypre_ParCSRMatrix *A, h
       }
    }
    u->all_zeros = 0;
-   handle().sync_compute = saved;
+   quiet.restore();
    maybe_sync();
    return hypre_error_flag;
 }
@@ -292,8 +290,7 @@ HYPRE_Int hypre_BoomerAMGRelax(hypre_ParCSRMatrix *A, hypre_ParVector *f, HYPRE_
    HYPRE_AMD_REQUIRE_DEVICE(f->local_vector->memory_location, "hypre_BoomerAMGRelax(f)");
    hipStream_t s = stream();
    const int n = A->diag->num_rows;
-   const int saved = handle().sync_compute;
-   handle().sync_compute = 0;
+   QuietSync quiet;
    double *ud = u->local_vector->data;
    const double *fd = f->local_vector->data;
    switch (relax_type)
@@ -360,7 +357,7 @@ HYPRE_Int hypre_BoomerAMGRelax(hypre_ParCSRMatrix *A, hypre_ParVector *f, HYPRE_
          break;
    }
    u->all_zeros = 0;
-   handle().sync_compute = saved;
+   quiet.restore();
    maybe_sync();
    return 0;     // relax_error (par_relax.c:36,172)
 }
@@ -745,8 +742,7 @@ static HYPRE_Int amg_cycle_from(void *amg_vdata, hypre_ParVector **F_array, hypr
    HYPRE_AMD_REQUIRE_DEVICE(U_array[0]->local_vector->memory_location, "hypre_BoomerAMGCycle(u)");
    HYPRE_AMD_REQUIRE_DEVICE(F_array[0]->local_vector->memory_location, "hypre_BoomerAMGCycle(f)");
    hipStream_t s = stream();
-   const int saved_sync = handle().sync_compute;
-   handle().sync_compute = 0;
+   QuietSync quiet;
    const int saved_gs_threads = handle().gs_threads;
    handle().gs_threads = pv->emulated_threads;
    const bool saved_fp32 = handle().fp32_values;
@@ -1194,7 +1190,7 @@ static HYPRE_Int amg_cycle_from(void *amg_vdata, hypre_ParVector **F_array, hypr
    handle().fp32_values = saved_fp32;
    hypre_amd_CommSetTag(-1);
    handle().gs_threads = saved_gs_threads;
-   handle().sync_compute = saved_sync;
+   quiet.restore();
    maybe_sync();
    return err;
 }
@@ -1472,8 +1468,7 @@ static HYPRE_Int amg_solve_columns(hypre_ParAMGData *d, hypre_ParCSRMatrix *A, h
 
    AmgPrivate *pv = (AmgPrivate *) d->amd_private;
    const HYPRE_Real tol = d->tol;
-   const int saved_sync = handle().sync_compute;
-   handle().sync_compute = 0;
+   QuietSync quiet;
    if (d->max_iter > 1) { verify_par_plans(A); }
    d->A_array[0] = A;
    hypre_ParVectorSetLocalSize(d->Vtemp, n);
@@ -1517,7 +1512,6 @@ static HYPRE_Int amg_solve_columns(hypre_ParAMGData *d, hypre_ParCSRMatrix *A, h
       if (ieee_check != ieee_check)
       {
          if (d->print_level > 0) { fprintf(stderr, "ERROR -- hypre_BoomerAMGSolve: INFs and/or NaNs detected in input.\n"); }
-         handle().sync_compute = saved_sync;
          d->F_array[0] = f; d->U_array[0] = u;
          hypre_error(HYPRE_ERROR_GENERIC);
          return hypre_error_flag;
@@ -1569,7 +1563,7 @@ static HYPRE_Int amg_solve_columns(hypre_ParAMGData *d, hypre_ParCSRMatrix *A, h
    }
    d->F_array[0] = f; d->U_array[0] = u;        // (no view of a column outlives the call)
    if (cycle_count == d->max_iter && tol > 0.) { hypre_error(HYPRE_ERROR_CONV); }
-   handle().sync_compute = saved_sync;
+   quiet.restore();
    maybe_sync();
    return hypre_error_flag;
 }
@@ -1591,8 +1585,7 @@ HYPRE_Int hypre_BoomerAMGSolve(void *amg_vdata, hypre_ParCSRMatrix *A, hypre_Par
    HYPRE_AMD_REQUIRE_DEVICE(u->local_vector->memory_location, "hypre_BoomerAMGSolve(u)");
    if (f->local_vector->num_vectors != 1 || u->local_vector->num_vectors != 1) { return amg_solve_columns(d, A, f, u); }
    const HYPRE_Real tol = d->tol;
-   const int saved_sync = handle().sync_compute;
-   handle().sync_compute = 0;
+   QuietSync quiet;
    // stand-alone solver (more than one cycle allowed): the fine-level plans are verified against the caller's arrays once
    // per solve (one pass over the CSR arrays; a Krylov method that applies one cycle per iteration does it itself, once per
    // solve — HYPRE_ParCSRPCGSolve / GMRESSolve)
@@ -1617,7 +1610,6 @@ HYPRE_Int hypre_BoomerAMGSolve(void *amg_vdata, hypre_ParCSRMatrix *A, hypre_Par
          {
             fprintf(stderr, "ERROR -- hypre_BoomerAMGSolve: INFs and/or NaNs detected in input.\n");
          }
-         handle().sync_compute = saved_sync;
          hypre_error(HYPRE_ERROR_GENERIC);
          return hypre_error_flag;
       }
@@ -1688,192 +1680,7 @@ HYPRE_Int hypre_BoomerAMGSolve(void *amg_vdata, hypre_ParCSRMatrix *A, hypre_Par
       hypre_error(HYPRE_ERROR_CONV);
    }
    (void) Solve_err_flag;
-   handle().sync_compute = saved_sync;
-   maybe_sync();
-   return hypre_error_flag;
-}
-
-// ===========================================================================
-// PCG (krylov/pcg.c:318-1000 with the defaults flex = rel_change = 0,
-// recompute_residual = 0, stop_crit = 0, atolf = 0, cf_tol = 0)
-// ===========================================================================
-struct hypre_amd_PCGData
-{
-   hypre_Solver base;
-   MPI_Comm comm;
-   HYPRE_Real tol = 1e-6, a_tol = 0.0;
-   HYPRE_Int max_iter = 1000, two_norm = 0, flex = 0;
-   HYPRE_PtrToSolverFcn precond = nullptr, precond_setup = nullptr;
-   HYPRE_Solver precond_data = nullptr;
-   hypre_ParVector *p = nullptr, *s = nullptr, *r = nullptr, *r_old = nullptr;
-   double *d_rr = nullptr;       // device scalar of this solver: <r,r> of the fused update survives the preconditioner call
-                                 // (which may itself run a PCG: the CG smoother)
-   HYPRE_Int num_iterations = 0, converged = 0;
-   HYPRE_Real rel_residual_norm = 0.0;
-};
-
-HYPRE_Int HYPRE_ParCSRPCGCreate(MPI_Comm comm, HYPRE_Solver *solver)
-{
-   hypre_amd_PCGData *d = new hypre_amd_PCGData();
-   memset(&d->base, 0, sizeof(d->base));
-   d->comm = comm;
-   *solver = (HYPRE_Solver) d;
-   return hypre_error_flag;
-}
-HYPRE_Int HYPRE_ParCSRPCGDestroy(HYPRE_Solver solver)
-{
-   hypre_amd_PCGData *d = (hypre_amd_PCGData *) solver;
-   if (!d) { return hypre_error_flag; }
-   hypre_ParVectorDestroy(d->p); hypre_ParVectorDestroy(d->s); hypre_ParVectorDestroy(d->r); hypre_ParVectorDestroy(d->r_old);
-   if (d->d_rr) { hypre_Free(d->d_rr, HYPRE_MEMORY_DEVICE); }
-   delete d;
-   return hypre_error_flag;
-}
-HYPRE_Int HYPRE_PCGSetTol(HYPRE_Solver s, HYPRE_Real v) { ((hypre_amd_PCGData *) s)->tol = v; return hypre_error_flag; }
-HYPRE_Int HYPRE_PCGSetAbsoluteTol(HYPRE_Solver s, HYPRE_Real v) { ((hypre_amd_PCGData *) s)->a_tol = v; return hypre_error_flag; }
-HYPRE_Int HYPRE_PCGSetMaxIter(HYPRE_Solver s, HYPRE_Int v) { ((hypre_amd_PCGData *) s)->max_iter = v; return hypre_error_flag; }
-HYPRE_Int HYPRE_PCGSetTwoNorm(HYPRE_Solver s, HYPRE_Int v) { ((hypre_amd_PCGData *) s)->two_norm = v; return hypre_error_flag; }
-// pcg.c:339-345: Polak-Ribiere beta instead of Fletcher-Reeves, for preconditioners that change between iterations
-HYPRE_Int HYPRE_PCGSetFlex(HYPRE_Solver s, HYPRE_Int v) { ((hypre_amd_PCGData *) s)->flex = v; return hypre_error_flag; }
-HYPRE_Int HYPRE_PCGSetPrecond(HYPRE_Solver s, HYPRE_PtrToSolverFcn precond, HYPRE_PtrToSolverFcn precond_setup,
-                              HYPRE_Solver precond_solver)
-{
-   hypre_amd_PCGData *d = (hypre_amd_PCGData *) s;
-   d->precond = precond; d->precond_setup = precond_setup; d->precond_data = precond_solver;
-   return hypre_error_flag;
-}
-// options of krylov/HYPRE_pcg.c an application sets routinely: logging and printing are accepted and inert (this PCG
-// keeps no residual history and prints nothing); the relative-change and recomputed-residual variants are not built
-HYPRE_Int HYPRE_PCGSetLogging(HYPRE_Solver s, HYPRE_Int v) { (void) s; (void) v; return hypre_error_flag; }
-HYPRE_Int HYPRE_PCGSetPrintLevel(HYPRE_Solver s, HYPRE_Int v) { (void) s; (void) v; return hypre_error_flag; }
-HYPRE_Int HYPRE_PCGSetRelChange(HYPRE_Solver s, HYPRE_Int v)
-{
-   (void) s;
-   if (v != 0) { hypre_error_in_arg(2); hypre_error_w_msg(HYPRE_ERROR_GENERIC, "HYPRE_PCGSetRelChange: the relative-change stopping test is not built (0 only)"); }
-   return hypre_error_flag;
-}
-HYPRE_Int HYPRE_PCGSetRecomputeResidual(HYPRE_Solver s, HYPRE_Int v)
-{
-   (void) s;
-   if (v != 0) { hypre_error_in_arg(2); hypre_error_w_msg(HYPRE_ERROR_GENERIC, "HYPRE_PCGSetRecomputeResidual: 0 only"); }
-   return hypre_error_flag;
-}
-HYPRE_Int HYPRE_PCGGetNumIterations(HYPRE_Solver s, HYPRE_Int *v) { *v = ((hypre_amd_PCGData *) s)->num_iterations; return hypre_error_flag; }
-HYPRE_Int HYPRE_PCGGetFinalRelativeResidualNorm(HYPRE_Solver s, HYPRE_Real *v) { *v = ((hypre_amd_PCGData *) s)->rel_residual_norm; return hypre_error_flag; }
-
-HYPRE_Int HYPRE_ParCSRPCGSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x)
-{
-   hypre_amd_PCGData *d = (hypre_amd_PCGData *) solver;
-   hypre_ParVectorDestroy(d->p); hypre_ParVectorDestroy(d->s); hypre_ParVectorDestroy(d->r); hypre_ParVectorDestroy(d->r_old);
-   const HYPRE_MemoryLocation loc = x->local_vector->memory_location;
-   // work vectors shaped like x (krylov/pcg.c:226-260 CreateVector(x)): as many columns as a multivector x has (`ij -nc N`)
-   const HYPRE_Int nv = x->local_vector->num_vectors;
-   auto mk = [&]() { hypre_ParVector *v = hypre_ParMultiVectorCreate(A->comm, A->global_num_rows, A->row_starts, nv); hypre_ParVectorInitialize_v2(v, loc); return v; };
-   d->p = mk(); d->s = mk(); d->r = mk();
-   d->r_old = d->flex ? mk() : nullptr;
-   if (!d->d_rr && loc == HYPRE_MEMORY_DEVICE) { d->d_rr = hypre_TAlloc(double, 2, HYPRE_MEMORY_DEVICE); }
-   if (d->precond_setup) { d->precond_setup(d->precond_data, A, b, x); }
-   return hypre_error_flag;
-}
-
-HYPRE_Int HYPRE_ParCSRPCGSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x)
-{
-   hypre_amd_PCGData *d = (hypre_amd_PCGData *) solver;
-   hypre_ParVector *p = d->p, *s = d->s, *r = d->r;
-   const HYPRE_Real r_tol = d->tol, a_tol = d->a_tol;
-   HYPRE_Real alpha, beta, gamma, gamma_old, bi_prod, eps, sdotp, i_prod = 0.0, i_prod_0 = 0.0, delta = 0.0;
-   HYPRE_Int i = 0;
-   d->converged = 0;
-   if (d->flex && !d->r_old)
-   {
-      hypre_error_w_msg(HYPRE_ERROR_GENERIC, "HYPRE_ParCSRPCGSolve: call HYPRE_ParCSRPCGSetup after HYPRE_PCGSetFlex");
-      return hypre_error_flag;
-   }
-   // multivectors (`ij -nc N`, test/TEST_ij/vector.jobs): the reference's PCG works on whatever its vector functions take,
-   // and hypre_ParVector's take every column — one Krylov iteration over the columns together.  The fused updates below
-   // run over the columns' common storage, which has to be one piece.
-   const HYPRE_Int nvec = x->local_vector->num_vectors;
-   for (hypre_ParVector *v : {b, x, p, s, r})
-   {
-      const hypre_Vector *l = v->local_vector;
-      if (l->num_vectors != nvec || (nvec > 1 && (l->idxstride != 1 || l->vecstride != l->size)))
-      {
-         hypre_error_w_msg(HYPRE_ERROR_GENERIC, "HYPRE_ParCSRPCGSolve: b, x and the work vectors of HYPRE_ParCSRPCGSetup must have the same number of "
-                                                "columns, stored one after the other");
-         return hypre_error_flag;
-      }
-   }
-   const size_t vec_len = (size_t) r->local_vector->size * (size_t) nvec;
-   const int saved_sync = handle().sync_compute;
-   handle().sync_compute = 0;
-   verify_par_plans(A);                    // a solve never starts from a plan its matrix has moved away from
-   auto precond = [&](hypre_ParVector *rhs, hypre_ParVector *sol)
-   {
-      hypre_ParVectorSetZeros(sol);       // ClearVector: all_zeros = 1 (par_vector.c:335-340)
-      if (d->precond) { d->precond(d->precond_data, A, rhs, sol); }
-      else { hypre_ParVectorCopy(rhs, sol); }
-   };
-   if (d->two_norm) { bi_prod = hypre_ParVectorInnerProd(b, b); }
-   else { precond(b, p); bi_prod = hypre_ParVectorInnerProd(p, b); }
-   HYPRE_Real ieee_check = 0.;
-   if (bi_prod != 0.) { ieee_check = bi_prod / bi_prod; }
-   if (ieee_check != ieee_check) { handle().sync_compute = saved_sync; hypre_error(HYPRE_ERROR_GENERIC); return hypre_error_flag; }
-   eps = r_tol * r_tol;
-   if (bi_prod > 0.0) { eps = std::max(r_tol * r_tol, a_tol * a_tol / bi_prod); }
-   else
-   {
-      hypre_ParVectorCopy(b, x);
-      d->num_iterations = 0; d->rel_residual_norm = 0.0;
-      handle().sync_compute = saved_sync;
-      return hypre_error_flag;
-   }
-   hypre_ParVectorCopy(b, r);
-   hypre_ParCSRMatrixMatvec(-1.0, A, x, 1.0, r);
-   precond(r, p);
-   gamma = hypre_ParVectorInnerProd(r, p);
-   if (gamma != 0.) { ieee_check = gamma / gamma; }
-   if (ieee_check != ieee_check) { handle().sync_compute = saved_sync; hypre_error(HYPRE_ERROR_GENERIC); return hypre_error_flag; }
-   i_prod_0 = d->two_norm ? hypre_ParVectorInnerProd(r, r) : gamma;
-   while ((i + 1) <= d->max_iter)
-   {
-      i++;
-      hypre_ParCSRMatrixMatvec(1.0, A, p, 0.0, s);
-      sdotp = hypre_ParVectorInnerProd(s, p);
-      if (sdotp == 0.0) { hypre_error_w_msg(HYPRE_ERROR_CONV, "Zero sdotp value in PCG"); if (i == 1) { i_prod = i_prod_0; } break; }
-      alpha = gamma / sdotp;
-      if (alpha <= 0.0) { hypre_error_w_msg(HYPRE_ERROR_CONV, "Negative or zero alpha value in PCG"); if (i == 1) { i_prod = i_prod_0; } break; }
-      gamma_old = gamma;
-      // x += alpha p ; r -= alpha s ; <r,r> of the new residual: one pass (pcg.c:716-760 makes
-      // three vector calls of it; element values and the norm's summation order are unchanged)
-      if (d->flex) { hypre_ParVectorCopy(r, d->r_old); }          // pcg.c:636-639
-      double *d_rr = d->d_rr;
-      launch_pcg_update(alpha, -alpha, p->local_vector->data, s->local_vector->data, x->local_vector->data,
-                        r->local_vector->data, vec_len, d_rr, stream());
-      x->all_zeros = 0; r->all_zeros = 0;
-      precond(r, s);
-      // gamma = <r, s> and, for the two-norm test, <r, r> (left on the device by the fused update): ONE all-reduce of
-      // two values and one read-back per iteration (pcg.c:716-760 reduces them separately)
-      launch_dot(r->local_vector->data, s->local_vector->data, vec_len, d_rr + 1, stream());
-      {
-         double sums[2];
-         dev_global_sums(r->comm, d_rr, 2, sums);
-         gamma = sums[1];
-         i_prod = d->two_norm ? sums[0] : gamma;
-      }
-      if (d->flex) { delta = gamma - hypre_ParVectorInnerProd(d->r_old, s); }      // pcg.c:720-723
-      if (i_prod / bi_prod < eps) { d->converged = 1; break; }
-      if (gamma <= 0.0) { hypre_error_w_msg(HYPRE_ERROR_CONV, "Negative or zero gamma value in PCG"); break; }
-      beta = (d->flex ? delta : gamma) / gamma_old;                 // pcg.c:957-965
-      // p = beta p + s in one pass (Scale then Axpy in the reference)
-      launch_pcg_direction(beta, s->local_vector->data, p->local_vector->data, vec_len, stream());
-   }
-   if (i >= d->max_iter && (i_prod / bi_prod) >= eps && eps > 0)
-   {
-      hypre_error_w_msg(HYPRE_ERROR_CONV, "Reached max iterations in PCG before convergence");
-   }
-   d->num_iterations = i;
-   d->rel_residual_norm = std::sqrt(i_prod / bi_prod);
-   handle().sync_compute = saved_sync;
+   quiet.restore();
    maybe_sync();
    return hypre_error_flag;
 }

@@ -935,8 +935,7 @@ HYPRE_Int hypre_ParCSRMatrixMatvecOutOfPlaceDevice(HYPRE_Complex alpha, hypre_Pa
          hypre_error_w_msg(HYPRE_ERROR_GENERIC, "hypre_ParCSRMatrixMatvec: multivectors must agree in num_vectors and be stored column by column");
          return hypre_error_flag;
       }
-      const int saved = handle().sync_compute;
-      handle().sync_compute = 0;
+      QuietSync quiet;
       HYPRE_Int np;
       hypre_MPI_Comm_size(A->comm, &np);
       if (np > 1 && !A->comm_pkg) { hypre_MatvecCommPkgCreate(A); }
@@ -974,7 +973,7 @@ HYPRE_Int hypre_ParCSRMatrixMatvecOutOfPlaceDevice(HYPRE_Complex alpha, hypre_Pa
          HIP_CHECK(hipStreamSynchronize(stream()));          // the buffers go away with the switch back
          hypre_ParCSRCommPkgUpdateVecStarts(pkg, 1, xl->vecstride, xl->idxstride);
       }
-      handle().sync_compute = saved;
+      quiet.restore();
       maybe_sync();
       return hypre_error_flag;
    }
@@ -982,8 +981,7 @@ HYPRE_Int hypre_ParCSRMatrixMatvecOutOfPlaceDevice(HYPRE_Complex alpha, hypre_Pa
    HYPRE_Int nprocs;
    hypre_MPI_Comm_size(A->comm, &nprocs);
 
-   const int saved_sync = handle().sync_compute;
-   handle().sync_compute = 0;
+   QuietSync quiet;
 
    // x halo: pack on the compute stream, grouped send/recv on the comm stream
    hypre_ParCSRCommHandle *ch = hamd::dev_halo_begin(A, xl->data);
@@ -1004,7 +1002,7 @@ HYPRE_Int hypre_ParCSRMatrixMatvecOutOfPlaceDevice(HYPRE_Complex alpha, hypre_Pa
    {
       hypre_CSRMatrixMatvecDevice(0, alpha, offd, &x_ghost, 1.0, yl, yl, 0);
    }
-   handle().sync_compute = saved_sync;
+   quiet.restore();
    maybe_sync();
    return hypre_error_flag;
 }
@@ -1059,8 +1057,7 @@ HYPRE_Int hypre_ParCSRMatrixMatvecTDevice(HYPRE_Complex alpha, hypre_ParCSRMatri
          hypre_error_w_msg(HYPRE_ERROR_GENERIC, "hypre_ParCSRMatrixMatvecT: multivectors must agree in num_vectors and be stored column by column");
          return hypre_error_flag;
       }
-      const int saved = handle().sync_compute;
-      handle().sync_compute = 0;
+      QuietSync quiet;
       HYPRE_Int np;
       hypre_MPI_Comm_size(A->comm, &np);
       if (np > 1 && !A->comm_pkg) { hypre_MatvecCommPkgCreate(A); }
@@ -1113,7 +1110,7 @@ HYPRE_Int hypre_ParCSRMatrixMatvecTDevice(HYPRE_Complex alpha, hypre_ParCSRMatri
          HIP_CHECK(hipStreamSynchronize(stream()));
          hypre_ParCSRCommPkgUpdateVecStarts(pkg, 1, yl->vecstride, yl->idxstride);
       }
-      handle().sync_compute = saved;
+      quiet.restore();
       maybe_sync();
       return hypre_error_flag;
    }
@@ -1121,8 +1118,7 @@ HYPRE_Int hypre_ParCSRMatrixMatvecTDevice(HYPRE_Complex alpha, hypre_ParCSRMatri
    HYPRE_Int nprocs;
    hypre_MPI_Comm_size(A->comm, &nprocs);
 
-   const int saved_sync = handle().sync_compute;
-   handle().sync_compute = 0;
+   QuietSync quiet;
 
    hypre_ParCSRCommHandle *ch = nullptr;
    hypre_ParCSRCommPkg *pkg = nullptr;
@@ -1164,7 +1160,7 @@ HYPRE_Int hypre_ParCSRMatrixMatvecTDevice(HYPRE_Complex alpha, hypre_ParCSRMatri
          handle().fp32_values = mp;
       }
    }
-   handle().sync_compute = saved_sync;
+   quiet.restore();
    maybe_sync();
    return hypre_error_flag;
 }

@@ -1,7 +1,7 @@
 // Stand-alone host check of the restarted-GMRES iteration (hypre_amd/csrc/gmres_core.hpp): the Hessenberg / Givens /
 // restart logic that par_gmres.cpp runs for GMRES, COGMRES and FlexGMRES, with plain arrays behind the vector callbacks,
 // on a dense non-symmetric system of 50 unknowns.  Meant to be built with
-//    c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I hypre_amd/csrc
+//    c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off -I hypre_amd/csrc
 // and run once (tests/test_gmres_host.py does): any out-of-bounds index into hh / uu / rv / rs / c / s, the basis arrays
 // or the coefficient lists of the batched operations ends the program.  It also checks what it computes, for every
 // combination of flexible / not and Gram-Schmidt variant that an entry point uses: convergence across several restarts,
@@ -9,89 +9,26 @@
 // the "not converged" end, the zero right-hand side, a NaN, the exit on a residual that stopped falling, and for the
 // flexible variant the modify_pc protocol with a preconditioner that changes every iteration.
 #include "gmres_core.hpp"
-#include <cstdio>
-#include <cstdlib>
-#include <memory>
+#include "dense_ops.hpp"
 
-using Vec = std::vector<double>;
 using hamd::GMRESOrtho;
 
-struct DenseOps
-{
-   int n;
-   const Vec &A;                      // row-major n x n
-   double omega = 1.0;                // damping of the Jacobi preconditioner
-   int calls = 0;
-   double last_rel = 0.0;
-   bool rel_in_order = true;
-   int k_dim;
-   bool vary;                         // omega changes with every precond call: only a flexible solver may be given that
-   int wrong_from = 0;                // from this iteration on the preconditioner answers 100 times too large (0: never)
-   void matvec(double alpha, Vec *x, double beta, Vec *y)
-   {
-      for (int i = 0; i < n; i++)
-      {
-         double t = 0.0;
-         for (int j = 0; j < n; j++) { t += A[(size_t) i * n + j] * (*x)[j]; }
-         (*y)[i] = alpha * t + beta * (*y)[i];
-      }
-   }
-   double inner(Vec *x, Vec *y) { double t = 0.0; for (int i = 0; i < n; i++) { t += (*x)[i] * (*y)[i]; } return t; }
-   void copy(Vec *x, Vec *y) { *y = *x; }
-   void scale(double a, Vec *y) { for (double &v : *y) { v *= a; } }
-   void axpy(double a, Vec *x, Vec *y) { for (int i = 0; i < n; i++) { (*y)[i] += a * (*x)[i]; } }
-   double axpy_dot(double a, Vec *x, Vec *y, Vec *z) { axpy(a, x, y); return inner(z, y); }
-   void mass_axpy(double *a, Vec **xs, Vec *y, int k, int) { for (int j = 0; j < k; j++) { axpy(a[j], xs[j], y); } }
-   void mass_inner(Vec *x, Vec **ys, int k, int, double *out) { for (int j = 0; j < k; j++) { out[j] = inner(x, ys[j]); } }
-   void mass_dot_two(Vec *x, Vec *y, Vec **zs, int k, int, double *outx, double *outy)
-   {
-      for (int j = 0; j < k; j++) { outx[j] = inner(x, zs[j]); outy[j] = inner(y, zs[j]); }
-   }
-   void precond(int iter, double rel, Vec *rhs, Vec *sol)
-   {
-      calls++;
-      if (iter != calls) { rel_in_order = false; }
-      if ((iter - 1) % k_dim != 0 && rel > last_rel) { rel_in_order = false; }      // non-increasing inside a restart cycle
-      last_rel = rel;
-      if (vary) { omega = (iter % 2) ? 1.0 : 0.6; }
-      const double f = (wrong_from && iter >= wrong_from) ? 100.0 * omega : omega;
-      for (int i = 0; i < n; i++) { (*sol)[i] = f * (*rhs)[i] / A[(size_t) i * n + i]; }
-   }
-   void solution_changed(Vec *) {}
-};
-
-struct Run { hamd::GMRESResult res; Vec x; int calls; bool in_order; };
+struct Run { hamd::GMRESResult res; Vec x; int calls; bool in_order; std::uint64_t trace; };
 
 static Run solve(const Vec &A, const Vec &b_in, int n, const hamd::GMRESParams &prm, int wrong_from = 0)
 {
    Vec b = b_in, x((size_t) n, 0.0), r((size_t) n), w((size_t) n);
-   // exactly k_dim + 1 vectors each, allocated one by one: an index past the end is a heap overflow the sanitizer sees;
-   // a solver that is not flexible gets no pre at all
-   std::vector<std::unique_ptr<Vec>> ps, zs;
-   std::vector<Vec *> p, z;
-   for (int i = 0; i <= prm.k_dim; i++)
-   {
-      ps.emplace_back(new Vec((size_t) n, 0.0));
-      p.push_back(ps.back().get());
-      if (prm.flexible) { zs.emplace_back(new Vec((size_t) n, 0.0)); z.push_back(zs.back().get()); }
-   }
-   DenseOps ops{n, A, 1.0, 0, 0.0, true, prm.k_dim, prm.flexible, wrong_from};
+   // exactly k_dim + 1 vectors each; a solver that is not flexible gets no pre at all
+   VecPool pool;
+   std::vector<Vec *> p = pool.several(prm.k_dim + 1, n), z = pool.several(prm.flexible ? prm.k_dim + 1 : 0, n);
+   DenseOps ops(n, A);
+   ops.k_dim = prm.k_dim; ops.vary = prm.flexible; ops.wrong_from = wrong_from;
+   ops.name(&b, DenseOps::B); ops.name(&x, DenseOps::X); ops.name(&r, DenseOps::R); ops.name(&w, DenseOps::W);
+   ops.name(p, DenseOps::P); ops.name(z, DenseOps::PRE);
    Run out;
    out.res = hamd::gmres_iterate<Vec *>(prm, ops, &b, &x, &r, &w, p.data(), prm.flexible ? z.data() : nullptr);
-   out.x = x; out.calls = ops.calls; out.in_order = ops.rel_in_order;
+   out.x = x; out.calls = ops.calls; out.in_order = ops.rel_in_order; out.trace = ops.trace_end(x, out.res);
    return out;
-}
-
-static double true_rel_residual(const Vec &A, const Vec &b, const Vec &x, int n)
-{
-   double rr = 0.0, bb = 0.0;
-   for (int i = 0; i < n; i++)
-   {
-      double t = b[i];
-      for (int j = 0; j < n; j++) { t -= A[(size_t) i * n + j] * x[j]; }
-      rr += t * t; bb += b[i] * b[i];
-   }
-   return std::sqrt(rr / bb);
 }
 
 // the parameters the three Create functions of par_gmres.cpp fill in, and the one combination no entry point uses yet
@@ -113,8 +50,6 @@ static hamd::GMRESParams params(const Config &cf)
    prm.count_at_zero_residual = !(cf.ortho == GMRESOrtho::CGS || cf.ortho == GMRESOrtho::CGS2);
    return prm;
 }
-
-#define CHECK(cond) do { if (!(cond)) { std::printf("FAILED line %d: %s\n", __LINE__, #cond); return 1; } } while (0)
 
 int main()
 {
@@ -228,6 +163,31 @@ int main()
       std::printf("the same, flexible:       %d iterations, reported %.6e, recomputed %.6e\n", on.res.iterations, on.res.rel_residual_norm, ro);
       CHECK(on.res.status == hamd::GMRES_NOT_CONVERGED && on.res.converged == 0 && on.res.iterations == q.max_iter);
       CHECK(on.res.iterations > stuck.res.iterations && ro < 1e-13);
+   }
+
+   // the traces compared with the recorded ones: every configuration at k_dim 5 across several restarts, a cycle cut short
+   // at i = 3 by max_iter with no tolerance, the end at max_iter above a tolerance, the zero right-hand side; then the exit
+   // on a residual that stopped falling, and the flexible solver in its place
+   for (const Config &cf : configs)
+   {
+      hamd::GMRESParams q = params(cf);
+      q.k_dim = 5; q.tol = 1e-13; q.max_iter = 200;
+      const Run restarts = solve(A, b, n, q);
+      CHECK(restarts.res.converged == 1 && restarts.res.iterations > 2 * q.k_dim);
+      print_trace(cf.name, "restarts", restarts.trace);
+      print_trace(cf.name, "zero_rhs", solve(A, Vec((size_t) n, 0.0), n, q).trace);
+      q.tol = 1e-14; q.max_iter = 12;
+      const Run limit = solve(A, b, n, q);
+      CHECK(limit.res.status == hamd::GMRES_NOT_CONVERGED && limit.res.iterations == 12);
+      print_trace(cf.name, "max_iter", limit.trace);
+      q.k_dim = 7; q.tol = 0.0; q.max_iter = 10;
+      print_trace(cf.name, "cut_short", solve(A, b, n, q).trace);
+   }
+   for (int which : {0, 3})
+   {
+      hamd::GMRESParams q = params(configs[which]);
+      q.k_dim = 7; q.tol = 1e-18; q.max_iter = 80;
+      print_trace(configs[which].name, "residual_stopped_falling", solve(A, b, n, q, 4).trace);
    }
    std::printf("gmres host check ok: %d configurations\n", (int) (sizeof(configs) / sizeof(configs[0])));
    return 0;

@@ -2,77 +2,33 @@
 // Arnoldi-or-augmentation decision, the order of the augmentation vectors and the restart, with plain arrays behind the
 // vector callbacks, on dense systems of 60 unknowns (one symmetric positive definite, one not symmetric) behind a Jacobi
 // preconditioner.  Meant to be built with
-//    c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I hypre_amd/csrc
+//    c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off -I hypre_amd/csrc
 // and run once (tests/test_lgmres_host.py does): any index past hh / rs / c / s / coef / terms / aug_order or past the
 // k_dim + 1 basis vectors, the aug_dim + 1 augmentation vectors and the aug_dim products ends the program.  It also checks
 // what it computes: k_dim 2 with aug_dim 1; k_dim 5 with aug_dim 2 over more than five cycles (fill phase and truncation);
 // approx_constant both ways; fused against plain, bit for bit; an iteration limit inside an augmentation step;
 // convergence inside the first cycle; a zero right-hand side; a NaN; and aug_dim 0, which is GMRES.
 #include "lgmres_core.hpp"
-#include <cstdio>
-#include <cstdlib>
-#include <memory>
+#include "dense_ops.hpp"
+#include <string>
 
-using Vec = std::vector<double>;
-
-struct DenseOps
-{
-   int n;
-   const Vec &A;                      // row-major n x n
-   const Vec *w = nullptr;            // the correction vector: a preconditioner call on it is the unwinding that ends a cycle
-   int arnoldi = 0, cycles = 0, fused_calls = 0;
-   void matvec(double alpha, Vec *x, double beta, Vec *y)
-   {
-      for (int i = 0; i < n; i++)
-      {
-         double t = 0.0;
-         for (int j = 0; j < n; j++) { t += A[(size_t) i * n + j] * (*x)[j]; }
-         (*y)[i] = alpha * t + beta * (*y)[i];
-      }
-   }
-   double inner(Vec *x, Vec *y) { double t = 0.0; for (int i = 0; i < n; i++) { t += (*x)[i] * (*y)[i]; } return t; }
-   void copy(Vec *x, Vec *y) { *y = *x; }
-   void scale(double a, Vec *y) { for (double &v : *y) { v *= a; } }
-   void axpy(double a, Vec *x, Vec *y) { for (int i = 0; i < n; i++) { (*y)[i] += a * (*x)[i]; } }
-   double axpy_dot(double a, Vec *x, Vec *y, Vec *z) { axpy(a, x, y); return inner(z, y); }
-   void mass_axpy(double *a, Vec **xs, Vec *y, int k, int) { for (int j = 0; j < k; j++) { axpy(a[j], xs[j], y); } }
-   void scaled_copy(double a, Vec *x, Vec *y) { fused_calls++; for (int i = 0; i < n; i++) { (*y)[i] = a * (*x)[i]; } }
-   double copy_norm2(Vec *x, Vec *y) { fused_calls++; *y = *x; return inner(y, y); }
-   void scaled_diff(double a, Vec *x, Vec *y, Vec *z) { fused_calls++; for (int i = 0; i < n; i++) { (*z)[i] = ((*y)[i] - (*x)[i]) * -a; } }
-   void precond(int, double, Vec *rhs, Vec *sol)
-   {
-      if (rhs == w) { cycles++; } else { arnoldi++; }
-      for (int i = 0; i < n; i++) { (*sol)[i] = (*rhs)[i] / A[(size_t) i * n + i]; }
-   }
-   void solution_changed(Vec *) {}
-};
-
-struct Run { hamd::LGMRESResult res; Vec x; int arnoldi, cycles, fused_calls; };
+struct Run { hamd::LGMRESResult res; Vec x; int arnoldi, cycles, fused_calls; std::uint64_t trace; };
 
 static Run solve(const Vec &A, const Vec &b_in, int n, const hamd::LGMRESParams &prm)
 {
    Vec b = b_in, x((size_t) n, 0.0), r((size_t) n), w((size_t) n);
-   // exactly as many vectors as Setup gives, allocated one by one: an index past the end is a heap overflow the sanitizer sees
-   std::vector<std::unique_ptr<Vec>> own;
-   auto several = [&](int count) { std::vector<Vec *> v; for (int i = 0; i < count; i++) { own.emplace_back(new Vec((size_t) n, 0.0)); v.push_back(own.back().get()); } return v; };
-   std::vector<Vec *> p = several(prm.k_dim + 1), aug = several(prm.aug_dim + 1), a_aug = several(prm.aug_dim);
-   DenseOps ops{n, A, &w};
+   // exactly as many vectors as Setup gives
+   VecPool pool;
+   std::vector<Vec *> p = pool.several(prm.k_dim + 1, n), aug = pool.several(prm.aug_dim + 1, n), a_aug = pool.several(prm.aug_dim, n);
+   DenseOps ops(n, A);
+   ops.w = &w;
+   ops.name(&b, DenseOps::B); ops.name(&x, DenseOps::X); ops.name(&r, DenseOps::R); ops.name(&w, DenseOps::W);
+   ops.name(p, DenseOps::P); ops.name(aug, DenseOps::AUG); ops.name(a_aug, DenseOps::A_AUG);
    Run out;
    out.res = hamd::lgmres_iterate<Vec *>(prm, ops, &b, &x, &r, &w, p.data(), aug.data(), a_aug.data());
    out.x = x; out.arnoldi = ops.arnoldi; out.cycles = ops.cycles; out.fused_calls = ops.fused_calls;
+   out.trace = ops.trace_end(x, out.res, out.res.fused_updates, out.res.plain_updates);
    return out;
-}
-
-static double true_rel_residual(const Vec &A, const Vec &b, const Vec &x, int n)
-{
-   double rr = 0.0, bb = 0.0;
-   for (int i = 0; i < n; i++)
-   {
-      double t = b[i];
-      for (int j = 0; j < n; j++) { t -= A[(size_t) i * n + j] * x[j]; }
-      rr += t * t; bb += b[i] * b[i];
-   }
-   return std::sqrt(rr / bb);
 }
 
 // iterations that are augmentation steps when nothing cuts a cycle short: cycle c (from 0) has min(c, aug_dim) of them at
@@ -90,8 +46,6 @@ static int expected_aug_steps(int iterations, const hamd::LGMRESParams &prm)
    }
    return steps;
 }
-
-#define CHECK(cond) do { if (!(cond)) { std::printf("FAILED line %d: %s\n", __LINE__, #cond); return 1; } } while (0)
 
 int main()
 {
@@ -154,17 +108,12 @@ int main()
          hamd::LGMRESParams q;
          q.k_dim = 5; q.aug_dim = 0; q.tol = 1e-10; q.max_iter = 2000; q.fused = false;
          const Run l = solve(A, b, n, q);
-         struct GOps : DenseOps
-         {
-            void mass_inner(Vec *, Vec **, int, int, double *) {}
-            void mass_dot_two(Vec *, Vec *, Vec **, int, int, double *, double *) {}
-         } gops{{n, A}};
+         DenseOps gops(n, A);
          hamd::GMRESParams gp;
          gp.k_dim = 5; gp.tol = 1e-10; gp.max_iter = 2000; gp.stop_when_residual_grows = false;
          Vec bb = b, x((size_t) n, 0.0), r((size_t) n), w((size_t) n);
-         std::vector<std::unique_ptr<Vec>> own;
-         std::vector<Vec *> p;
-         for (int i = 0; i <= gp.k_dim; i++) { own.emplace_back(new Vec((size_t) n, 0.0)); p.push_back(own.back().get()); }
+         VecPool pool;
+         std::vector<Vec *> p = pool.several(gp.k_dim + 1, n);
          const hamd::GMRESResult gr = hamd::gmres_iterate<Vec *>(gp, gops, &bb, &x, &r, &w, p.data(), (Vec **) nullptr);
          std::printf("%-12s aug_dim 0: %d iterations, GMRES %d\n", sys.name, l.res.iterations, gr.iterations);
          CHECK(l.res.converged == 1 && gr.converged == 1 && l.res.iterations > q.k_dim);
@@ -215,6 +164,28 @@ int main()
          Vec bad = b; bad[3] = std::nan("");
          const Run n0 = solve(A, bad, n, q);
          CHECK(n0.res.status == hamd::GMRES_NOT_A_NUMBER && !n0.res.iterations_set && !n0.res.norm_set && n0.arnoldi == 0);
+      }
+   }
+
+   // the traces compared with the recorded ones: both systems, fused and plain, aug_dim 0 and 2, approx_constant both ways,
+   // and a run that max_iter ends at the first of the two augmentation steps of the third cycle
+   for (const auto &sys : systems)
+   {
+      for (int fused = 1; fused >= 0; fused--)
+      {
+         hamd::LGMRESParams q;
+         q.k_dim = 5; q.tol = 1e-10; q.max_iter = 2000; q.fused = fused != 0;
+         for (int aug_dim : {0, 2})
+         {
+            for (int approx : {0, 1})
+            {
+               q.aug_dim = aug_dim; q.approx_constant = approx;
+               const std::string variant = std::string(fused ? "fused" : "plain") + " aug_dim " + std::to_string(aug_dim) + " approx_constant " + std::to_string(approx);
+               print_trace(sys.name, variant.c_str(), solve(sys.A, b, n, q).trace);
+            }
+         }
+         q.tol = 1e-14; q.max_iter = 14;
+         print_trace(sys.name, fused ? "fused max_iter 14" : "plain max_iter 14", solve(sys.A, b, n, q).trace);
       }
    }
    std::printf("lgmres host check ok: 2 systems\n");

@@ -1,6 +1,42 @@
-"""Shared helpers for the tests: seeded inputs and small sparse matrices."""
+"""Shared helpers for the tests: seeded inputs, small sparse matrices, and stand-alone host programs."""
+import json
+import os
+import shutil
+import subprocess
+
 import numpy as np
 import scipy.sparse as sp
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# address and undefined-behaviour sanitizers, every warning an error; no contraction into fused multiply-adds and no -march,
+# so that what a program computes depends on IEEE double arithmetic alone
+HOST_FLAGS = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra", "-Werror",
+              "-ffp-contract=off"]
+
+
+def run_host_program(source, tmp_path, flags=HOST_FLAGS, cxx=None, timeout=120):
+    """Builds the stand-alone program tests/<source> (its own main, host code only, hypre_amd/csrc on the include path) and
+    runs it once; both must succeed.  Returns what it printed.  Nothing is loaded into python."""
+    cxx = cxx or shutil.which("g++") or shutil.which("c++")
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path / os.path.splitext(os.path.basename(source))[0])
+    build = subprocess.run([cxx] + list(flags) + ["-I", os.path.join(ROOT, "hypre_amd", "csrc"), os.path.join(ROOT, "tests", source), "-o", exe],
+                           capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr[-3000:]
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=timeout)
+    print(run.stdout)
+    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-3000:]
+    return run.stdout
+
+
+def assert_recorded_traces(stdout, which):
+    """The `trace <run> <hash>` lines of a Krylov host check against tests/golden/krylov_host_traces.json: the same runs, and
+    for each the same sequence of vector operations with the same scalars as the recorded commit's."""
+    with open(os.path.join(ROOT, "tests", "golden", "krylov_host_traces.json")) as f:
+        recorded = json.load(f)[which]
+    printed = dict(line[len("trace "):].rsplit(" ", 1) for line in stdout.splitlines() if line.startswith("trace "))
+    assert printed == recorded, {k: (printed.get(k), recorded.get(k)) for k in set(printed) | set(recorded) if printed.get(k) != recorded.get(k)}
 
 
 def lcg_vector(n, seed=1):
