@@ -20,8 +20,7 @@
 // Rows are processed in parallel with OpenMP where every row's result is
 // independent of the others (strength, interpolation, RAP); the per-row
 // arithmetic and entry order are those of the sequential reference loops.
-#include "amg_internal.hpp"
-#include <algorithm>
+#include "setup_common.hpp"
 #include <cmath>
 #include <omp.h>
 #include <unordered_map>
@@ -29,37 +28,6 @@
 using namespace hamd;
 
 namespace {
-
-// ---------------------------------------------------------------------------
-// host halo helpers over a comm package
-// ---------------------------------------------------------------------------
-template <class T> struct HaloJob;
-template <> struct HaloJob<double>       { static constexpr int fwd = 1,  rev = 2; };
-template <> struct HaloJob<HYPRE_Int>    { static constexpr int fwd = 11, rev = 12; };
-template <> struct HaloJob<HYPRE_BigInt> { static constexpr int fwd = 21; };      // ghost -> owner is never needed for indices
-
-// owner values -> ghost array (offd column order)
-template <class T>
-void halo_forward(hypre_ParCSRCommPkg *pkg, const T *local, T *ghost)
-{
-   if (!pkg) { return; }
-   const HYPRE_Int tot = pkg->send_map_starts[pkg->num_sends];
-   std::vector<T> buf((size_t) std::max(tot, 1));
-   for (HYPRE_Int k = 0; k < tot; k++) { buf[(size_t) k] = local[pkg->send_map_elmts[k]]; }
-   hypre_ParCSRCommHandle *h = hypre_ParCSRCommHandleCreate(HaloJob<T>::fwd, pkg, buf.data(), ghost);
-   hypre_ParCSRCommHandleDestroy(h);
-}
-// ghost values -> owners' buffer laid out like send_map_elmts
-template <class T>
-void halo_reverse(hypre_ParCSRCommPkg *pkg, const T *ghost, T *buf)
-{
-   if (!pkg) { return; }
-   hypre_ParCSRCommHandle *h = hypre_ParCSRCommHandleCreate(HaloJob<T>::rev, pkg, (void *) ghost, buf);
-   hypre_ParCSRCommHandleDestroy(h);
-}
-
-int comm_size(MPI_Comm c) { HYPRE_Int n; hypre_MPI_Comm_size(c, &n); return n; }
-int comm_rank(MPI_Comm c) { HYPRE_Int r; hypre_MPI_Comm_rank(c, &r); return r; }
 
 HYPRE_BigInt global_sum_big(MPI_Comm comm, HYPRE_BigInt v)
 {
@@ -94,15 +62,6 @@ struct HypreRand
 };
 
 inline int num_threads_avail() { return omp_get_max_threads(); }
-
-
-// contiguous row chunk of thread t out of T
-inline void chunk(int n, int T, int t, int *b, int *e)
-{
-   const long long per = n / T, rest = n % T;
-   *b = (int) (t * per + std::min<long long>(t, rest));
-   *e = (int) (*b + per + (t < rest ? 1 : 0));
-}
 
 // Sparse accumulator index for one matrix row at a time: integer key -> 64-bit value, emptied
 // after every row by revisiting only the slots that were used.  It stands in for the reference's
@@ -199,6 +158,7 @@ extern "C" HYPRE_Int hypre_amd_SetSetupDeviceRAP(HYPRE_Int on, HYPRE_Int min_row
    return c;
 }
 static bool device_rap_allowed() { return g_setup_targets_device; }
+static bool g_setup_timing = false;          // HYPRE_AMD_SETUP_TIMING: per-step times on stderr (read when a setup starts)
 static bool device_setup_allowed() { return g_setup_targets_device; }
 
 // Device twins of host matrices made during a device-targeted setup (operators uploaded for, or produced by, the device
@@ -256,19 +216,6 @@ static void place_on_device(hypre_CSRMatrix *M)
    d->i = nullptr; d->j = nullptr; d->data = nullptr;
    hypre_CSRMatrixDestroy(d);
 }
-// device -> fresh host arrays of n items: the destination pages are touched by all threads first (a copy into untouched
-// memory faults them in one by one on one thread: 1.8 GB took 0.4 s that way)
-static void download_bytes(void *host, const void *dev, size_t bytes)
-{
-   if (bytes > (size_t) 1 << 24)
-   {
-      char *p = (char *) host;
-#pragma omp parallel for schedule(static)
-      for (long long o = 0; o < (long long) bytes; o += 4096) { p[o] = 0; }
-   }
-   hypre_Memcpy(host, (void *) dev, bytes, HYPRE_MEMORY_HOST, HYPRE_MEMORY_DEVICE);
-}
-#define download(host, dev, n) download_bytes((host), (dev), sizeof(*(host)) * (size_t) (n))
 static int  g_device_interp_on = [] { const char *e = getenv("HYPRE_AMD_SETUP_DEVICE_INTERP"); return e ? atoi(e) : 1; }();
 static int  g_device_interp_count = 0;
 static bool g_interp_host_once = false;      // the next interpolation goes to the host loop (the device kernel just declined it)
@@ -358,9 +305,9 @@ static void make_host_resident(hypre_CSRMatrix *M)
    HYPRE_Int *hi = hypre_TAlloc(HYPRE_Int, (size_t) nr + 1, HYPRE_MEMORY_HOST);
    HYPRE_Int *hj = hypre_TAlloc(HYPRE_Int, (size_t) std::max(nnz, 1), HYPRE_MEMORY_HOST);
    HYPRE_Real *ha = M->data ? hypre_TAlloc(HYPRE_Real, (size_t) std::max(nnz, 1), HYPRE_MEMORY_HOST) : nullptr;
-   if (M->i) { download(hi, M->i, (size_t) nr + 1); } else { memset(hi, 0, sizeof(HYPRE_Int) * ((size_t) nr + 1)); }
-   if (nnz > 0 && M->j) { download(hj, M->j, (size_t) nnz); }
-   if (nnz > 0 && ha) { download(ha, M->data, (size_t) nnz); }
+   if (M->i) { fetch(hi, M->i, (size_t) nr + 1); } else { memset(hi, 0, sizeof(HYPRE_Int) * ((size_t) nr + 1)); }
+   if (nnz > 0 && M->j) { fetch(hj, M->j, (size_t) nnz); }
+   if (nnz > 0 && ha) { fetch(ha, M->data, (size_t) nnz); }
    drop_plan(M);
    device_twins()[M] = wrap_device_csr(nr, M->num_cols, nnz, M->i, M->j, M->data);
    M->i = hi; M->j = hj; M->data = ha;
@@ -402,13 +349,11 @@ HYPRE_Int hypre_BoomerAMGCreateS(hypre_ParCSRMatrix *A, HYPRE_Real theta, HYPRE_
    {
       // this level of a device-targeted setup: one thread per row, the loops below statement for statement; S stays there
       hypre_CSRMatrix *dA = device_twin_of(Ad, 1);
-      int *Si = nullptr, *Sj = nullptr, snnz = 0;
-      device_strength(n, dA->i, dA->j, dA->data, theta, max_row_sum, &Si, &Sj, &snnz, stream());
+      DevCSRBlock Sb;
+      device_strength(n, dA->i, dA->j, dA->data, theta, max_row_sum, &Sb.i.p, &Sb.j.p, &Sb.nnz, stream());
       hypre_ParCSRMatrix *S = hypre_ParCSRMatrixCreate(A->comm, A->global_num_rows, A->global_num_rows,
-                                                       A->row_starts, A->row_starts, 0, snnz, 0);
-      hypre_CSRMatrixDestroy(S->diag);
-      S->diag = wrap_device_csr(n, n, snnz, Si, Sj, nullptr);
-      hypre_CSRMatrixInitialize_v2(S->offd, 0, HYPRE_MEMORY_HOST);
+                                                       A->row_starts, A->row_starts, 0, Sb.nnz, 0);
+      adopt_device_blocks(S, Sb);
       *S_ptr = S;
       return hypre_error_flag;
    }
@@ -540,7 +485,7 @@ HYPRE_Int hypre_BoomerAMGCoarsenPMIS(hypre_ParCSRMatrix *S, hypre_ParCSRMatrix *
       HYPRE_Int *dCF = hypre_TAlloc(HYPRE_Int, (size_t) std::max(n, 1), HYPRE_MEMORY_DEVICE);
       device_pmis(n, Sd->i, Sd->j, Sd->num_nonzeros, 2747u + (CF_init == 2 ? 0u : (unsigned) my_id),
                   CF_init == 2 ? (unsigned long long) S->first_row_index : 0ull, dCF, stream());
-      download(CFh, dCF, (size_t) n);
+      fetch(CFh, dCF, (size_t) n);
       auto &mk = device_markers();
       auto it = mk.find(CFh);
       if (it != mk.end()) { hypre_Free(it->second, HYPRE_MEMORY_DEVICE); }
@@ -1087,9 +1032,8 @@ HYPRE_Int hypre_BoomerAMGBuildExtPIInterp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_m
       HYPRE_Int *dCF = device_marker_of(CF_marker, n);           // left by the device coarsening, or uploaded now
       HYPRE_Int *dF2C = hypre_TAlloc(HYPRE_Int, (size_t) n, HYPRE_MEMORY_DEVICE);
       device_coarse_numbering(n, dCF, dF2C, st);
-      int *dPi = nullptr, *dPj = nullptr, pnnz = 0;
-      double *dPa = nullptr;
-      const bool ok = device_extpi(n, dA->i, dA->j, dA->data, dS->i, dS->j, dCF, dF2C, trunc_factor, max_elmts, g_device_interp_on - 1, &dPi, &dPj, &dPa, &pnnz, st);
+      DevCSRBlock Pb;
+      const bool ok = device_extpi(n, dA->i, dA->j, dA->data, dS->i, dS->j, dCF, dF2C, trunc_factor, max_elmts, g_device_interp_on - 1, &Pb.i.p, &Pb.j.p, &Pb.a.p, &Pb.nnz, st);
       if (!S_there) { hypre_CSRMatrixDestroy(dS); }
       hypre_Free(dF2C, HYPRE_MEMORY_DEVICE);
       if (ok)
@@ -1097,10 +1041,8 @@ HYPRE_Int hypre_BoomerAMGBuildExtPIInterp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_m
          // the operator stays where it was made: nothing on the host reads it (the Galerkin product that follows runs
          // on the device as well; should that fall back to the host loop, it fetches a copy)
          HYPRE_BigInt cs[2] = {num_cpts_global[0], num_cpts_global[1]};
-         hypre_ParCSRMatrix *P = hypre_ParCSRMatrixCreate(comm, A->global_num_rows, total_cpts, A->col_starts, cs, 0, pnnz, 0);
-         hypre_CSRMatrixDestroy(P->diag);
-         P->diag = wrap_device_csr(n, (HYPRE_Int) (cs[1] - cs[0]), pnnz, dPi, dPj, dPa);
-         hypre_CSRMatrixInitialize_v2(P->offd, 0, HYPRE_MEMORY_HOST);
+         hypre_ParCSRMatrix *P = hypre_ParCSRMatrixCreate(comm, A->global_num_rows, total_cpts, A->col_starts, cs, 0, Pb.nnz, 0);
+         adopt_device_blocks(P, Pb);
          hypre_CSRMatrixSetRownnz(P->offd);
          *P_ptr = P;
          g_device_interp_count++;
@@ -1122,18 +1064,14 @@ HYPRE_Int hypre_BoomerAMGBuildExtPIInterp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_m
       HYPRE_Int c = 0;
       for (HYPRE_Int i = 0; i < n; i++) { if (CF_marker[i] >= 0) { f2c[(size_t) i] = c++; } }
    }
-   const int T = num_threads_avail();
-   std::vector<std::vector<HYPRE_Int>> tj((size_t) T);
-   std::vector<std::vector<HYPRE_Real>> ta((size_t) T);
-   std::vector<HYPRE_Int> rowlen((size_t) std::max(n, 1), 0);
-
-#pragma omp parallel num_threads(T)
+   RowBlocks rows(n, num_threads_avail(), false);
+#pragma omp parallel num_threads(rows.T)
    {
       const int t = omp_get_thread_num();
       int rb, re;
-      chunk(n, T, t, &rb, &re);
-      std::vector<HYPRE_Int> &pj = tj[(size_t) t];
-      std::vector<HYPRE_Real> &pa = ta[(size_t) t];
+      rows.rows_of(t, &rb, &re);
+      std::vector<HYPRE_Int> &pj = rows.diag[(size_t) t].j;
+      std::vector<HYPRE_Real> &pa = rows.diag[(size_t) t].a;
       // marker holds, per fine point, either the position of its column in
       // the current row (>= row begin), or the strong-F tag of the current row
       RowMarker marker;
@@ -1209,33 +1147,15 @@ HYPRE_Int hypre_BoomerAMGBuildExtPIInterp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_m
             if (diagonal) { for (size_t k = (size_t) begin; k < pj.size(); k++) { pa[k] /= -diagonal; } }
             strong_f--;
          }
-         rowlen[(size_t) i] = (HYPRE_Int) ((long long) pj.size() - begin);
+         rows.di[(size_t) i + 1] = (HYPRE_Int) ((long long) pj.size() - begin);
          marker.end_row();
       }
    }
-   // stitch
-   std::vector<HYPRE_Int> Pi((size_t) n + 1, 0);
-   for (HYPRE_Int i = 0; i < n; i++) { Pi[(size_t) i + 1] = Pi[(size_t) i] + rowlen[(size_t) i]; }
-   const HYPRE_Int nnz = Pi[(size_t) n];
+   rows.offsets();
    HYPRE_BigInt cs[2] = {num_cpts_global[0], num_cpts_global[1]};
-   hypre_ParCSRMatrix *P = hypre_ParCSRMatrixCreate(comm, A->global_num_rows, total_cpts, A->col_starts, cs, 0, nnz, 0);
+   hypre_ParCSRMatrix *P = hypre_ParCSRMatrixCreate(comm, A->global_num_rows, total_cpts, A->col_starts, cs, 0, rows.nnz_diag(), 0);
    hypre_ParCSRMatrixInitialize_v2(P, HYPRE_MEMORY_HOST);
-   memcpy(P->diag->i, Pi.data(), sizeof(HYPRE_Int) * ((size_t) n + 1));
-#pragma omp parallel num_threads(T)
-   {
-      const int t = omp_get_thread_num();
-      int rb, re;
-      chunk(n, T, t, &rb, &re);
-      if (re > rb)
-      {
-         const size_t off = (size_t) Pi[(size_t) rb];
-         if (!tj[(size_t) t].empty())
-         {
-            memcpy(P->diag->j + off, tj[(size_t) t].data(), sizeof(HYPRE_Int) * tj[(size_t) t].size());
-            memcpy(P->diag->data + off, ta[(size_t) t].data(), sizeof(HYPRE_Real) * ta[(size_t) t].size());
-         }
-      }
-   }
+   rows.stitch(P->diag);
    if (trunc_factor != 0.0 || max_elmts > 0) { hypre_BoomerAMGInterpTruncation(P, trunc_factor, max_elmts); }
    hypre_CSRMatrixSetRownnz(P->offd);
    *P_ptr = P;
@@ -1376,20 +1296,10 @@ HYPRE_Int hypre_BoomerAMGBuildDirInterp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_mar
    if (trunc_factor != 0.0 || max_elmts > 0) { hypre_BoomerAMGInterpTruncation(P, trunc_factor, max_elmts); }
    if (dist)
    {
-      // ghost C-points that survived: P's own column map, ascending (par_interp.c:2370-2440)
-      const HYPRE_Int nnz_o = P->offd->i[n];
-      std::vector<HYPRE_Int> renum((size_t) std::max(nco, 1), -1);
-      for (HYPRE_Int k = 0; k < nnz_o; k++) { renum[(size_t) P->offd->j[k]] = 0; }
-      std::vector<HYPRE_BigInt> cmap;
-      for (HYPRE_Int g = 0; g < nco; g++) { if (renum[(size_t) g] == 0) { renum[(size_t) g] = (HYPRE_Int) cmap.size(); cmap.push_back(f2c_offd[(size_t) g]); } }
-      for (HYPRE_Int k = 0; k < nnz_o; k++) { P->offd->j[k] = renum[(size_t) P->offd->j[k]]; }
-      P->offd->num_cols = (HYPRE_Int) cmap.size();
-      if (P->col_map_offd) { hypre_Free(P->col_map_offd, HYPRE_MEMORY_HOST); P->col_map_offd = nullptr; }
-      if (!cmap.empty())
-      {
-         P->col_map_offd = hypre_TAlloc(HYPRE_BigInt, cmap.size(), HYPRE_MEMORY_HOST);
-         memcpy(P->col_map_offd, cmap.data(), sizeof(HYPRE_BigInt) * cmap.size());
-      }
+      // ghost C-points that survived: P's own column map, ascending (par_interp.c:2370-2440).  Only C ghosts are in use;
+      // A's ghosts ascend in global fine id and a rank's coarse ids ascend with its fine ids, rank after rank, so their
+      // coarse ids already ascend without repeats: the sort inside is the identity and the ghosts keep their order
+      set_col_map_offd(P, compact_offd_columns(P->offd->j, (size_t) P->offd->i[n], f2c_offd.data(), nco));
       hypre_CSRMatrixSetRownnz(P->offd);
       hypre_MatvecCommPkgCreate(P);
       *P_ptr = P;
@@ -1423,6 +1333,7 @@ struct SetupScope
       g_setup_targets_device = device;
       g_level_on_device = false;
       g_interp_host_once = false;
+      g_setup_timing = getenv("HYPRE_AMD_SETUP_TIMING") != nullptr;
       drop_device_twins();
    }
    ~SetupScope()
@@ -1445,7 +1356,6 @@ static bool device_galerkin_product(hypre_ParCSRMatrix *RT, hypre_ParCSRMatrix *
    if (nf < g_device_rap_min_rows || A->diag->num_nonzeros <= 0 || P->diag->num_nonzeros <= 0) { return false; }   // small levels: the host loop is quicker than the transfers
    if (!ensure_device()) { return false; }
    hipStream_t s = stream();
-   const bool timing = getenv("HYPRE_AMD_SETUP_TIMING") != nullptr;
    const double t0 = omp_get_wtime();
    hypre_CSRMatrix *dA = device_twin_of(A->diag, 1);
    hypre_CSRMatrix *dP = device_twin_of(P->diag, 1);
@@ -1456,18 +1366,15 @@ static bool device_galerkin_product(hypre_ParCSRMatrix *RT, hypre_ParCSRMatrix *
    int maxP = 0;
    if (P->diag->memory_location == HYPRE_MEMORY_DEVICE) { maxP = device_max_row_nnz(P->diag->i, nf, s); }
    else { for (HYPRE_Int i = 0; i < nf; i++) { maxP = std::max(maxP, (int) (P->diag->i[i + 1] - P->diag->i[i])); } }
-   int *Ci = nullptr, *Cj = nullptr, nnz = 0;
-   double *Ca = nullptr;
-   const bool ok = device_rap(nc, nc, maxP, dR->i, dR->j, dR->data, dA->i, dA->j, dA->data, dP->i, dP->j, dP->data, &Ci, &Cj, &Ca, &nnz, s);
+   DevCSRBlock Cb;
+   const bool ok = device_rap(nc, nc, maxP, dR->i, dR->j, dR->data, dA->i, dA->j, dA->data, dP->i, dP->j, dP->data, &Cb.i.p, &Cb.j.p, &Cb.a.p, &Cb.nnz, s);
    const double t3 = omp_get_wtime();
    if (!ok) { hypre_CSRMatrixDestroy(dR); return false; }
    hypre_ParCSRMatrix *C = hypre_ParCSRMatrixCreate(A->comm, RT->global_num_cols, P->global_num_cols, RT->col_starts,
-                                                    P->col_starts, 0, nnz, 0);
+                                                    P->col_starts, 0, Cb.nnz, 0);
    // the coarse operator stays where it was made; a later step that runs on the host (a small level, a smoother whose
    // setup is a host loop) fetches it then (make_host_resident) and the device arrays stay on as its twin
-   hypre_CSRMatrixDestroy(C->diag);
-   C->diag = wrap_device_csr(nc, nc, nnz, Ci, Cj, Ca);
-   hypre_CSRMatrixInitialize_v2(C->offd, 0, HYPRE_MEMORY_HOST);
+   adopt_device_blocks(C, Cb);
    if (keepTranspose) { RT->diagT = dR; }          // the restriction operator is used on the device only
    else { hypre_CSRMatrixDestroy(dR); }
    hypre_CSRMatrixSetRownnz(C->offd);
@@ -1475,7 +1382,7 @@ static bool device_galerkin_product(hypre_ParCSRMatrix *RT, hypre_ParCSRMatrix *
    hypre_ParCSRMatrixSetDNumNonzeros(C);
    *RAP_ptr = C;
    g_device_rap_count++;
-   if (timing) { fprintf(stderr, "   device RAP: upload %.3fs  transpose %.3fs  product %.3fs  rest %.3fs\n", t1 - t0, t2 - t1, t3 - t2, omp_get_wtime() - t3); }
+   if (g_setup_timing) { fprintf(stderr, "   device RAP: upload %.3fs  transpose %.3fs  product %.3fs  rest %.3fs\n", t1 - t0, t2 - t1, t3 - t2, omp_get_wtime() - t3); }
    return true;
 }
 
@@ -1522,17 +1429,14 @@ HYPRE_Int hypre_BoomerAMGBuildCoarseOperatorKT(hypre_ParCSRMatrix *RT, hypre_Par
    const HYPRE_Int *Pi = P->diag->i, *Pj = P->diag->j; const HYPRE_Real *Pa = P->diag->data;
    const bool square = (RT->diag->num_cols == P->diag->num_cols);
 
-   const int T = num_threads_avail();
-   std::vector<std::vector<HYPRE_Int>> tj((size_t) T);
-   std::vector<std::vector<HYPRE_Real>> ta((size_t) T);
-   std::vector<HYPRE_Int> rowlen((size_t) std::max(nc, 1), 0);
-#pragma omp parallel num_threads(T)
+   RowBlocks rows(nc, num_threads_avail(), false);
+#pragma omp parallel num_threads(rows.T)
    {
       const int t = omp_get_thread_num();
       int rb, re;
-      chunk(nc, T, t, &rb, &re);
-      std::vector<HYPRE_Int> &oj = tj[(size_t) t];
-      std::vector<HYPRE_Real> &oa = ta[(size_t) t];
+      rows.rows_of(t, &rb, &re);
+      std::vector<HYPRE_Int> &oj = rows.diag[(size_t) t].j;
+      std::vector<HYPRE_Real> &oa = rows.diag[(size_t) t].a;
       RowMap Pmark(1024), Amark(1024);         // column -> position in the row being formed
       std::vector<HYPRE_Int> raj;
       std::vector<HYPRE_Real> raa;
@@ -1570,28 +1474,15 @@ HYPRE_Int hypre_BoomerAMGBuildCoarseOperatorKT(hypre_ParCSRMatrix *RT, hypre_Par
                else { oa[(size_t) m] += rap * Pa[j2]; }
             }
          }
-         rowlen[(size_t) ic] = (HYPRE_Int) ((long long) oj.size() - begin);
+         rows.di[(size_t) ic + 1] = (HYPRE_Int) ((long long) oj.size() - begin);
          Amark.clear(); Pmark.clear();
       }
    }
-   std::vector<HYPRE_Int> Ci((size_t) nc + 1, 0);
-   for (HYPRE_Int i = 0; i < nc; i++) { Ci[(size_t) i + 1] = Ci[(size_t) i] + rowlen[(size_t) i]; }
+   rows.offsets();
    hypre_ParCSRMatrix *C = hypre_ParCSRMatrixCreate(comm, RT->global_num_cols, P->global_num_cols, RT->col_starts,
-                                                    P->col_starts, 0, Ci[(size_t) nc], 0);
+                                                    P->col_starts, 0, rows.nnz_diag(), 0);
    hypre_ParCSRMatrixInitialize_v2(C, HYPRE_MEMORY_HOST);
-   memcpy(C->diag->i, Ci.data(), sizeof(HYPRE_Int) * ((size_t) nc + 1));
-#pragma omp parallel num_threads(T)
-   {
-      const int t = omp_get_thread_num();
-      int rb, re;
-      chunk(nc, T, t, &rb, &re);
-      if (re > rb && !tj[(size_t) t].empty())
-      {
-         const size_t off = (size_t) Ci[(size_t) rb];
-         memcpy(C->diag->j + off, tj[(size_t) t].data(), sizeof(HYPRE_Int) * tj[(size_t) t].size());
-         memcpy(C->diag->data + off, ta[(size_t) t].data(), sizeof(HYPRE_Real) * ta[(size_t) t].size());
-      }
-   }
+   rows.stitch(C->diag);
    if (keepTranspose) { RT->diagT = R; } else { hypre_CSRMatrixDestroy(R); }
    hypre_CSRMatrixSetRownnz(C->offd);
    hypre_ParCSRMatrixSetNumNonzeros(C);
@@ -1835,7 +1726,6 @@ static hypre_ParCSRMatrix *blk_filter(hypre_ParCSRMatrix *A, HYPRE_Int block_siz
    const HYPRE_Int n = Ad->num_rows, nco = Ao->num_cols;
    std::vector<HYPRE_Int> di((size_t) n + 1, 0), oi((size_t) n + 1, 0), dj, oj;
    std::vector<HYPRE_Real> da, oa;
-   std::vector<char> used((size_t) std::max(nco, 1), 0);
    for (HYPRE_Int i = 0; i < n; i++)
    {
       const HYPRE_Int c = i % block_size;
@@ -1847,16 +1737,13 @@ static hypre_ParCSRMatrix *blk_filter(hypre_ParCSRMatrix *A, HYPRE_Int block_siz
       {
          if (c == (HYPRE_Int) (A->col_map_offd[Ao->j[k]] % (HYPRE_BigInt) block_size))
          {
-            oj.push_back(Ao->j[k]); oa.push_back(Ao->data[k]); used[(size_t) Ao->j[k]] = 1;
+            oj.push_back(Ao->j[k]); oa.push_back(Ao->data[k]);
          }
       }
       di[(size_t) i + 1] = (HYPRE_Int) dj.size();
       oi[(size_t) i + 1] = (HYPRE_Int) oj.size();
    }
-   std::vector<HYPRE_Int> renum((size_t) std::max(nco, 1), -1);
-   std::vector<HYPRE_BigInt> cmap;
-   for (HYPRE_Int c = 0; c < nco; c++) { if (used[(size_t) c]) { renum[(size_t) c] = (HYPRE_Int) cmap.size(); cmap.push_back(A->col_map_offd[c]); } }
-   for (HYPRE_Int &c : oj) { c = renum[(size_t) c]; }
+   std::vector<HYPRE_BigInt> cmap = compact_offd_columns(oj.data(), oj.size(), A->col_map_offd, nco);      // ascending already
    hypre_ParCSRMatrix *Bm = hypre_amd_ParCSRMatrixFromArrays(A->comm, A->global_num_rows, A->global_num_cols, A->row_starts,
                                                              A->col_starts, (HYPRE_Int) cmap.size(), cmap.data(), di.data(),
                                                              dj.data(), da.data(), oi.data(), oj.data(), oa.data(), HYPRE_MEMORY_HOST);
@@ -1979,8 +1866,7 @@ HYPRE_Int hypre_BoomerAMGSetup(void *amg_vdata, hypre_ParCSRMatrix *A, hypre_Par
       for (HYPRE_Int i = 0; i < n0; i++) { dof_func[(size_t) i] = (i + offset) % d->num_functions; }
    }
    // host threads: no more than the cores this process owns, and no more than a level's rows can keep busy
-   const int saved_omp_threads = omp_get_max_threads();
-   const int thread_cap = std::max(1, std::min(saved_omp_threads, host_cpu_share()));
+   const int thread_cap = std::max(1, std::min(scope.saved_threads, host_cpu_share()));
    omp_set_num_threads(thread_cap);
    while (not_finished)
    {
@@ -2013,6 +1899,19 @@ HYPRE_Int hypre_BoomerAMGSetup(void *amg_vdata, hypre_ParCSRMatrix *A, hypre_Par
       }
       const double t_c1 = omp_get_wtime();
       HYPRE_Int *CF = d->CF_marker_array[level]->data;
+      // this level stays the last one: its strength matrix, its work vectors (the finest level's are the caller's) and,
+      // when asked, its C/F marker go
+      auto drop_level = [&](bool marker_too)
+      {
+         destroy_with_twins(S);
+         if (marker_too) { hypre_IntArrayDestroy(d->CF_marker_array[level]); d->CF_marker_array[level] = nullptr; }
+         if (level > 0)
+         {
+            hypre_ParVectorDestroy(d->F_array[level]); d->F_array[level] = nullptr;
+            hypre_ParVectorDestroy(d->U_array[level]); d->U_array[level] = nullptr;
+         }
+         coarse_size = fine_size;
+      };
       HYPRE_BigInt cpts[2];
       coarse_parms(comm, nloc, CF, cpts, &coarse_size);
       std::vector<HYPRE_Int> coarse_dof_func;
@@ -2030,28 +1929,10 @@ HYPRE_Int hypre_BoomerAMGSetup(void *amg_vdata, hypre_ParCSRMatrix *A, hypre_Par
             d->num_grid_sweeps[3] = 1;
             if (d->grid_relax_points) { d->grid_relax_points[3][0] = 0; }
          }
-         destroy_with_twins(S);
-         if (level > 0)
-         {
-            hypre_IntArrayDestroy(d->CF_marker_array[level]); d->CF_marker_array[level] = nullptr;
-            hypre_ParVectorDestroy(d->F_array[level]); d->F_array[level] = nullptr;
-            hypre_ParVectorDestroy(d->U_array[level]); d->U_array[level] = nullptr;
-         }
-         coarse_size = fine_size;
+         drop_level(level > 0);
          break;
       }
-      if (coarse_size < (HYPRE_BigInt) d->min_coarse_size)
-      {
-         destroy_with_twins(S);
-         hypre_IntArrayDestroy(d->CF_marker_array[level]); d->CF_marker_array[level] = nullptr;
-         if (level > 0)
-         {
-            hypre_ParVectorDestroy(d->F_array[level]); d->F_array[level] = nullptr;
-            hypre_ParVectorDestroy(d->U_array[level]); d->U_array[level] = nullptr;
-         }
-         coarse_size = fine_size;
-         break;
-      }
+      if (coarse_size < (HYPRE_BigInt) d->min_coarse_size) { drop_level(true); break; }
       const double t_i0 = omp_get_wtime();
       hypre_ParCSRMatrix *P = nullptr;
       if (d->interp_type == 6)
@@ -2102,7 +1983,7 @@ HYPRE_Int hypre_BoomerAMGSetup(void *amg_vdata, hypre_ParCSRMatrix *A, hypre_Par
          }
          hypre_BoomerAMGBuildCoarseOperatorKT(P, Al, P, 1, &AH);
       }
-      if (getenv("HYPRE_AMD_SETUP_TIMING") && comm_rank(comm) == 0)
+      if (g_setup_timing && comm_rank(comm) == 0)
       {
          fprintf(stderr, "setup level %d: rows %lld  strength %.2fs  coarsen %.2fs  interp %.2fs  RAP %.2fs  (threads %d)\n", level,
                  (long long) fine_size, t_s1 - t_s0, t_c1 - t_s1, t_r0 - t_i0, omp_get_wtime() - t_r0, omp_get_max_threads());

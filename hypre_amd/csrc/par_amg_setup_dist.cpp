@@ -10,28 +10,19 @@
 //   parcsr_ls/par_lr_interp.c:1024-1700    extended+i interpolation, off-rank branches
 //   parcsr_ls/aux_interp.c:777-900         column map of P's off-rank block
 //   parcsr_ls/par_rap.c:30-2000            RAP with P_ext and RAP_ext
-#include "amg_internal.hpp"
+#include "setup_common.hpp"
 #include <omp.h>
-#include <algorithm>
 #include <cmath>
+#include <memory>
+#include <optional>
 
 using namespace hamd;
 
 namespace {
 
-int comm_size(MPI_Comm c) { HYPRE_Int n; hypre_MPI_Comm_size(c, &n); return n; }
-
 // ---------------------------------------------------------------------------
-// variable-length rows through a comm package
+// variable-length rows (ExtCSR) through a comm package
 // ---------------------------------------------------------------------------
-struct ExtCSR
-{
-   std::vector<HYPRE_Int>    i;       // [nrows+1]
-   std::vector<HYPRE_BigInt> j;       // global column ids (or encoded local/ghost ids later)
-   std::vector<HYPRE_Real>   a;       // may stay empty
-   HYPRE_Int nrows() const { return (HYPRE_Int) i.size() - 1; }
-};
-
 // forward = owner -> ghost: `rows` holds one row per send_map entry (in send_map
 // order); the result holds one row per ghost column.  reverse = ghost -> owner.
 ExtCSR exchange_rows(hypre_ParCSRCommPkg *pkg, const ExtCSR &rows, bool forward, bool with_data)
@@ -128,22 +119,6 @@ ExtCSR extract_ext(hypre_ParCSRMatrix *B, hypre_ParCSRCommPkg *pkg, bool with_da
    return exchange_rows(pkg, rows, true, with_data);
 }
 
-template <class T>
-void halo_fwd(hypre_ParCSRCommPkg *pkg, const T *local, T *ghost, int job)
-{
-   const HYPRE_Int tot = pkg->send_map_starts[pkg->num_sends];
-   std::vector<T> buf((size_t) std::max(tot, 1));
-   for (HYPRE_Int k = 0; k < tot; k++) { buf[(size_t) k] = local[pkg->send_map_elmts[k]]; }
-   hypre_ParCSRCommHandle *h = hypre_ParCSRCommHandleCreate(job, pkg, buf.data(), ghost);
-   hypre_ParCSRCommHandleDestroy(h);
-}
-
-HYPRE_Int bsearch_big(const HYPRE_BigInt *list, HYPRE_BigInt v, HYPRE_Int n)
-{
-   const HYPRE_BigInt *p = std::lower_bound(list, list + n, v);
-   return (p != list + n && *p == v) ? (HYPRE_Int) (p - list) : -1;
-}
-
 // New off-rank nodes of the extended+i interpolation (aux_interp.c:351-560): the columns of ghost F rows (of the
 // fetched rows Aext and Sop) that are neither local nor ghosts of A become `found` (ascending); every off-rank column
 // of those rows is re-encoded as -(k) - 1 with k its position among A's ghosts, or nco + its position in `found`.
@@ -203,6 +178,32 @@ void ghost_row_numbering(const HYPRE_BigInt *col_map_offd, HYPRE_Int nco, HYPRE_
    }
 }
 
+// What the host and the device builder of the distributed extended+i interpolation do first (hypre_exchange_interp_data,
+// aux_interp.c:351-640): the markers of A's ghost points, the rows of A and S their owners hold for them (fetch_rows: how
+// the builder extracts and exchanges them), the new off-rank nodes those rows name, the package that reaches the new
+// nodes and their markers.  Collective.
+struct ExtPIGhosts
+{
+   std::vector<HYPRE_Int>    CF_offd;           // [A's ghosts | new nodes]
+   ExtCSR                    Aext, Sop;         // off-rank columns encoded by ghost_row_numbering
+   std::vector<HYPRE_BigInt> found;             // the new nodes, ascending
+   std::optional<ExtPkg>     ext;
+   HYPRE_Int                 full_off = 0;
+   template <class FetchRows>
+   ExtPIGhosts(hypre_ParCSRMatrix *A, const HYPRE_Int *CF_marker, FetchRows fetch_rows)
+   {
+      const HYPRE_Int n = A->diag->num_rows, nco = A->offd->num_cols;
+      CF_offd.resize((size_t) std::max(nco, 1));
+      halo_forward<HYPRE_Int>(A->comm_pkg, CF_marker, CF_offd.data());
+      fetch_rows(CF_offd, Aext, Sop);
+      ghost_row_numbering(A->col_map_offd, nco, A->first_row_index, A->first_row_index + n, CF_offd, Aext, Sop, found);
+      ext.emplace(A, found);
+      full_off = nco + (HYPRE_Int) found.size();
+      CF_offd.resize((size_t) std::max(full_off, 1));
+      halo_forward<HYPRE_Int>(&ext->pkg, CF_marker, CF_offd.data() + nco);
+   }
+};
+
 }  // namespace
 
 namespace hamd {
@@ -223,7 +224,7 @@ HYPRE_Int dist_build_extpi_interp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, h
    if (dof_func && A->offd->num_cols)
    {
       dof_offd.resize((size_t) A->offd->num_cols);
-      halo_fwd<HYPRE_Int>(pkg, dof_func, dof_offd.data(), 11);
+      halo_forward<HYPRE_Int>(pkg, dof_func, dof_offd.data());
    }
    hypre_CSRMatrix *Ad = A->diag, *Ao = A->offd;
    const HYPRE_Int *Adi = Ad->i, *Adj = Ad->j, *Aoi = Ao->i, *Aoj = Ao->j;
@@ -233,25 +234,14 @@ HYPRE_Int dist_build_extpi_interp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, h
    const HYPRE_BigInt col_1 = A->first_row_index, col_n = col_1 + n;
    const HYPRE_BigInt my_first_cpt = num_cpts_global[0];
 
-   // ---- hypre_exchange_interp_data ----------------------------------------------------
-   std::vector<HYPRE_Int> CF_offd((size_t) std::max(nco, 1));
-   halo_fwd<HYPRE_Int>(pkg, CF_marker, CF_offd.data(), 11);
-   ExtCSR Aext = extract_ext(A, pkg, true, 2, CF_marker, CF_offd.data());
-   ExtCSR Sop  = extract_ext(S, pkg, false, 1, CF_marker, CF_offd.data());
-   std::vector<HYPRE_BigInt> found;
-   ghost_row_numbering(A->col_map_offd, nco, col_1, col_n, CF_offd, Aext, Sop, found);
-   const HYPRE_Int newoff = (HYPRE_Int) found.size();
-   const HYPRE_Int full_off = nco + newoff;
-   // package for the new nodes only (collective: every rank builds one, possibly empty)
-   hypre_ParCSRCommPkg ext_pkg;
-   memset(&ext_pkg, 0, sizeof(ext_pkg));
-   ext_pkg.comm = comm;
-   hypre_ParCSRCommPkgCreate_core(comm, found.empty() ? nullptr : found.data(), A->first_col_diag, A->col_starts,
-                                  Ad->num_cols, newoff, &ext_pkg.num_recvs, &ext_pkg.recv_procs,
-                                  &ext_pkg.recv_vec_starts, &ext_pkg.num_sends, &ext_pkg.send_procs,
-                                  &ext_pkg.send_map_starts, &ext_pkg.send_map_elmts);
-   CF_offd.resize((size_t) std::max(full_off, 1));
-   halo_fwd<HYPRE_Int>(&ext_pkg, CF_marker, CF_offd.data() + nco, 11);
+   ExtPIGhosts gh(A, CF_marker, [&](const std::vector<HYPRE_Int> &cf_offd, ExtCSR &Ae, ExtCSR &So)
+   {
+      Ae = extract_ext(A, pkg, true, 2, CF_marker, cf_offd.data());
+      So = extract_ext(S, pkg, false, 1, CF_marker, cf_offd.data());
+   });
+   const std::vector<HYPRE_Int> &CF_offd = gh.CF_offd;
+   const ExtCSR &Aext = gh.Aext, &Sop = gh.Sop;
+   const HYPRE_Int full_off = gh.full_off;
 
    // ---- fine -> coarse numbering, local and for every (extended) ghost ----------------
    std::vector<HYPRE_Int> f2c((size_t) std::max(n, 1), -1);
@@ -261,21 +251,19 @@ HYPRE_Int dist_build_extpi_interp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, h
    }
    std::vector<HYPRE_BigInt> f2c_big((size_t) std::max(n, 1)), f2c_offd((size_t) std::max(full_off, 1), -1);
    for (HYPRE_Int i = 0; i < n; i++) { f2c_big[(size_t) i] = (HYPRE_BigInt) f2c[(size_t) i] + my_first_cpt; }
-   halo_fwd<HYPRE_BigInt>(pkg, f2c_big.data(), f2c_offd.data(), 21);
-   halo_fwd<HYPRE_BigInt>(&ext_pkg, f2c_big.data(), f2c_offd.data() + nco, 21);
+   halo_forward<HYPRE_BigInt>(pkg, f2c_big.data(), f2c_offd.data());
+   halo_forward<HYPRE_BigInt>(&gh.ext->pkg, f2c_big.data(), f2c_offd.data() + nco);
 
    // ---- rows of P: contiguous row blocks, one per thread, each with its own markers and output (a row only
    // reads A, S, the ghost rows and the CF / coarse-index arrays) ------------------------------------------------
-   std::vector<HYPRE_Int> Pdi((size_t) n + 1, 0), Poi((size_t) n + 1, 0);
-   const int T = std::max(1, std::min(omp_get_max_threads(), n / 2048 + 1));
-   std::vector<std::vector<HYPRE_Int>> t_pdj((size_t) T), t_poj((size_t) T);
-   std::vector<std::vector<HYPRE_Real>> t_pda((size_t) T), t_poa((size_t) T);
-#pragma omp parallel num_threads(T)
+   RowBlocks rows(n, std::min(omp_get_max_threads(), n / 2048 + 1), true);
+#pragma omp parallel num_threads(rows.T)
    {
    const int tid = omp_get_thread_num();
-   const HYPRE_Int row_b = (HYPRE_Int) ((long long) n * tid / T), row_e = (HYPRE_Int) ((long long) n * (tid + 1) / T);
-   std::vector<HYPRE_Int> &pdj = t_pdj[(size_t) tid], &poj = t_poj[(size_t) tid];
-   std::vector<HYPRE_Real> &pda = t_pda[(size_t) tid], &poa = t_poa[(size_t) tid];
+   HYPRE_Int row_b, row_e;
+   rows.rows_of(tid, &row_b, &row_e);
+   std::vector<HYPRE_Int> &pdj = rows.diag[(size_t) tid].j, &poj = rows.offd[(size_t) tid].j;
+   std::vector<HYPRE_Real> &pda = rows.diag[(size_t) tid].a, &poa = rows.offd[(size_t) tid].a;
    std::vector<long long> mk((size_t) std::max(n, 1), -1), mko((size_t) std::max(full_off, 1), -1);
    long long strong_f = -2;
    for (HYPRE_Int i = row_b; i < row_e; i++)
@@ -422,62 +410,23 @@ HYPRE_Int dist_build_extpi_interp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, h
          }
          strong_f--;
       }
-      Pdi[(size_t) i + 1] = (HYPRE_Int) ((long long) pdj.size() - bd);      // row lengths; offsets after the region
-      Poi[(size_t) i + 1] = (HYPRE_Int) ((long long) poj.size() - bo);
+      rows.di[(size_t) i + 1] = (HYPRE_Int) ((long long) pdj.size() - bd);
+      rows.oi[(size_t) i + 1] = (HYPRE_Int) ((long long) poj.size() - bo);
    }
    }  // parallel region
-   for (HYPRE_Int i = 0; i < n; i++) { Pdi[(size_t) i + 1] += Pdi[(size_t) i]; Poi[(size_t) i + 1] += Poi[(size_t) i]; }
-
+   rows.offsets();
    HYPRE_BigInt cs[2] = {num_cpts_global[0], num_cpts_global[1]};
    hypre_ParCSRMatrix *P = hypre_ParCSRMatrixCreate(comm, A->global_num_rows, total_global_cpts, A->col_starts, cs,
-                                                    full_off, Pdi[(size_t) n], Poi[(size_t) n]);
+                                                    full_off, rows.nnz_diag(), rows.nnz_offd());
    hypre_CSRMatrixInitialize_v2(P->diag, 0, HYPRE_MEMORY_HOST);
    hypre_CSRMatrixInitialize_v2(P->offd, 0, HYPRE_MEMORY_HOST);
-   memcpy(P->diag->i, Pdi.data(), sizeof(HYPRE_Int) * ((size_t) n + 1));
-   memcpy(P->offd->i, Poi.data(), sizeof(HYPRE_Int) * ((size_t) n + 1));
-#pragma omp parallel for num_threads(T) schedule(static, 1)
-   for (int t = 0; t < T; t++)
-   {
-      const HYPRE_Int row_b = (HYPRE_Int) ((long long) n * t / T);
-      const size_t od = (size_t) Pdi[(size_t) row_b], oo = (size_t) Poi[(size_t) row_b];
-      if (!t_pdj[(size_t) t].empty())
-      {
-         memcpy(P->diag->j + od, t_pdj[(size_t) t].data(), sizeof(HYPRE_Int) * t_pdj[(size_t) t].size());
-         memcpy(P->diag->data + od, t_pda[(size_t) t].data(), sizeof(HYPRE_Real) * t_pda[(size_t) t].size());
-      }
-      if (!t_poj[(size_t) t].empty())
-      {
-         memcpy(P->offd->j + oo, t_poj[(size_t) t].data(), sizeof(HYPRE_Int) * t_poj[(size_t) t].size());
-         memcpy(P->offd->data + oo, t_poa[(size_t) t].data(), sizeof(HYPRE_Real) * t_poa[(size_t) t].size());
-      }
-   }
+   rows.stitch(P->diag, P->offd);
    if (trunc_factor != 0.0 || max_elmts > 0) { hypre_BoomerAMGInterpTruncation(P, trunc_factor, max_elmts); }
 
    // ---- column map of the off-rank block (aux_interp.c:777-900): used ghosts, ascending coarse id
-   {
-      const HYPRE_Int nnz_o = P->offd->i[n];
-      std::vector<char> used((size_t) std::max(full_off, 1), 0);
-      for (HYPRE_Int k = 0; k < nnz_o; k++) { used[(size_t) P->offd->j[k]] = 1; }
-      std::vector<HYPRE_BigInt> cmap;
-      for (HYPRE_Int g = 0; g < full_off; g++) { if (used[(size_t) g]) { cmap.push_back(f2c_offd[(size_t) g]); } }
-      std::sort(cmap.begin(), cmap.end());
-      cmap.erase(std::unique(cmap.begin(), cmap.end()), cmap.end());
-      for (HYPRE_Int k = 0; k < nnz_o; k++)
-      {
-         P->offd->j[k] = (HYPRE_Int) (std::lower_bound(cmap.begin(), cmap.end(), f2c_offd[(size_t) P->offd->j[k]]) - cmap.begin());
-      }
-      P->offd->num_cols = (HYPRE_Int) cmap.size();
-      if (!cmap.empty())
-      {
-         P->col_map_offd = hypre_TAlloc(HYPRE_BigInt, cmap.size(), HYPRE_MEMORY_HOST);
-         memcpy(P->col_map_offd, cmap.data(), sizeof(HYPRE_BigInt) * cmap.size());
-      }
-   }
+   set_col_map_offd(P, compact_offd_columns(P->offd->j, (size_t) P->offd->i[n], f2c_offd.data(), full_off));
    hypre_CSRMatrixSetRownnz(P->offd);
    hypre_MatvecCommPkgCreate(P);
-   hypre_Free(ext_pkg.recv_procs, HYPRE_MEMORY_HOST); hypre_Free(ext_pkg.recv_vec_starts, HYPRE_MEMORY_HOST);
-   hypre_Free(ext_pkg.send_procs, HYPRE_MEMORY_HOST); hypre_Free(ext_pkg.send_map_starts, HYPRE_MEMORY_HOST);
-   hypre_Free(ext_pkg.send_map_elmts, HYPRE_MEMORY_HOST);
    *P_ptr = P;
    return hypre_error_flag;
 }
@@ -495,37 +444,15 @@ HYPRE_Int dist_build_coarse_operator(hypre_ParCSRMatrix *RT, hypre_ParCSRMatrix 
    hypre_CSRMatrix *Ad = A->diag, *Ao = A->offd, *Pd = P->diag, *Po = P->offd;
    const HYPRE_Int ncP = Pd->num_cols, ncoP = Po->num_cols, ncoA = Ao->num_cols, ncoRT = RT->offd->num_cols;
    const HYPRE_Int ncRT = RT->diag->num_cols;
-   const HYPRE_BigInt first_c = P->first_col_diag, last_c = first_c + ncP - 1;
+   const HYPRE_BigInt first_c = P->first_col_diag;
    const bool square = (ncRT == ncP);
    hypre_CSRMatrix *Rd = nullptr, *Ro = nullptr;
    hypre_CSRMatrixTranspose(RT->diag, &Rd, 1);
    if (ncoRT) { hypre_CSRMatrixTranspose(RT->offd, &Ro, 1); }
 
    // ---- P_ext: rows of P for A's ghost columns, split into local-coarse and off-rank-coarse parts
-   ExtCSR Ps = extract_ext(P, pkgA, true, 0, nullptr, nullptr);
-   std::vector<HYPRE_Int> Pedi((size_t) ncoA + 1, 0), Peoi((size_t) ncoA + 1, 0), Pedj, Peoj;
-   std::vector<HYPRE_Real> Peda, Peoa;
-   std::vector<HYPRE_BigInt> Pe_big;
-   for (HYPRE_Int i = 0; i < ncoA; i++)
-   {
-      for (HYPRE_Int k = Ps.i[(size_t) i]; k < Ps.i[(size_t) i + 1]; k++)
-      {
-         const HYPRE_BigInt g = Ps.j[(size_t) k];
-         if (g < first_c || g > last_c) { Pe_big.push_back(g); Peoa.push_back(Ps.a[(size_t) k]); }
-         else { Pedj.push_back((HYPRE_Int) (g - first_c)); Peda.push_back(Ps.a[(size_t) k]); }
-      }
-      Pedi[(size_t) i + 1] = (HYPRE_Int) Pedj.size();
-      Peoi[(size_t) i + 1] = (HYPRE_Int) Pe_big.size();
-   }
-   std::vector<HYPRE_BigInt> cmapPext(Pe_big);
-   for (HYPRE_Int k = 0; k < ncoP; k++) { cmapPext.push_back(P->col_map_offd[k]); }
-   std::sort(cmapPext.begin(), cmapPext.end());
-   cmapPext.erase(std::unique(cmapPext.begin(), cmapPext.end()), cmapPext.end());
-   const HYPRE_Int ncoPext = (HYPRE_Int) cmapPext.size();
-   Peoj.resize(Pe_big.size());
-   for (size_t k = 0; k < Pe_big.size(); k++) { Peoj[k] = bsearch_big(cmapPext.data(), Pe_big[k], ncoPext); }
-   std::vector<HYPRE_Int> mapP2Pext((size_t) std::max(ncoP, 1));
-   for (HYPRE_Int k = 0; k < ncoP; k++) { mapP2Pext[(size_t) k] = bsearch_big(cmapPext.data(), P->col_map_offd[k], ncoPext); }
+   const PExt Pe = split_P_ext(extract_ext(P, pkgA, true, 0, nullptr, nullptr), ncoA, first_c, ncP, P->col_map_offd, ncoP);
+   const HYPRE_Int ncoPext = Pe.ncols_offd();
 
    // ---- RAP_int: rows of the product that belong to other ranks (one per ghost coarse column of RT)
    ExtCSR Rint;
@@ -543,18 +470,18 @@ HYPRE_Int dist_build_coarse_operator(hypre_ParCSRMatrix *RT, hypre_ParCSRMatrix 
             {
                const HYPRE_Int i2 = Ao->j[j2];
                const HYPRE_Real ra = r * Ao->data[j2];
-               for (HYPRE_Int j3 = Pedi[(size_t) i2]; j3 < Pedi[(size_t) i2 + 1]; j3++)
+               for (HYPRE_Int j3 = Pe.di[(size_t) i2]; j3 < Pe.di[(size_t) i2 + 1]; j3++)
                {
-                  const HYPRE_Int i3 = Pedj[(size_t) j3];
-                  const HYPRE_Real v = ra * Peda[(size_t) j3];
+                  const HYPRE_Int i3 = Pe.dj[(size_t) j3];
+                  const HYPRE_Real v = ra * Pe.da[(size_t) j3];
                   if (Pm[(size_t) i3] < begin) { Pm[(size_t) i3] = (long long) Rint.j.size(); Rint.j.push_back((HYPRE_BigInt) i3 + first_c); Rint.a.push_back(v); }
                   else { Rint.a[(size_t) Pm[(size_t) i3]] += v; }
                }
-               for (HYPRE_Int j3 = Peoi[(size_t) i2]; j3 < Peoi[(size_t) i2 + 1]; j3++)
+               for (HYPRE_Int j3 = Pe.oi[(size_t) i2]; j3 < Pe.oi[(size_t) i2 + 1]; j3++)
                {
-                  const HYPRE_Int i3 = Peoj[(size_t) j3] + ncP;
-                  const HYPRE_Real v = ra * Peoa[(size_t) j3];
-                  if (Pm[(size_t) i3] < begin) { Pm[(size_t) i3] = (long long) Rint.j.size(); Rint.j.push_back(cmapPext[(size_t) (i3 - ncP)]); Rint.a.push_back(v); }
+                  const HYPRE_Int i3 = Pe.oj[(size_t) j3] + ncP;
+                  const HYPRE_Real v = ra * Pe.oa[(size_t) j3];
+                  if (Pm[(size_t) i3] < begin) { Pm[(size_t) i3] = (long long) Rint.j.size(); Rint.j.push_back(Pe.cmap[(size_t) (i3 - ncP)]); Rint.a.push_back(v); }
                   else { Rint.a[(size_t) Pm[(size_t) i3]] += v; }
                }
             }
@@ -571,9 +498,9 @@ HYPRE_Int dist_build_coarse_operator(hypre_ParCSRMatrix *RT, hypre_ParCSRMatrix 
                }
                for (HYPRE_Int j3 = Po->i[i2]; j3 < Po->i[i2 + 1]; j3++)
                {
-                  const HYPRE_Int i3 = mapP2Pext[(size_t) Po->j[j3]] + ncP;
+                  const HYPRE_Int i3 = Pe.mapP2Pext[(size_t) Po->j[j3]] + ncP;
                   const HYPRE_Real v = ra * Po->data[j3];
-                  if (Pm[(size_t) i3] < begin) { Pm[(size_t) i3] = (long long) Rint.j.size(); Rint.j.push_back(cmapPext[(size_t) (i3 - ncP)]); Rint.a.push_back(v); }
+                  if (Pm[(size_t) i3] < begin) { Pm[(size_t) i3] = (long long) Rint.j.size(); Rint.j.push_back(Pe.cmap[(size_t) (i3 - ncP)]); Rint.a.push_back(v); }
                   else { Rint.a[(size_t) Pm[(size_t) i3]] += v; }
                }
             }
@@ -586,36 +513,19 @@ HYPRE_Int dist_build_coarse_operator(hypre_ParCSRMatrix *RT, hypre_ParCSRMatrix 
    ExtCSR Rext = exchange_rows(pkgRT, Rint, false, true);
    const HYPRE_Int nsendRT = pkgRT->send_map_starts[pkgRT->num_sends];
 
-   // ---- column map of the off-rank block of RAP
-   std::vector<HYPRE_BigInt> cmapRAP;
-   for (size_t k = 0; k < Rext.j.size(); k++) { if (Rext.j[k] < first_c || Rext.j[k] > last_c) { cmapRAP.push_back(Rext.j[k]); } }
-   for (HYPRE_Int k = 0; k < ncoPext; k++) { cmapRAP.push_back(cmapPext[(size_t) k]); }
-   std::sort(cmapRAP.begin(), cmapRAP.end());
-   cmapRAP.erase(std::unique(cmapRAP.begin(), cmapRAP.end()), cmapRAP.end());
-   const HYPRE_Int ncoRAP = (HYPRE_Int) cmapRAP.size();
-   std::vector<HYPRE_Int> mapP2RAP((size_t) std::max(ncoP, 1)), mapPext2RAP((size_t) std::max(ncoPext, 1));
-   for (HYPRE_Int k = 0; k < ncoP; k++) { mapP2RAP[(size_t) k] = bsearch_big(cmapRAP.data(), P->col_map_offd[k], ncoRAP); }
-   for (HYPRE_Int k = 0; k < ncoPext; k++) { mapPext2RAP[(size_t) k] = bsearch_big(cmapRAP.data(), cmapPext[(size_t) k], ncoRAP); }
-   for (size_t k = 0; k < Rext.j.size(); k++)
-   {
-      const HYPRE_BigInt g = Rext.j[k];
-      Rext.j[k] = (g < first_c || g > last_c) ? (HYPRE_BigInt) ncP + bsearch_big(cmapRAP.data(), g, ncoRAP) : g - first_c;
-   }
-   // which received rows feed local coarse row ic (in package order)
-   std::vector<std::vector<HYPRE_Int>> feeds((size_t) std::max(ncRT, 1));
-   for (HYPRE_Int s = 0; s < nsendRT; s++) { feeds[(size_t) pkgRT->send_map_elmts[s]].push_back(s); }
+   // ---- column map of the off-rank block of RAP, the received rows in its numbering, which of them feed which row
+   const RapExt Rx = number_received_rows(Rext, Pe, first_c, ncP, ncRT, pkgRT->send_map_elmts, nsendRT);
+   const HYPRE_Int ncoRAP = Rx.ncols_offd();
 
    // ---- local rows: diagonal slot, received contributions, RA_offd*P_ext, RA_diag*P
-   std::vector<HYPRE_Int> Cdi((size_t) ncRT + 1, 0), Coi((size_t) ncRT + 1, 0);
-   const int T = std::max(1, std::min(omp_get_max_threads(), ncRT / 2048 + 1));
-   std::vector<std::vector<HYPRE_Int>> t_cdj((size_t) T), t_coj((size_t) T);
-   std::vector<std::vector<HYPRE_Real>> t_cda((size_t) T), t_coa((size_t) T);
-#pragma omp parallel num_threads(T)
+   RowBlocks rows(ncRT, std::min(omp_get_max_threads(), ncRT / 2048 + 1), true);
+#pragma omp parallel num_threads(rows.T)
    {
       const int tid = omp_get_thread_num();
-      const HYPRE_Int ic_b = (HYPRE_Int) ((long long) ncRT * tid / T), ic_e = (HYPRE_Int) ((long long) ncRT * (tid + 1) / T);
-      std::vector<HYPRE_Int> &cdj = t_cdj[(size_t) tid], &coj = t_coj[(size_t) tid];
-      std::vector<HYPRE_Real> &cda = t_cda[(size_t) tid], &coa = t_coa[(size_t) tid];
+      HYPRE_Int ic_b, ic_e;
+      rows.rows_of(tid, &ic_b, &ic_e);
+      std::vector<HYPRE_Int> &cdj = rows.diag[(size_t) tid].j, &coj = rows.offd[(size_t) tid].j;
+      std::vector<HYPRE_Real> &cda = rows.diag[(size_t) tid].a, &coa = rows.offd[(size_t) tid].a;
       std::vector<long long> Pm((size_t) std::max(ncP + ncoRAP, 1), -1);
       std::vector<HYPRE_Int> Am((size_t) std::max(ncoA + Ad->num_cols, 1), -1);
       std::vector<HYPRE_Int> radj, raoj;
@@ -635,11 +545,12 @@ HYPRE_Int dist_build_coarse_operator(hypre_ParCSRMatrix *RT, hypre_ParCSRMatrix 
       {
          const long long bd = (long long) cdj.size(), bo = (long long) coj.size();
          if (square) { Pm[(size_t) ic] = bd; cdj.push_back(ic); cda.push_back(0.0); }
-         for (HYPRE_Int s : feeds[(size_t) ic])
+         for (HYPRE_Int q = Rx.Fi[(size_t) ic]; q < Rx.Fi[(size_t) ic + 1]; q++)
          {
+            const HYPRE_Int s = Rx.Fj[(size_t) q];
             for (HYPRE_Int k = Rext.i[(size_t) s]; k < Rext.i[(size_t) s + 1]; k++)
             {
-               const HYPRE_Int jc = (HYPRE_Int) Rext.j[(size_t) k];
+               const HYPRE_Int jc = Rx.xj[(size_t) k];
                if (jc < ncP) { add_d(jc, Rext.a[(size_t) k], bd); } else { add_o(jc - ncP, Rext.a[(size_t) k], bo); }
             }
          }
@@ -667,48 +578,27 @@ HYPRE_Int dist_build_coarse_operator(hypre_ParCSRMatrix *RT, hypre_ParCSRMatrix 
          {
             const HYPRE_Int i1 = raoj[q];
             const HYPRE_Real rap = raoa[q];
-            for (HYPRE_Int j2 = Pedi[(size_t) i1]; j2 < Pedi[(size_t) i1 + 1]; j2++) { add_d(Pedj[(size_t) j2], rap * Peda[(size_t) j2], bd); }
-            for (HYPRE_Int j2 = Peoi[(size_t) i1]; j2 < Peoi[(size_t) i1 + 1]; j2++) { add_o(mapPext2RAP[(size_t) Peoj[(size_t) j2]], rap * Peoa[(size_t) j2], bo); }
+            for (HYPRE_Int j2 = Pe.di[(size_t) i1]; j2 < Pe.di[(size_t) i1 + 1]; j2++) { add_d(Pe.dj[(size_t) j2], rap * Pe.da[(size_t) j2], bd); }
+            for (HYPRE_Int j2 = Pe.oi[(size_t) i1]; j2 < Pe.oi[(size_t) i1 + 1]; j2++) { add_o(Rx.mapPext2RAP[(size_t) Pe.oj[(size_t) j2]], rap * Pe.oa[(size_t) j2], bo); }
          }
          for (size_t q = 0; q < radj.size(); q++)
          {
             const HYPRE_Int i1 = radj[q];
             const HYPRE_Real rap = rada[q];
             for (HYPRE_Int j2 = Pd->i[i1]; j2 < Pd->i[i1 + 1]; j2++) { add_d(Pd->j[j2], rap * Pd->data[j2], bd); }
-            for (HYPRE_Int j2 = Po->i[i1]; j2 < Po->i[i1 + 1]; j2++) { add_o(mapP2RAP[(size_t) Po->j[j2]], rap * Po->data[j2], bo); }
+            for (HYPRE_Int j2 = Po->i[i1]; j2 < Po->i[i1 + 1]; j2++) { add_o(Rx.mapPext2RAP[(size_t) Pe.mapP2Pext[(size_t) Po->j[j2]]], rap * Po->data[j2], bo); }
          }
-         Cdi[(size_t) ic + 1] = (HYPRE_Int) ((long long) cdj.size() - bd);      // row lengths; offsets below
-         Coi[(size_t) ic + 1] = (HYPRE_Int) ((long long) coj.size() - bo);
+         rows.di[(size_t) ic + 1] = (HYPRE_Int) ((long long) cdj.size() - bd);
+         rows.oi[(size_t) ic + 1] = (HYPRE_Int) ((long long) coj.size() - bo);
       }
    }
-   for (HYPRE_Int ic = 0; ic < ncRT; ic++) { Cdi[(size_t) ic + 1] += Cdi[(size_t) ic]; Coi[(size_t) ic + 1] += Coi[(size_t) ic]; }
+   rows.offsets();
    hypre_ParCSRMatrix *C = hypre_ParCSRMatrixCreate(comm, RT->global_num_cols, P->global_num_cols, RT->col_starts,
-                                                    P->col_starts, ncoRAP, Cdi[(size_t) ncRT], Coi[(size_t) ncRT]);
+                                                    P->col_starts, ncoRAP, rows.nnz_diag(), rows.nnz_offd());
    hypre_CSRMatrixInitialize_v2(C->diag, 0, HYPRE_MEMORY_HOST);
    hypre_CSRMatrixInitialize_v2(C->offd, 0, HYPRE_MEMORY_HOST);
-   memcpy(C->diag->i, Cdi.data(), sizeof(HYPRE_Int) * ((size_t) ncRT + 1));
-   memcpy(C->offd->i, Coi.data(), sizeof(HYPRE_Int) * ((size_t) ncRT + 1));
-#pragma omp parallel for num_threads(T) schedule(static, 1)
-   for (int t = 0; t < T; t++)
-   {
-      const HYPRE_Int ic_b = (HYPRE_Int) ((long long) ncRT * t / T);
-      const size_t od = (size_t) Cdi[(size_t) ic_b], oo = (size_t) Coi[(size_t) ic_b];
-      if (!t_cdj[(size_t) t].empty())
-      {
-         memcpy(C->diag->j + od, t_cdj[(size_t) t].data(), sizeof(HYPRE_Int) * t_cdj[(size_t) t].size());
-         memcpy(C->diag->data + od, t_cda[(size_t) t].data(), sizeof(HYPRE_Real) * t_cda[(size_t) t].size());
-      }
-      if (!t_coj[(size_t) t].empty())
-      {
-         memcpy(C->offd->j + oo, t_coj[(size_t) t].data(), sizeof(HYPRE_Int) * t_coj[(size_t) t].size());
-         memcpy(C->offd->data + oo, t_coa[(size_t) t].data(), sizeof(HYPRE_Real) * t_coa[(size_t) t].size());
-      }
-   }
-   if (ncoRAP)
-   {
-      C->col_map_offd = hypre_TAlloc(HYPRE_BigInt, ncoRAP, HYPRE_MEMORY_HOST);
-      memcpy(C->col_map_offd, cmapRAP.data(), sizeof(HYPRE_BigInt) * (size_t) ncoRAP);
-   }
+   rows.stitch(C->diag, C->offd);
+   set_col_map_offd(C, Rx.cmap);
    if (keepTranspose) { RT->diagT = Rd; RT->offdT = Ro; }
    else { hypre_CSRMatrixDestroy(Rd); if (Ro) { hypre_CSRMatrixDestroy(Ro); } }
    hypre_CSRMatrixSetRownnz(C->offd);
@@ -729,40 +619,15 @@ HYPRE_Int dist_build_coarse_operator(hypre_ParCSRMatrix *RT, hypre_ParCSRMatrix 
 // ===========================================================================
 namespace {
 
-template <class T>
-T *upload(const T *h, size_t n)
-{
-   T *d = nullptr;
-   HIP_CHECK(hipMalloc((void **) &d, sizeof(T) * std::max<size_t>(n, 1)));
-   if (n)
-   {
-      HIP_CHECK(hipMemcpyAsync(d, h, sizeof(T) * n, hipMemcpyHostToDevice, stream()));
-      HIP_CHECK(hipStreamSynchronize(stream()));
-   }
-   return d;
-}
-template <class T>
-void fetch(T *h, const T *d, size_t n)
-{
-   if (!n) { return; }
-   HIP_CHECK(hipMemcpyAsync(h, d, sizeof(T) * n, hipMemcpyDeviceToHost, stream()));
-   HIP_CHECK(hipStreamSynchronize(stream()));
-}
-void dfree(void *p) { if (p) { HIP_CHECK(hipFree(p)); } }
-
 // a host CSR (rows of ghost points, extended column numbers) on the device
-struct DevCSR
+DevCSRBlock upload_csr(const std::vector<HYPRE_Int> &hi, const std::vector<HYPRE_Int> &hj, const std::vector<HYPRE_Real> *ha)
 {
-   int *i = nullptr, *j = nullptr;
-   double *a = nullptr;
-   void put(const std::vector<HYPRE_Int> &hi, const std::vector<HYPRE_Int> &hj, const std::vector<HYPRE_Real> *ha)
-   {
-      i = upload(hi.data(), hi.size());
-      j = upload(hj.data(), hj.size());
-      if (ha) { a = upload(ha->data(), ha->size()); }
-   }
-   ~DevCSR() { dfree(i); dfree(j); dfree(a); }
-};
+   DevCSRBlock b;
+   b.i = upload(hi.data(), hi.size());
+   b.j = upload(hj.data(), hj.size());
+   if (ha) { b.a = upload(ha->data(), ha->size()); }
+   return b;
+}
 
 const int *send_elmts_on_device(hypre_ParCSRCommPkg *pkg)
 {
@@ -773,6 +638,15 @@ const int *send_elmts_on_device(hypre_ParCSRCommPkg *pkg)
       hypre_TMemcpy(pkg->device_send_map_elmts, pkg->send_map_elmts, HYPRE_Int, tot, HYPRE_MEMORY_DEVICE, HYPRE_MEMORY_HOST);
    }
    return pkg->device_send_map_elmts;
+}
+
+struct CSRDestroy { void operator()(hypre_CSRMatrix *m) const { hypre_CSRMatrixDestroy(m); } };
+using OwnedCSR = std::unique_ptr<hypre_CSRMatrix, CSRDestroy>;
+OwnedCSR transposed(hypre_CSRMatrix *M)
+{
+   hypre_CSRMatrix *t = nullptr;
+   hypre_CSRMatrixTranspose(M, &t, 1);
+   return OwnedCSR(t);
 }
 
 }  // namespace
@@ -792,9 +666,7 @@ extern "C" HYPRE_Int hypre_amd_SetupDistTestDecline(HYPRE_Int what, HYPRE_Int ra
 }
 static bool test_declines(MPI_Comm comm, int what)
 {
-   HYPRE_Int me;
-   hypre_MPI_Comm_rank(comm, &me);
-   if (g_decline_count > 0 && g_decline_what == what && me == g_decline_rank) { g_decline_count--; return true; }
+   if (g_decline_count > 0 && g_decline_what == what && comm_rank(comm) == g_decline_rank) { g_decline_count--; return true; }
    return false;
 }
 
@@ -802,12 +674,11 @@ HYPRE_Int dist_device_create_S(hypre_ParCSRMatrix *A, HYPRE_Real theta, HYPRE_Re
 {
    hypre_CSRMatrix *dD = setup_device_twin_of(A->diag, 1), *dO = setup_device_twin_of(A->offd, 1);
    const HYPRE_Int n = A->diag->num_rows, nco = A->offd->num_cols;
-   int *Si = nullptr, *Sj = nullptr, snnz = 0;
-   device_strength_blocks(n, dD->i, dD->j, dD->data, nco ? dO->i : nullptr, dO->j, dO->data, theta, max_row_sum, &Si, &Sj, &snnz, stream());
-   hypre_ParCSRMatrix *S = hypre_ParCSRMatrixCreate(A->comm, A->global_num_rows, A->global_num_rows, A->row_starts, A->row_starts, 0, snnz, 0);
-   hypre_CSRMatrixDestroy(S->diag);
-   S->diag = setup_wrap_device_csr(n, n + nco, snnz, Si, Sj, nullptr);      // one pattern over the extended numbering
-   hypre_CSRMatrixInitialize_v2(S->offd, 0, HYPRE_MEMORY_HOST);
+   DevCSRBlock Sb;
+   device_strength_blocks(n, dD->i, dD->j, dD->data, nco ? dO->i : nullptr, dO->j, dO->data, theta, max_row_sum, &Sb.i.p, &Sb.j.p, &Sb.nnz, stream());
+   hypre_ParCSRMatrix *S = hypre_ParCSRMatrixCreate(A->comm, A->global_num_rows, A->global_num_rows, A->row_starts, A->row_starts, 0, Sb.nnz, 0);
+   adopt_device_blocks(S, Sb);
+   S->diag->num_cols = n + nco;                  // one pattern over the extended numbering
    *S_ptr = S;
    return hypre_error_flag;
 }
@@ -815,8 +686,7 @@ HYPRE_Int dist_device_create_S(hypre_ParCSRMatrix *A, HYPRE_Real theta, HYPRE_Re
 HYPRE_Int dist_device_pmis(hypre_ParCSRMatrix *S, hypre_ParCSRMatrix *A, HYPRE_Int CF_init, HYPRE_Int *CF_host)
 {
    MPI_Comm comm = A->comm;
-   HYPRE_Int my_id;
-   hypre_MPI_Comm_rank(comm, &my_id);
+   const int my_id = comm_rank(comm);
    if (!A->comm_pkg) { hypre_MatvecCommPkgCreate(A); }
    hypre_ParCSRCommPkg *pkg = A->comm_pkg;
    const HYPRE_Int n = A->diag->num_rows, nco = A->offd->num_cols;
@@ -830,17 +700,18 @@ HYPRE_Int dist_device_pmis(hypre_ParCSRMatrix *S, hypre_ParCSRMatrix *A, HYPRE_I
       std::sort(order.begin(), order.end());
       for (HYPRE_Int q = 1; q < tot; q++) { if (order[(size_t) q].first == order[(size_t) q - 1].first) { prev[(size_t) order[(size_t) q].second] = order[(size_t) q - 1].second; } }
    }
-   int *d_prev = upload(prev.data(), (size_t) tot);
+   DevBuf<int> d_prev = upload(prev.data(), (size_t) tot);
    HYPRE_Int *dCF = hypre_TAlloc(HYPRE_Int, (size_t) std::max(n + nco, 1), HYPRE_MEMORY_DEVICE);
    hypre_CSRMatrix *Sd = S->diag;
    device_pmis_dist(n, nco, Sd->i, Sd->j, Sd->num_nonzeros, 2747u + (CF_init == 2 ? 0u : (unsigned) my_id),
                     CF_init == 2 ? (unsigned long long) S->first_row_index : 0ull, pkg, d_elmts, d_prev, comm, dCF, stream());
    fetch(CF_host, dCF, (size_t) n);
-   dfree(d_prev);
    setup_register_device_marker(CF_host, dCF);
    return hypre_error_flag;
 }
 
+// Ways out: (1) some rank's kernel declined — nothing was adopted; Pd, Po and the extra package go with their owners;
+// (2) the end — Pd and Po gave their arrays to P (adopt_device_blocks), the extra package goes with gh.
 HYPRE_Int dist_device_extpi_interp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, hypre_ParCSRMatrix *S,
                                    HYPRE_BigInt *num_cpts_global, HYPRE_BigInt total_global_cpts, HYPRE_Real trunc_factor,
                                    HYPRE_Int max_elmts, HYPRE_Int first_rung, hypre_ParCSRMatrix **P_ptr)
@@ -852,53 +723,37 @@ HYPRE_Int dist_device_extpi_interp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, 
    hypre_ParCSRCommPkg *pkg = A->comm_pkg;
    hypre_CSRMatrix *dD = setup_device_twin_of(A->diag, 1), *dO = setup_device_twin_of(A->offd, 1), *Sx = S->diag;
    const HYPRE_Int n = A->diag->num_rows, nco = A->offd->num_cols;
-   const HYPRE_BigInt col_1 = A->first_row_index, col_n = col_1 + n;
+   const HYPRE_BigInt col_1 = A->first_row_index;
    const HYPRE_BigInt my_first_cpt = num_cpts_global[0];
    const HYPRE_Int ncP = (HYPRE_Int) (num_cpts_global[1] - num_cpts_global[0]);
    const HYPRE_Int tot = pkg->send_map_starts[pkg->num_sends];
    const int *d_elmts = send_elmts_on_device(pkg);
    HYPRE_Int *dCF = setup_device_marker_of(CF_marker, n);          // left by the device coarsening (or uploaded now)
 
-   // ---- markers of the ghost points, the rows of A and S the neighbours hold for them
-   std::vector<HYPRE_Int> CF_offd((size_t) std::max(nco, 1));
-   halo_fwd<HYPRE_Int>(pkg, CF_marker, CF_offd.data(), 11);
-   long long *d_cmap = upload((const long long *) A->col_map_offd, (size_t) nco);
-   int *dCFx = nullptr;                                            // markers over [local | ghosts of A]
-   HIP_CHECK(hipMalloc((void **) &dCFx, sizeof(int) * (size_t) std::max(n + nco, 1)));
-   if (n) { HIP_CHECK(hipMemcpyAsync(dCFx, dCF, sizeof(int) * (size_t) n, hipMemcpyDeviceToDevice, st)); }
-   if (nco) { HIP_CHECK(hipMemcpyAsync(dCFx + n, CF_offd.data(), sizeof(int) * (size_t) nco, hipMemcpyHostToDevice, st)); }
-   HIP_CHECK(hipStreamSynchronize(st));
-   ExtCSR Aext, Sop;
+   // ---- markers of the ghost points, the rows of A and S the neighbours hold for them (extracted on the device), new nodes
+   ExtPIGhosts gh(A, CF_marker, [&](const std::vector<HYPRE_Int> &cf_offd, ExtCSR &Aext, ExtCSR &Sop)
    {
-      ExtCSR rows;
+      DevBuf<long long> d_cmap = upload((const long long *) A->col_map_offd, (size_t) nco);
+      DevBuf<int> dCFx = dev_alloc<int>((size_t) n + (size_t) nco);                      // markers over [local | ghosts of A]
+      if (n) { HIP_CHECK(hipMemcpyAsync(dCFx, dCF, sizeof(int) * (size_t) n, hipMemcpyDeviceToDevice, st)); }
+      if (nco) { HIP_CHECK(hipMemcpyAsync(dCFx + n, cf_offd.data(), sizeof(int) * (size_t) nco, hipMemcpyHostToDevice, st)); }
+      HIP_CHECK(hipStreamSynchronize(st));
+      ExtCSR rows, srows;
       device_extract_rows(2, tot, d_elmts, dD->i, dD->j, dD->data, nco ? dO->i : nullptr, dO->j, dO->data, (long long) A->first_col_diag,
                           d_cmap, dCF, rows.i, rows.j, rows.a, st);
       if (rows.j.empty()) { rows.j.push_back(0); rows.a.push_back(0.0); }
       Aext = exchange_rows(pkg, rows, true, true);
-   }
-   {
-      ExtCSR rows;
-      device_extract_S_rows(tot, d_elmts, n, Sx->i, Sx->j, (long long) A->first_col_diag, d_cmap, dCFx, rows.i, rows.j, st);
-      if (rows.j.empty()) { rows.j.push_back(0); }
-      Sop = exchange_rows(pkg, rows, true, false);
-   }
-   dfree(d_cmap); dfree(dCFx);
-   std::vector<HYPRE_BigInt> found;
-   ghost_row_numbering(A->col_map_offd, nco, col_1, col_n, CF_offd, Aext, Sop, found);
-   const HYPRE_Int newoff = (HYPRE_Int) found.size(), full_off = nco + newoff;
-   hypre_ParCSRCommPkg ext_pkg;
-   memset(&ext_pkg, 0, sizeof(ext_pkg));
-   ext_pkg.comm = comm;
-   hypre_ParCSRCommPkgCreate_core(comm, found.empty() ? nullptr : found.data(), A->first_col_diag, A->col_starts,
-                                  A->diag->num_cols, newoff, &ext_pkg.num_recvs, &ext_pkg.recv_procs,
-                                  &ext_pkg.recv_vec_starts, &ext_pkg.num_sends, &ext_pkg.send_procs,
-                                  &ext_pkg.send_map_starts, &ext_pkg.send_map_elmts);
-   CF_offd.resize((size_t) std::max(full_off, 1));
-   halo_fwd<HYPRE_Int>(&ext_pkg, CF_marker, CF_offd.data() + nco, 11);
+      device_extract_S_rows(tot, d_elmts, n, Sx->i, Sx->j, (long long) A->first_col_diag, d_cmap, dCFx, srows.i, srows.j, st);
+      if (srows.j.empty()) { srows.j.push_back(0); }
+      Sop = exchange_rows(pkg, srows, true, false);
+   });
+   const std::vector<HYPRE_Int> &CF_offd = gh.CF_offd;
+   const ExtCSR &Aext = gh.Aext, &Sop = gh.Sop;
+   const HYPRE_Int full_off = gh.full_off;
+   hypre_ParCSRCommPkg *ext_pkg = &gh.ext->pkg;
 
    // ---- coarse numbers: local ones on the device; the ghosts' global ones through the two packages
-   int *dF2Cx = nullptr;                                          // over [local | ghosts | new nodes]
-   HIP_CHECK(hipMalloc((void **) &dF2Cx, sizeof(int) * (size_t) std::max(n + full_off, 1)));
+   DevBuf<int> dF2Cx = dev_alloc<int>((size_t) n + (size_t) full_off);                   // over [local | ghosts | new nodes]
    device_coarse_numbering(n, dCF, dF2Cx, st);
    std::vector<HYPRE_BigInt> f2c_offd((size_t) std::max(full_off, 1), -1);
    auto coarse_ids_out = [&](hypre_ParCSRCommPkg *pk, const int *d_idx, HYPRE_BigInt *ghost)
@@ -908,11 +763,9 @@ HYPRE_Int dist_device_extpi_interp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, 
       std::vector<HYPRE_BigInt> buf((size_t) std::max(t, 1));
       if (t)
       {
-         int *d_out = nullptr;
-         HIP_CHECK(hipMalloc((void **) &d_out, sizeof(int) * (size_t) t));
+         DevBuf<int> d_out = dev_alloc<int>((size_t) t);
          launch_gather_int(dF2Cx, d_idx, d_out, (size_t) t, st);
-         fetch(loc.data(), d_out, (size_t) t);
-         dfree(d_out);
+         fetch(loc.data(), d_out.p, (size_t) t);
       }
       for (HYPRE_Int k = 0; k < t; k++) { buf[(size_t) k] = (HYPRE_BigInt) loc[(size_t) k] + my_first_cpt; }
       hypre_ParCSRCommHandle *h = hypre_ParCSRCommHandleCreate(21, pk, buf.data(), ghost);
@@ -920,10 +773,8 @@ HYPRE_Int dist_device_extpi_interp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, 
    };
    coarse_ids_out(pkg, d_elmts, f2c_offd.data());
    {
-      const HYPRE_Int t = ext_pkg.send_map_starts[ext_pkg.num_sends];
-      int *d_idx = upload(ext_pkg.send_map_elmts, (size_t) t);
-      coarse_ids_out(&ext_pkg, d_idx, f2c_offd.data() + nco);
-      dfree(d_idx);
+      DevBuf<int> d_idx = upload(ext_pkg->send_map_elmts, (size_t) ext_pkg->send_map_starts[ext_pkg->num_sends]);
+      coarse_ids_out(ext_pkg, d_idx, f2c_offd.data() + nco);
    }
 
    // ---- extended matrices: the ghost F points' rows behind the local ones.  A fetched row of A holds only the entries the
@@ -946,20 +797,14 @@ HYPRE_Int dist_device_extpi_interp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, 
       si[(size_t) k + 1] = (HYPRE_Int) sj.size();
    }
    for (HYPRE_Int k = nco; k < full_off; k++) { gi[(size_t) k + 1] = gi[(size_t) k]; si[(size_t) k + 1] = si[(size_t) k]; }
-   bool ok = true;
-   int *Pdi = nullptr, *Pdj = nullptr, *Poi = nullptr, *Poj = nullptr, dnnz = 0, onnz = 0;
-   double *Pda = nullptr, *Poa = nullptr;
+   DevCSRBlock Pd, Po;
+   bool ok;
    {
-      DevCSR G, GS;
-      G.put(gi, gj, &ga);
-      GS.put(si, sj, nullptr);
-      int *Ei = nullptr, *Ej = nullptr, *SEi = nullptr, *SEj = nullptr, ennz = 0, sennz = 0;
-      double *Ea = nullptr;
-      device_extend_csr(n, dD->i, dD->j, dD->data, nco ? dO->i : nullptr, dO->j, dO->data, n, full_off, G.i, G.j, G.a, &Ei, &Ej, &Ea, &ennz, st);
-      device_extend_csr(n, Sx->i, Sx->j, nullptr, nullptr, nullptr, nullptr, 0, full_off, GS.i, GS.j, nullptr, &SEi, &SEj, nullptr, &sennz, st);
+      DevCSRBlock G = upload_csr(gi, gj, &ga), GS = upload_csr(si, sj, nullptr), E, SE;
+      device_extend_csr(n, dD->i, dD->j, dD->data, nco ? dO->i : nullptr, dO->j, dO->data, n, full_off, G.i, G.j, G.a, &E.i.p, &E.j.p, &E.a.p, &E.nnz, st);
+      device_extend_csr(n, Sx->i, Sx->j, nullptr, nullptr, nullptr, nullptr, 0, full_off, GS.i, GS.j, nullptr, &SE.i.p, &SE.j.p, nullptr, &SE.nnz, st);
       // markers and coarse numbers of the ghost points: an off-rank C point's column is ncP + its ghost number
-      int *dCFf = nullptr;
-      HIP_CHECK(hipMalloc((void **) &dCFf, sizeof(int) * (size_t) std::max(n + full_off, 1)));
+      DevBuf<int> dCFf = dev_alloc<int>((size_t) n + (size_t) full_off);
       std::vector<int> f2c_g((size_t) std::max(full_off, 1));
       for (HYPRE_Int k = 0; k < full_off; k++) { f2c_g[(size_t) k] = CF_offd[(size_t) k] >= 0 ? ncP + k : -1; }
       if (n) { HIP_CHECK(hipMemcpyAsync(dCFf, dCF, sizeof(int) * (size_t) n, hipMemcpyDeviceToDevice, st)); }
@@ -969,65 +814,41 @@ HYPRE_Int dist_device_extpi_interp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, 
          HIP_CHECK(hipMemcpyAsync(dF2Cx + n, f2c_g.data(), sizeof(int) * (size_t) full_off, hipMemcpyHostToDevice, st));
       }
       HIP_CHECK(hipStreamSynchronize(st));
-      ok = device_extpi(n, Ei, Ej, Ea, SEi, SEj, dCFf, dF2Cx, trunc_factor, max_elmts, first_rung, &Pdi, &Pdj, &Pda, &dnnz, st,
-                        ncP, &Poi, &Poj, &Poa, &onnz);
-      dfree(Ei); dfree(Ej); dfree(Ea); dfree(SEi); dfree(SEj); dfree(dCFf);
+      ok = device_extpi(n, E.i, E.j, E.a, SE.i, SE.j, dCFf, dF2Cx, trunc_factor, max_elmts, first_rung, &Pd.i.p, &Pd.j.p, &Pd.a.p, &Pd.nnz, st,
+                        ncP, &Po.i.p, &Po.j.p, &Po.a.p, &Po.nnz);
    }
-   dfree(dF2Cx);
-   auto free_ext_pkg = [&]()
-   {
-      hypre_Free(ext_pkg.recv_procs, HYPRE_MEMORY_HOST); hypre_Free(ext_pkg.recv_vec_starts, HYPRE_MEMORY_HOST);
-      hypre_Free(ext_pkg.send_procs, HYPRE_MEMORY_HOST); hypre_Free(ext_pkg.send_map_starts, HYPRE_MEMORY_HOST);
-      hypre_Free(ext_pkg.send_map_elmts, HYPRE_MEMORY_HOST);
-   };
-   if (ok && test_declines(comm, 1)) { dfree(Pdi); dfree(Pdj); dfree(Pda); dfree(Poi); dfree(Poj); dfree(Poa); ok = false; }
-   if (!all_ranks_agree(comm, ok))
-   {
-      if (ok) { dfree(Pdi); dfree(Pdj); dfree(Pda); dfree(Poi); dfree(Poj); dfree(Poa); }
-      free_ext_pkg();
-      return hypre_error_flag;
-   }
+   dF2Cx.reset();
+   if (ok && test_declines(comm, 1)) { ok = false; }
+   if (!all_ranks_agree(comm, ok)) { return hypre_error_flag; }
 
    // ---- column map of the off-rank block (aux_interp.c:777-900): the ghosts in use, ascending coarse number
-   std::vector<HYPRE_BigInt> cmap;
+   GhostCompaction cm;
    {
-      int *d_used = nullptr;
-      HIP_CHECK(hipMalloc((void **) &d_used, sizeof(int) * (size_t) std::max(full_off, 1)));
+      DevBuf<int> d_used = dev_alloc<int>((size_t) full_off);
       HIP_CHECK(hipMemsetAsync(d_used, 0, sizeof(int) * (size_t) std::max(full_off, 1), st));
-      launch_mark_used(Poj, (size_t) onnz, d_used, st);
+      launch_mark_used(Po.j, (size_t) Po.nnz, d_used, st);
       std::vector<int> used((size_t) std::max(full_off, 1), 0);
-      fetch(used.data(), d_used, (size_t) full_off);
-      for (HYPRE_Int g = 0; g < full_off; g++) { if (used[(size_t) g]) { cmap.push_back(f2c_offd[(size_t) g]); } }
-      std::sort(cmap.begin(), cmap.end());
-      cmap.erase(std::unique(cmap.begin(), cmap.end()), cmap.end());
-      std::vector<int> renum((size_t) std::max(full_off, 1), 0);
-      for (HYPRE_Int g = 0; g < full_off; g++)
-      {
-         if (used[(size_t) g]) { renum[(size_t) g] = (int) (std::lower_bound(cmap.begin(), cmap.end(), f2c_offd[(size_t) g]) - cmap.begin()); }
-      }
-      HIP_CHECK(hipMemcpyAsync(d_used, renum.data(), sizeof(int) * (size_t) full_off, hipMemcpyHostToDevice, st));
-      launch_renumber(Poj, (size_t) onnz, 0, d_used, st);
+      fetch(used.data(), d_used.p, (size_t) full_off);
+      cm = compact_ghosts(used.data(), f2c_offd.data(), full_off);
+      HIP_CHECK(hipMemcpyAsync(d_used, cm.renum.data(), sizeof(int) * (size_t) full_off, hipMemcpyHostToDevice, st));
+      launch_renumber(Po.j, (size_t) Po.nnz, 0, d_used, st);
       HIP_CHECK(hipStreamSynchronize(st));
-      dfree(d_used);
    }
    HYPRE_BigInt cs[2] = {num_cpts_global[0], num_cpts_global[1]};
    hypre_ParCSRMatrix *P = hypre_ParCSRMatrixCreate(comm, A->global_num_rows, total_global_cpts, A->col_starts, cs,
-                                                    (HYPRE_Int) cmap.size(), dnnz, onnz);
-   hypre_CSRMatrixDestroy(P->diag); hypre_CSRMatrixDestroy(P->offd);
-   P->diag = setup_wrap_device_csr(n, ncP, dnnz, Pdi, Pdj, Pda);
-   P->offd = setup_wrap_device_csr(n, (HYPRE_Int) cmap.size(), onnz, Poi, Poj, Poa);
-   if (!cmap.empty())
-   {
-      P->col_map_offd = hypre_TAlloc(HYPRE_BigInt, cmap.size(), HYPRE_MEMORY_HOST);
-      memcpy(P->col_map_offd, cmap.data(), sizeof(HYPRE_BigInt) * cmap.size());
-   }
+                                                    (HYPRE_Int) cm.cmap.size(), Pd.nnz, Po.nnz);
+   adopt_device_blocks(P, Pd, &Po);
+   set_col_map_offd(P, cm.cmap);
    hypre_CSRMatrixSetRownnz(P->offd);
    hypre_MatvecCommPkgCreate(P);
-   free_ext_pkg();
    *P_ptr = P;
    return hypre_error_flag;
 }
 
+// Ways out: (1) the rows for the neighbours declined on some rank, (2) the product declined on some rank — nothing was
+// adopted: the extended operator X, the block the kernel may have returned on this rank (I, or Cd and Co) and both
+// transposes go with their owners; (3) the end — Cd and Co gave their arrays to C, the transposes to RT when it keeps
+// them, X and whatever was not handed on go with their owners.
 HYPRE_Int dist_device_coarse_operator(hypre_ParCSRMatrix *RT, hypre_ParCSRMatrix *A, hypre_ParCSRMatrix *P,
                                       HYPRE_Int keepTranspose, hypre_ParCSRMatrix **RAP_ptr)
 {
@@ -1041,177 +862,94 @@ HYPRE_Int dist_device_coarse_operator(hypre_ParCSRMatrix *RT, hypre_ParCSRMatrix
    hypre_CSRMatrix *Pd = setup_device_twin_of(P->diag, 1), *Po = setup_device_twin_of(P->offd, 1);
    const HYPRE_Int n = A->diag->num_rows, ncoA = A->offd->num_cols;
    const HYPRE_Int ncP = P->diag->num_cols, ncoP = P->offd->num_cols, ncoRT = RT->offd->num_cols, ncRT = RT->diag->num_cols;
-   const HYPRE_BigInt first_c = P->first_col_diag, last_c = first_c + ncP - 1;
-   hypre_CSRMatrix *Rd = nullptr, *Ro = nullptr;
-   hypre_CSRMatrixTranspose(Pd, &Rd, 1);
-   if (ncoRT) { hypre_CSRMatrixTranspose(Po, &Ro, 1); }
+   const HYPRE_BigInt first_c = P->first_col_diag;
+   OwnedCSR Rd = transposed(Pd), Ro = ncoRT ? transposed(Po) : OwnedCSR();
 
    // ---- P_ext: the rows of P of A's ghost columns, local coarse columns first, off-rank ones behind
    ExtCSR Ps;
    {
       const HYPRE_Int totA = pkgA->send_map_starts[pkgA->num_sends];
-      long long *d_cmapP = upload((const long long *) P->col_map_offd, (size_t) ncoP);
+      DevBuf<long long> d_cmapP = upload((const long long *) P->col_map_offd, (size_t) ncoP);
       ExtCSR rows;
       device_extract_rows(0, totA, send_elmts_on_device(pkgA), Pd->i, Pd->j, Pd->data, ncoP ? Po->i : nullptr, Po->j, Po->data,
                           (long long) first_c, d_cmapP, nullptr, rows.i, rows.j, rows.a, st);
-      dfree(d_cmapP);
       if (rows.j.empty()) { rows.j.push_back(0); rows.a.push_back(0.0); }
       Ps = exchange_rows(pkgA, rows, true, true);
    }
-   std::vector<HYPRE_Int> Pedi((size_t) ncoA + 1, 0), Peoi((size_t) ncoA + 1, 0), Pedj, Peoj;
-   std::vector<HYPRE_Real> Peda, Peoa;
-   std::vector<HYPRE_BigInt> Pe_big;
-   for (HYPRE_Int i = 0; i < ncoA; i++)
-   {
-      for (HYPRE_Int k = Ps.i[(size_t) i]; k < Ps.i[(size_t) i + 1]; k++)
-      {
-         const HYPRE_BigInt g = Ps.j[(size_t) k];
-         if (g < first_c || g > last_c) { Pe_big.push_back(g); Peoa.push_back(Ps.a[(size_t) k]); }
-         else { Pedj.push_back((HYPRE_Int) (g - first_c)); Peda.push_back(Ps.a[(size_t) k]); }
-      }
-      Pedi[(size_t) i + 1] = (HYPRE_Int) Pedj.size();
-      Peoi[(size_t) i + 1] = (HYPRE_Int) Pe_big.size();
-   }
-   std::vector<HYPRE_BigInt> cmapPext(Pe_big);
-   for (HYPRE_Int k = 0; k < ncoP; k++) { cmapPext.push_back(P->col_map_offd[k]); }
-   std::sort(cmapPext.begin(), cmapPext.end());
-   cmapPext.erase(std::unique(cmapPext.begin(), cmapPext.end()), cmapPext.end());
-   const HYPRE_Int ncoPext = (HYPRE_Int) cmapPext.size();
-   Peoj.resize(Pe_big.size());
-   for (size_t k = 0; k < Pe_big.size(); k++) { Peoj[k] = bsearch_big(cmapPext.data(), Pe_big[k], ncoPext); }
-   std::vector<int> mapP2Pext((size_t) std::max(ncoP, 1));
-   for (HYPRE_Int k = 0; k < ncoP; k++) { mapP2Pext[(size_t) k] = bsearch_big(cmapPext.data(), P->col_map_offd[k], ncoPext); }
+   const PExt Pe = split_P_ext(Ps, ncoA, first_c, ncP, P->col_map_offd, ncoP);
+   const HYPRE_Int ncoPext = Pe.ncols_offd();
 
    // ---- the extended interpolation operator: rows of the local points [P_diag | ncP + P_offd in P_ext's numbering], then
    // the ghost points' rows
-   int *Xi = nullptr, *Xj = nullptr, xnnz = 0;
-   double *Xa = nullptr;
+   DevCSRBlock X;
    {
       std::vector<HYPRE_Int> gi((size_t) ncoA + 1, 0), gj;
       std::vector<HYPRE_Real> ga;
       for (HYPRE_Int i = 0; i < ncoA; i++)
       {
-         for (HYPRE_Int k = Pedi[(size_t) i]; k < Pedi[(size_t) i + 1]; k++) { gj.push_back(Pedj[(size_t) k]); ga.push_back(Peda[(size_t) k]); }
-         for (HYPRE_Int k = Peoi[(size_t) i]; k < Peoi[(size_t) i + 1]; k++) { gj.push_back(ncP + Peoj[(size_t) k]); ga.push_back(Peoa[(size_t) k]); }
+         for (HYPRE_Int k = Pe.di[(size_t) i]; k < Pe.di[(size_t) i + 1]; k++) { gj.push_back(Pe.dj[(size_t) k]); ga.push_back(Pe.da[(size_t) k]); }
+         for (HYPRE_Int k = Pe.oi[(size_t) i]; k < Pe.oi[(size_t) i + 1]; k++) { gj.push_back(ncP + Pe.oj[(size_t) k]); ga.push_back(Pe.oa[(size_t) k]); }
          gi[(size_t) i + 1] = (HYPRE_Int) gj.size();
       }
-      DevCSR G;
-      G.put(gi, gj, &ga);
-      int *d_map = upload(mapP2Pext.data(), (size_t) ncoP), *oj = nullptr;
+      DevCSRBlock G = upload_csr(gi, gj, &ga);
       const HYPRE_Int onz = Po->num_nonzeros;
-      HIP_CHECK(hipMalloc((void **) &oj, sizeof(int) * (size_t) std::max(onz, 1)));
+      DevBuf<int> d_map = upload(Pe.mapP2Pext.data(), (size_t) ncoP), oj = dev_alloc<int>((size_t) onz);
       if (onz) { HIP_CHECK(hipMemcpyAsync(oj, Po->j, sizeof(int) * (size_t) onz, hipMemcpyDeviceToDevice, st)); }
       launch_renumber(oj, (size_t) onz, 0, d_map, st);
-      device_extend_csr(n, Pd->i, Pd->j, Pd->data, ncoP ? Po->i : nullptr, oj, Po->data, ncP, ncoA, G.i, G.j, G.a, &Xi, &Xj, &Xa, &xnnz, st);
-      dfree(d_map); dfree(oj);
+      device_extend_csr(n, Pd->i, Pd->j, Pd->data, ncoP ? Po->i : nullptr, oj, Po->data, ncP, ncoA, G.i, G.j, G.a, &X.i.p, &X.j.p, &X.a.p, &X.nnz, st);
    }
-   const int maxP = device_max_row_nnz(Xi, n + ncoA, st);
-   auto give_up = [&]()
-   {
-      dfree(Xi); dfree(Xj); dfree(Xa);
-      hypre_CSRMatrixDestroy(Rd);
-      if (Ro) { hypre_CSRMatrixDestroy(Ro); }
-      return hypre_error_flag;
-   };
+   const int maxP = device_max_row_nnz(X.i, n + ncoA, st);
 
    // ---- the rows of the product that belong to the neighbours (one per ghost coarse column of P), sent home
    ExtCSR Rint;
    {
-      int *Ii = nullptr, *Ij = nullptr, innz = 0;
-      double *Ia = nullptr;
-      const bool ok = device_rap_dist(true, ncoRT, 0, ncP + ncoPext, maxP, 0, Ro ? Ro->i : nullptr, Ro ? Ro->j : nullptr, Ro ? Ro->data : nullptr,
-                                      dD->i, dD->j, dD->data, ncoA ? dO->i : nullptr, dO->j, dO->data, n, n, Xi, Xj, Xa,
-                                      nullptr, nullptr, nullptr, nullptr, nullptr, ncP, &Ii, &Ij, &Ia, &innz, nullptr, nullptr, nullptr, nullptr, st);
-      bool okk = ok;
-      if (okk && test_declines(comm, 2)) { dfree(Ii); dfree(Ij); dfree(Ia); okk = false; }
-      if (!all_ranks_agree(comm, okk))
-      {
-         if (okk) { dfree(Ii); dfree(Ij); dfree(Ia); }
-         return give_up();
-      }
+      DevCSRBlock I;
+      bool ok = device_rap_dist(true, ncoRT, 0, ncP + ncoPext, maxP, 0, Ro ? Ro->i : nullptr, Ro ? Ro->j : nullptr, Ro ? Ro->data : nullptr,
+                                dD->i, dD->j, dD->data, ncoA ? dO->i : nullptr, dO->j, dO->data, n, n, X.i, X.j, X.a,
+                                nullptr, nullptr, nullptr, nullptr, nullptr, ncP, &I.i.p, &I.j.p, &I.a.p, &I.nnz, nullptr, nullptr, nullptr, nullptr, st);
+      if (ok && test_declines(comm, 2)) { ok = false; }
+      if (!all_ranks_agree(comm, ok)) { return hypre_error_flag; }
+      const int innz = I.nnz;
       Rint.i.assign((size_t) ncoRT + 1, 0);
       std::vector<int> hj((size_t) std::max(innz, 1));
       Rint.a.resize((size_t) std::max(innz, 1));
-      fetch(Rint.i.data(), Ii, (size_t) ncoRT + 1);
-      fetch(hj.data(), Ij, (size_t) innz);
-      fetch(Rint.a.data(), Ia, (size_t) innz);
-      dfree(Ii); dfree(Ij); dfree(Ia);
+      fetch(Rint.i.data(), I.i.p, (size_t) ncoRT + 1);
+      fetch(hj.data(), I.j.p, (size_t) innz);
+      fetch(Rint.a.data(), I.a.p, (size_t) innz);
       Rint.j.resize((size_t) std::max(innz, 1), 0);
       for (HYPRE_Int k = 0; k < innz; k++)
       {
          const int c = hj[(size_t) k];
-         Rint.j[(size_t) k] = c < ncP ? (HYPRE_BigInt) c + first_c : cmapPext[(size_t) (c - ncP)];
+         Rint.j[(size_t) k] = c < ncP ? (HYPRE_BigInt) c + first_c : Pe.cmap[(size_t) (c - ncP)];
       }
       if (innz == 0) { Rint.j.assign(1, 0); Rint.a.assign(1, 0.0); }
       else { Rint.j.resize((size_t) innz); Rint.a.resize((size_t) innz); }
    }
-   ExtCSR Rext = exchange_rows(pkgRT, Rint, false, true);
+   const ExtCSR Rext = exchange_rows(pkgRT, Rint, false, true);
    const HYPRE_Int nsendRT = pkgRT->send_map_starts[pkgRT->num_sends];
 
-   // ---- column map of the off-rank block of the product
-   std::vector<HYPRE_BigInt> cmapRAP;
-   for (size_t k = 0; k < Rext.j.size(); k++) { if (Rext.j[k] < first_c || Rext.j[k] > last_c) { cmapRAP.push_back(Rext.j[k]); } }
-   for (HYPRE_Int k = 0; k < ncoPext; k++) { cmapRAP.push_back(cmapPext[(size_t) k]); }
-   std::sort(cmapRAP.begin(), cmapRAP.end());
-   cmapRAP.erase(std::unique(cmapRAP.begin(), cmapRAP.end()), cmapRAP.end());
-   const HYPRE_Int ncoRAP = (HYPRE_Int) cmapRAP.size();
-   std::vector<int> mapPext2RAP((size_t) std::max(ncoPext, 1));
-   for (HYPRE_Int k = 0; k < ncoPext; k++) { mapPext2RAP[(size_t) k] = bsearch_big(cmapRAP.data(), cmapPext[(size_t) k], ncoRAP); }
-   // what the neighbours computed for this rank's rows: the received rows in the extended coarse numbering, and per local
-   // coarse row the received rows that feed it, in package order
-   std::vector<HYPRE_Int> xj(Rext.j.size());
-   for (size_t k = 0; k < Rext.j.size(); k++)
-   {
-      const HYPRE_BigInt g = Rext.j[k];
-      xj[k] = (g < first_c || g > last_c) ? ncP + bsearch_big(cmapRAP.data(), g, ncoRAP) : (HYPRE_Int) (g - first_c);
-   }
-   std::vector<HYPRE_Int> Fi((size_t) ncRT + 1, 0), Fj((size_t) std::max(nsendRT, 1));
-   for (HYPRE_Int s = 0; s < nsendRT; s++) { Fi[(size_t) pkgRT->send_map_elmts[s] + 1]++; }
-   for (HYPRE_Int ic = 0; ic < ncRT; ic++) { Fi[(size_t) ic + 1] += Fi[(size_t) ic]; }
-   int max_seed = 0;
-   {
-      std::vector<HYPRE_Int> pos(Fi.begin(), Fi.end() - 1), seed((size_t) std::max(ncRT, 1), 0);
-      for (HYPRE_Int s = 0; s < nsendRT; s++)
-      {
-         const HYPRE_Int ic = pkgRT->send_map_elmts[s];
-         Fj[(size_t) pos[(size_t) ic]++] = s;
-         seed[(size_t) ic] += Rext.i[(size_t) s + 1] - Rext.i[(size_t) s];
-         max_seed = std::max(max_seed, (int) seed[(size_t) ic]);
-      }
-   }
-   int *Cdi = nullptr, *Cdj = nullptr, *Coi = nullptr, *Coj = nullptr, cdnnz = 0, connz = 0;
-   double *Cda = nullptr, *Coa = nullptr;
+   // ---- column map of the off-rank block of the product; what the neighbours computed for this rank's rows: the received
+   // rows in the extended coarse numbering, and per local coarse row the received rows that feed it, in package order
+   const RapExt Rx = number_received_rows(Rext, Pe, first_c, ncP, ncRT, pkgRT->send_map_elmts, nsendRT);
+   const HYPRE_Int ncoRAP = Rx.ncols_offd();
+   DevCSRBlock Cd, Co;
    bool ok;
    {
-      DevCSR X;
-      X.put(Rext.i, xj, &Rext.a);
-      int *dFi = upload(Fi.data(), Fi.size()), *dFj = upload(Fj.data(), (size_t) nsendRT);
-      int *d_map = upload(mapPext2RAP.data(), (size_t) ncoPext);
-      launch_renumber(Xj, (size_t) xnnz, ncP, d_map, st);            // P_ext's numbering of the ghost coarse points -> the product's
-      ok = device_rap_dist(false, ncRT, ncRT == ncP ? 1 : 0, ncP + ncoRAP, maxP, max_seed, Rd->i, Rd->j, Rd->data,
-                           dD->i, dD->j, dD->data, ncoA ? dO->i : nullptr, dO->j, dO->data, n, n, Xi, Xj, Xa,
-                           nsendRT ? dFi : nullptr, dFj, X.i, X.j, X.a, ncP, &Cdi, &Cdj, &Cda, &cdnnz, &Coi, &Coj, &Coa, &connz, st);
-      dfree(dFi); dfree(dFj); dfree(d_map);
+      DevCSRBlock Xr = upload_csr(Rext.i, Rx.xj, &Rext.a);
+      DevBuf<int> dFi = upload(Rx.Fi.data(), Rx.Fi.size()), dFj = upload(Rx.Fj.data(), (size_t) nsendRT);
+      DevBuf<int> d_map = upload(Rx.mapPext2RAP.data(), (size_t) ncoPext);
+      launch_renumber(X.j, (size_t) X.nnz, ncP, d_map, st);          // P_ext's numbering of the ghost coarse points -> the product's
+      ok = device_rap_dist(false, ncRT, ncRT == ncP ? 1 : 0, ncP + ncoRAP, maxP, Rx.max_seed, Rd->i, Rd->j, Rd->data,
+                           dD->i, dD->j, dD->data, ncoA ? dO->i : nullptr, dO->j, dO->data, n, n, X.i, X.j, X.a,
+                           nsendRT ? dFi.p : nullptr, dFj, Xr.i, Xr.j, Xr.a, ncP, &Cd.i.p, &Cd.j.p, &Cd.a.p, &Cd.nnz, &Co.i.p, &Co.j.p, &Co.a.p, &Co.nnz, st);
    }
-   if (ok && test_declines(comm, 3)) { dfree(Cdi); dfree(Cdj); dfree(Cda); dfree(Coi); dfree(Coj); dfree(Coa); ok = false; }
-   if (!all_ranks_agree(comm, ok))
-   {
-      if (ok) { dfree(Cdi); dfree(Cdj); dfree(Cda); dfree(Coi); dfree(Coj); dfree(Coa); }
-      return give_up();
-   }
-   dfree(Xi); dfree(Xj); dfree(Xa);
+   if (ok && test_declines(comm, 3)) { ok = false; }
+   if (!all_ranks_agree(comm, ok)) { return hypre_error_flag; }
    hypre_ParCSRMatrix *C = hypre_ParCSRMatrixCreate(comm, RT->global_num_cols, P->global_num_cols, RT->col_starts,
-                                                    P->col_starts, ncoRAP, cdnnz, connz);
-   hypre_CSRMatrixDestroy(C->diag); hypre_CSRMatrixDestroy(C->offd);
-   C->diag = setup_wrap_device_csr(ncRT, ncP, cdnnz, Cdi, Cdj, Cda);
-   C->offd = setup_wrap_device_csr(ncRT, ncoRAP, connz, Coi, Coj, Coa);
-   if (ncoRAP)
-   {
-      C->col_map_offd = hypre_TAlloc(HYPRE_BigInt, ncoRAP, HYPRE_MEMORY_HOST);
-      memcpy(C->col_map_offd, cmapRAP.data(), sizeof(HYPRE_BigInt) * (size_t) ncoRAP);
-   }
-   if (keepTranspose) { RT->diagT = Rd; RT->offdT = Ro; }
-   else { hypre_CSRMatrixDestroy(Rd); if (Ro) { hypre_CSRMatrixDestroy(Ro); } }
+                                                    P->col_starts, ncoRAP, Cd.nnz, Co.nnz);
+   adopt_device_blocks(C, Cd, &Co);
+   set_col_map_offd(C, Rx.cmap);
+   if (keepTranspose) { RT->diagT = Rd.release(); RT->offdT = Ro.release(); }
    hypre_CSRMatrixSetRownnz(C->offd);
    hypre_ParCSRMatrixSetNumNonzeros(C);
    hypre_ParCSRMatrixSetDNumNonzeros(C);

@@ -52,6 +52,61 @@ def _blocks(B, m):
     return out
 
 
+def hierarchy_digests(L, B, s):
+    """One sha256 per level of this rank's share of a set-up hierarchy: A_l and P_l (both blocks' i / j / data and column
+    counts, the ghost column map), the C/F marker and the smoother diagonal.  Pins the setup array for array."""
+    import hashlib
+    nl = L.hypre_amd_BoomerAMGGetNumLevels(s)
+    out = []
+    for l in range(nl):
+        h = hashlib.sha256()
+
+        def put(tag, arrays):
+            for k, a in enumerate(arrays):
+                h.update(("%s.%d:%s:%d;" % (tag, k, a.dtype.str, a.size)).encode())
+                h.update(np.ascontiguousarray(a).tobytes())
+
+        mats = [("A", L.hypre_amd_BoomerAMGGetA(s, l))] + ([("P", L.hypre_amd_BoomerAMGGetP(s, l))] if l < nl - 1 else [])
+        for tag, ptr in mats:
+            m = C.cast(ptr, C.POINTER(B.ParCSRMatrix)).contents
+            nco = m.offd.contents.num_cols
+            put(tag, list(B.csr_to_arrays(m.diag)) + list(B.csr_to_arrays(m.offd))
+                + [np.array([m.diag.contents.num_cols, nco], dtype=np.int64),
+                   np.array([m.col_map_offd[k] for k in range(nco)], dtype=np.int64)])
+        cfp = L.hypre_amd_BoomerAMGGetCFMarker(s, l)
+        if cfp:
+            ia = C.cast(cfp, C.POINTER(B.IntArray)).contents
+            put("cf", [B.fetch(ia.data, ia.size, np.int32, ia.memory_location)])
+        lp = L.hypre_amd_BoomerAMGGetL1Norms(s, l)
+        if lp:
+            v = C.cast(lp, C.POINTER(B.Vector)).contents
+            put("l1", [B.fetch(v.data, v.size, np.float64, v.memory_location)])
+        out.append(h.hexdigest())
+    return out
+
+
+def new_nodes_in_P(L, B, s, dist, world):
+    """How many ghost columns of this rank's interpolation operators, over all levels, are coarse points that are NOT
+    ghost columns of A_l: the new off-rank nodes of extended+i interpolation (ghosts of ghosts), which travel through the
+    extra comm package.  Collective: every rank calls it."""
+    count = 0
+    for l in range(L.hypre_amd_BoomerAMGGetNumLevels(s) - 1):
+        Al = C.cast(L.hypre_amd_BoomerAMGGetA(s, l), C.POINTER(B.ParCSRMatrix)).contents
+        Pl = C.cast(L.hypre_amd_BoomerAMGGetP(s, l), C.POINTER(B.ParCSRMatrix)).contents
+        ia = C.cast(L.hypre_amd_BoomerAMGGetCFMarker(s, l), C.POINTER(B.IntArray)).contents
+        cf = B.fetch(ia.data, ia.size, np.int32, ia.memory_location)
+        info = [None] * world
+        dist.all_gather_object(info, (int(Al.first_row_index), cf, int(Pl.first_col_diag)))
+        known = set()
+        for k in range(Al.offd.contents.num_cols):
+            g = int(Al.col_map_offd[k])
+            for first, cfr, first_c in info:
+                if first <= g < first + len(cfr) and cfr[g - first] >= 0:
+                    known.add(first_c + int(np.count_nonzero(cfr[:g - first] >= 0)))
+        count += sum(1 for k in range(Pl.offd.contents.num_cols) if int(Pl.col_map_offd[k]) not in known)
+    return count
+
+
 def compare_setup(case, L, B, ij, O, dist, comm, rank, world):
     """HYPRE_BoomerAMGSetup twice on the same distributed problem, hierarchy in device memory: the distributed levels worked
     on by the host routines (OpenMP loops) and by the device kernels.  Every array of every level of this rank's share must
@@ -231,6 +286,8 @@ def run_case(case, L, B, ij, O, dist, comm, rank, world):
     # this rank's rows of the coarsest level (its slice of the right-hand side the dense solve gathers)
     Ac = C.cast(L.hypre_amd_BoomerAMGGetA(s, L.hypre_amd_BoomerAMGGetNumLevels(s) - 1), C.POINTER(B.ParCSRMatrix)).contents
     mine.update(coarse_rows=int(Ac.diag.contents.num_rows))
+    if case.get("digest"):
+        mine.update(digest=hierarchy_digests(L, B, s), new_nodes=new_nodes_in_P(L, B, s, dist, world))
     if device:
         # the product path: distributed solve on the GPU (two ranks may share one card in the
         # test; halo traffic goes through the callback communicator, staged over the host)
@@ -377,6 +434,8 @@ def run_case(case, L, B, ij, O, dist, comm, rank, world):
                        matvecT_err=float(np.max(np.abs(zd - zr)) / np.max(np.abs(zr))),
                        dot_err=float(abs(parts[0]["dev_dot"] - float(np.dot(xt, yr))) / abs(float(np.dot(xt, yr)))),
                        x_err=float(np.max(np.abs(xd - xg)) / np.max(np.abs(xg))))
+        if case.get("digest"):
+            out.update(digest=[p["digest"] for p in parts], new_nodes=[p["new_nodes"] for p in parts])
         if "name" in case:
             out["name"] = case["name"]
         print("RESULT " + json.dumps(out), flush=True)
