@@ -429,9 +429,10 @@ bool device_l1_norms(int n, const int *Ai, const int *Aj, const double *Aa, int 
 bool device_rap(int nc, int ncP, int maxP, const int *Ri, const int *Rj, const double *Ra, const int *Ai, const int *Aj,
                 const double *Aa, const int *Pi, const int *Pj, const double *Pa, int **Ci_out, int **Cj_out, double **Ca_out,
                 int *nnz_out, hipStream_t s);
-// extended+i interpolation rows on the device, bit-identical to the host setup's (interp_kernels.hip); false: use the host
+// extended+i (interp_type 6), extended (14) or extended+i-if-no-common-C (7) interpolation rows on the device, bit-identical
+// to the host setup's (interp_kernels.hip); false: use the host
 bool device_extpi(int n, const int *Ai, const int *Aj, const double *Aa, const int *Si, const int *Sj, const int *CF,
-                  const int *f2c, double trunc_tol, int max_elmts, int first_rung, int **Pi_out, int **Pj_out, double **Pa_out,
+                  const int *f2c, double trunc_tol, int max_elmts, int first_rung, int interp_type, int **Pi_out, int **Pj_out, double **Pa_out,
                   int *nnz_out, hipStream_t s, int split = -1, int **Oi_out = nullptr, int **Oj_out = nullptr,
                   double **Oa_out = nullptr, int *onnz_out = nullptr);
 // ---- distributed levels on the device (dist_setup_kernels.hip, setup_kernels.hip, rap_kernels.hip): the single-rank kernels

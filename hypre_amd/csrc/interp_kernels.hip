@@ -1,8 +1,9 @@
-// hypre_amd — extended+i interpolation on the device (single rank, scalar problems), bit-identical to the host setup.
+// hypre_amd — extended+i interpolation and its two relatives (extended, extended+i "if no common C point") on the device
+// (scalar problems), bit-identical to the host setup.
 //
-// Reference: parcsr_ls/par_lr_interp.c:1024-1700 (hypre_BoomerAMGBuildExtPIInterpHost) and the truncation of
-// parcsr_mv/par_csr_matrix.c:2874-3400; restated for the host in par_amg_setup.cpp (hypre_BoomerAMGBuildExtPIInterp,
-// hypre_BoomerAMGInterpTruncation), whose loop order — the order in which a row's interpolatory set is discovered, the
+// Reference: parcsr_ls/par_lr_interp.c:1024-1700 (hypre_BoomerAMGBuildExtPIInterpHost), :4777-5520 (..BuildExtInterpHost),
+// :1931-2920 (..BuildExtPICCInterp) and the truncation of parcsr_mv/par_csr_matrix.c:2874-3400; restated for the host in
+// par_amg_setup.cpp (build_ext_family_interp, hypre_BoomerAMGInterpTruncation), whose loop order — the order in which a row's interpolatory set is discovered, the
 // order of every sum, the quicksort that picks the entries a truncated row keeps, ties included — this kernel follows
 // statement for statement, because the hierarchies the reference's regression files pin depend on those bits.
 // The reference's own device routine: parcsr_ls/par_lr_interp_device.c:1001 (a different formulation of the same weights).
@@ -80,7 +81,10 @@ __device__ void qsort2_abs_dev(int *v, double *w, int n, int keep, int *stack)
 
 // MODE 0: row lengths only (no truncation by count is possible then: max_elmts == 0, tol == 0 handled by the caller);
 // MODE 1: write rows at out_off[i] (exact offsets) ; MODE 2: write rows at i * stride and their lengths to rowlen.
-template <int MODE>
+// TYPE: the interp_type.  6: extended+i.  14: extended — the same set, no "+i" term in the sum over an F neighbour's row and
+// no share of it for the diagonal.  7: extended+i if no common C point — the row's strong C neighbours enter the set first
+// (positions below ndirect), and an F neighbour's C points are appended only if none of them sits at such a position.
+template <int MODE, int TYPE>
 __global__ __launch_bounds__(64)
 void extpi_rows_kernel(int n, const int *__restrict__ Ai, const int *__restrict__ Aj, const double *__restrict__ Aa,
                        const int *__restrict__ Si, const int *__restrict__ Sj, const int *__restrict__ CF,
@@ -133,6 +137,28 @@ void extpi_rows_kernel(int n, const int *__restrict__ Ai, const int *__restrict_
          // every strong F neighbour becomes an entry of the map, beside the set's (at most capR): the probes end only
          // while a slot stays free (extpi_map.hpp), so a row that could fill the map is left to the next rung
          bad = !extpi_map_has_room(s1 - s0, capR, capM);
+         int ndirect = 0;
+         if constexpr (TYPE == 7)
+         {
+            // the columns of a row of S are distinct: every strong C neighbour is new, a batch is appended side by side
+            for (int sb = s0; sb < s1 && !bad; sb += 64)
+            {
+               const int jj = sb + lane;
+               const int i1 = jj < s1 ? Sj[jj] : 0;
+               const int fc = jj < s1 ? f2c[i1] : -1;
+               const unsigned long long ball = __ballot(fc >= 0);
+               if (len + __popcll(ball) > capR) { bad = true; break; }
+               if (fc >= 0)
+               {
+                  const int p = len + below(ball, lane);
+                  map_set(Mkey, Mval, mask, tag, i1, p);
+                  pj[p] = fc; pa[p] = 0.0;
+               }
+               len += __popcll(ball);
+               __syncthreads();
+            }
+            ndirect = len;
+         }
          for (int sb = s0; sb < s1 && !bad; sb += 64)
          {
             const int jj = sb + lane;
@@ -154,7 +180,7 @@ void extpi_rows_kernel(int n, const int *__restrict__ Ai, const int *__restrict_
                const int ci1 = s_i1[sl], ccf = s_cf[sl];
                if (ccf >= 0)
                {
-                  const int m = map_get(Mkey, Mval, mask, tag, ci1);
+                  const int m = TYPE == 7 ? 0 : map_get(Mkey, Mval, mask, tag, ci1);      // type 7: entered by the first pass
                   if (m < 0)
                   {
                      if (len + 1 > capR) { bad = true; break; }
@@ -168,31 +194,44 @@ void extpi_rows_kernel(int n, const int *__restrict__ Ai, const int *__restrict_
                   if (lane == 0) { map_set(Mkey, Mval, mask, tag, ci1, STRONG_F); }
                   __syncthreads();
                   const int e0 = sl ? sincl[sl - 1] : 0, e1 = sincl[sl];
-                  for (int c = e0 >> 6; (c << 6) < e1; c++)
+                  // type 7 walks the neighbour's entries twice: pass 0 only asks whether one of them is a strong C neighbour of
+                  // the row (a map position below ndirect; nothing is written), pass 1 — the only one of the other types —
+                  // appends the new C points, unless pass 0 found a common one
+                  bool common = false;
+                  for (int pass = TYPE == 7 ? 0 : 1; pass < 2 && !common && !bad; pass++)
                   {
-                     const int t = (c << 6) + lane;
-                     if (c != loaded)
+                     for (int c = e0 >> 6; (c << 6) < e1; c++)
                      {
-                        const bool have = t < total;
-                        const int src = have ? owner_of(sincl, t) : 0;
-                        const int kk = have ? sbeg[src] + (t - (src ? sincl[src - 1] : 0)) : 0;
-                        k1 = have ? Sj[kk] : 0;
-                        fck = have ? f2c[k1] : -1;           // the coarse number says it all: -1 for every point that is not C
-                        isc = fck >= 0;
-                        loaded = c;
+                        const int t = (c << 6) + lane;
+                        if (c != loaded)
+                        {
+                           const bool have = t < total;
+                           const int src = have ? owner_of(sincl, t) : 0;
+                           const int kk = have ? sbeg[src] + (t - (src ? sincl[src - 1] : 0)) : 0;
+                           k1 = have ? Sj[kk] : 0;
+                           fck = have ? f2c[k1] : -1;           // the coarse number says it all: -1 for every point that is not C
+                           isc = fck >= 0;
+                           loaded = c;
+                        }
+                        const bool mine = t >= e0 && t < e1;
+                        const int m = (mine && isc) ? map_get(Mkey, Mval, mask, tag, k1) : 0;
+                        if (TYPE == 7 && pass == 0)
+                        {
+                           if (__ballot(mine && isc && m >= 0 && m < ndirect)) { common = true; break; }
+                           continue;
+                        }
+                        const bool fresh = mine && isc && m < 0;
+                        const unsigned long long ball = __ballot(fresh);
+                        if (len + __popcll(ball) > capR) { bad = true; break; }
+                        if (fresh)
+                        {
+                           const int p = len + below(ball, lane);
+                           map_set(Mkey, Mval, mask, tag, k1, p);
+                           pj[p] = fck; pa[p] = 0.0;
+                        }
+                        len += __popcll(ball);
+                        __syncthreads();
                      }
-                     const bool mine = t >= e0 && t < e1;
-                     const bool fresh = mine && isc && map_get(Mkey, Mval, mask, tag, k1) < 0;
-                     const unsigned long long ball = __ballot(fresh);
-                     if (len + __popcll(ball) > capR) { bad = true; break; }
-                     if (fresh)
-                     {
-                        const int p = len + below(ball, lane);
-                        map_set(Mkey, Mval, mask, tag, k1, p);
-                        pj[p] = fck; pa[p] = 0.0;
-                     }
-                     len += __popcll(ball);
-                     __syncthreads();
                   }
                }
             }
@@ -253,7 +292,7 @@ void extpi_rows_kernel(int n, const int *__restrict__ Ai, const int *__restrict_
                         if (c == (e0 >> 6)) { sgn = lane_value(v, e0 & 63) < 0 ? -1 : 1; }
                         const int t = (c << 6) + lane;
                         const bool mine = t > e0 && t < e1;
-                        const bool take = mine && (sgn * v) < 0 && (i2 == i || map_get(Mkey, Mval, mask, tag, i2) >= 0);
+                        const bool take = mine && (sgn * v) < 0 && ((TYPE != 14 && i2 == i) || map_get(Mkey, Mval, mask, tag, i2) >= 0);
                         unsigned long long ball = __ballot(take);
                         while (ball)
                         {
@@ -273,9 +312,12 @@ void extpi_rows_kernel(int n, const int *__restrict__ Ai, const int *__restrict_
                            const bool neg = mine && (sgn * v) < 0;
                            const int m2 = neg ? map_get(Mkey, Mval, mask, tag, i2) : ABSENT;
                            if (m2 >= 0) { pa[m2] += distribute * v; }
-                           // at most one entry of the row is i itself
-                           const unsigned long long self = __ballot(neg && i2 == i);
-                           if (self) { diagonal += distribute * lane_value(v, __ffsll((long long) self) - 1); }
+                           if (TYPE != 14)
+                           {
+                              // at most one entry of the row is i itself
+                              const unsigned long long self = __ballot(neg && i2 == i);
+                              if (self) { diagonal += distribute * lane_value(v, __ffsll((long long) self) - 1); }
+                           }
                         }
                         __syncthreads();
                      }
@@ -384,6 +426,14 @@ __global__ void compact_rows_kernel(int n, int stride, const int *__restrict__ P
    if (i < n && k < Pi[i + 1] - Pi[i]) { Pj[Pi[i] + k] = sj[t]; Pa[Pi[i] + k] = sa[t]; }
 }
 
+// the kernel of one MODE for the interp_type (device_extpi admits 6, 7 and 14 only)
+template <int MODE, class F> void with_rows_kernel(int interp_type, F f)
+{
+   if (interp_type == 14) { f(extpi_rows_kernel<MODE, 14>); }
+   else if (interp_type == 7) { f(extpi_rows_kernel<MODE, 7>); }
+   else { f(extpi_rows_kernel<MODE, 6>); }
+}
+
 // How the last device_extpi call went (hypre_amd_GetDeviceInterpPath) and the test switch for the number of waves
 // (hypre_amd_SetDeviceInterpWaves; 0: one per row up to 32 a CU): tests walk the ladder and make one wave own many rows
 enum { INTERP_NOT_DECLINED = 0, INTERP_THRESHOLD_ONLY = 1, INTERP_TABLES_EXHAUSTED = 2, INTERP_ALLOCATION = 3 };
@@ -401,9 +451,10 @@ void device_split_strided(int n, int stride, int *len, int *nd, const int *sj, c
 // cover the ghost points as well, coarse numbers >= split are off-rank; the operator comes back as two blocks
 // (Pi/Pj/Pa: columns < split; Oi/Oj/Oa: the others, minus split).
 bool device_extpi(int n, const int *Ai, const int *Aj, const double *Aa, const int *Si, const int *Sj, const int *CF,
-                  const int *f2c, double trunc_tol, int max_elmts, int first_rung, int **Pi_out, int **Pj_out, double **Pa_out,
-                  int *nnz_out, hipStream_t s, int split, int **Oi_out, int **Oj_out, double **Oa_out, int *onnz_out)
+                  const int *f2c, double trunc_tol, int max_elmts, int first_rung, int interp_type, int **Pi_out, int **Pj_out,
+                  double **Pa_out, int *nnz_out, hipStream_t s, int split, int **Oi_out, int **Oj_out, double **Oa_out, int *onnz_out)
 {
+   if (interp_type != 6 && interp_type != 7 && interp_type != 14) { hypre_error_w_msg(HYPRE_ERROR_GENERIC, "device_extpi: interp_type must be 6, 7 or 14"); return false; }
    const bool dist = split >= 0;
    const bool fixed = max_elmts > 0 || dist;
    InterpPath &path = g_interp_path;
@@ -421,9 +472,10 @@ bool device_extpi(int n, const int *Ai, const int *Aj, const double *Aa, const i
    }
    auto lds = [](int capM, int capR) { return (size_t) 8 * capM + 8 * capR + 8 * 64 + 4 * capM + 4 * capR + 4 * (4 * capR + 8) + 4 * 64 * 5 + 64; };
    const size_t budget = 150 * 1024;
-   (void) hipFuncSetAttribute((const void *) extpi_rows_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) budget);
-   (void) hipFuncSetAttribute((const void *) extpi_rows_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) budget);
-   (void) hipFuncSetAttribute((const void *) extpi_rows_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) budget);
+   auto allow_lds = [&](auto *k) { (void) hipFuncSetAttribute((const void *) k, hipFuncAttributeMaxDynamicSharedMemorySize, (int) budget); };
+   with_rows_kernel<0>(interp_type, allow_lds);
+   with_rows_kernel<1>(interp_type, allow_lds);
+   with_rows_kernel<2>(interp_type, allow_lds);
    int *d_flag = nullptr, *rowlen = nullptr, *rowlen_d = nullptr;
    HIP_CHECK(hipMalloc((void **) &d_flag, sizeof(int)));
    HIP_CHECK(hipMalloc((void **) &rowlen, sizeof(int) * ((size_t) n + 1)));
@@ -472,13 +524,19 @@ bool device_extpi(int n, const int *Ai, const int *Aj, const double *Aa, const i
       if (fixed)
       {
          if (max_elmts <= 0 && !alloc_strided(capR)) { return give_up(INTERP_ALLOCATION); }
-         hipLaunchKernelGGL((extpi_rows_kernel<2>), dim3(waves), dim3(64), lds(capM, capR), s, n, Ai, Aj, Aa, Si, Sj, CF, f2c, trunc_tol,
-                            max_elmts, capM, capR, (const int *) nullptr, stride, rowlen, sj, sa, d_flag, split, rowlen_d);
+         with_rows_kernel<2>(interp_type, [&](auto *k)
+         {
+            hipLaunchKernelGGL(k, dim3(waves), dim3(64), lds(capM, capR), s, n, Ai, Aj, Aa, Si, Sj, CF, f2c, trunc_tol,
+                               max_elmts, capM, capR, (const int *) nullptr, stride, rowlen, sj, sa, d_flag, split, rowlen_d);
+         });
       }
       else
       {
-         hipLaunchKernelGGL((extpi_rows_kernel<0>), dim3(waves), dim3(64), lds(capM, capR), s, n, Ai, Aj, Aa, Si, Sj, CF, f2c, trunc_tol,
-                            max_elmts, capM, capR, (const int *) nullptr, 0, rowlen, (int *) nullptr, (double *) nullptr, d_flag, -1, (int *) nullptr);
+         with_rows_kernel<0>(interp_type, [&](auto *k)
+         {
+            hipLaunchKernelGGL(k, dim3(waves), dim3(64), lds(capM, capR), s, n, Ai, Aj, Aa, Si, Sj, CF, f2c, trunc_tol,
+                               max_elmts, capM, capR, (const int *) nullptr, 0, rowlen, (int *) nullptr, (double *) nullptr, d_flag, -1, (int *) nullptr);
+         });
       }
       HIP_CHECK(hipMemcpyAsync(&h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));
@@ -510,8 +568,11 @@ bool device_extpi(int n, const int *Ai, const int *Aj, const double *Aa, const i
    else
    {
       HIP_CHECK(hipMemsetAsync(d_flag, 0, sizeof(int), s));
-      hipLaunchKernelGGL((extpi_rows_kernel<1>), dim3(waves), dim3(64), lds(capM, capR), s, n, Ai, Aj, Aa, Si, Sj, CF, f2c, trunc_tol,
-                         max_elmts, capM, capR, Pi, 0, (int *) nullptr, Pj, Pa, d_flag, -1, (int *) nullptr);
+      with_rows_kernel<1>(interp_type, [&](auto *k)
+      {
+         hipLaunchKernelGGL(k, dim3(waves), dim3(64), lds(capM, capR), s, n, Ai, Aj, Aa, Si, Sj, CF, f2c, trunc_tol,
+                            max_elmts, capM, capR, Pi, 0, (int *) nullptr, Pj, Pa, d_flag, -1, (int *) nullptr);
+      });
    }
    HIP_CHECK(hipStreamSynchronize(s));
    HIP_CHECK(hipFree(d_flag));
@@ -523,7 +584,7 @@ bool device_extpi(int n, const int *Ai, const int *Aj, const double *Aa, const i
 
 // The code object of this file is loaded when one of its kernels is first asked for: ensure_device() asks here, so that
 // the load (tens of milliseconds per file) is part of bringing the device up, not of the first setup or solve.
-void preload_interp_kernels() { hipFuncAttributes at; (void) hipFuncGetAttributes(&at, (const void *) extpi_rows_kernel<2>); (void) hipGetLastError(); }
+void preload_interp_kernels() { hipFuncAttributes at; (void) hipFuncGetAttributes(&at, (const void *) extpi_rows_kernel<2, 6>); (void) hipGetLastError(); }
 
 }  // namespace hamd
 

@@ -981,23 +981,34 @@ HYPRE_Int hypre_BoomerAMGInterpTruncation(hypre_ParCSRMatrix *P, HYPRE_Real tol,
 }
 
 // ===========================================================================
-// extended+i interpolation (par_lr_interp.c:1024-1700), single-rank form.
+// The long-range interpolations of the extended family, single-rank form: one walk, the type an argument.
+//   6  extended+i (par_lr_interp.c:1024-1700)
+//   14 extended (par_lr_interp.c:4777-5520)
+//   7  extended+i "if no common C point" (par_lr_interp.c:1931-2920)
 // For an F-point i the interpolatory set C^_i is: strong C neighbours of i and
-// strong C neighbours of i's strong F neighbours (distance two).  Weights:
-//   w_ij = -( a_ij + sum_{k in F_i^s} a_ik a^-_kj / sum_{l in C^_i u {i}} a^-_kl ) / a~_ii
-// with a~_ii = a_ii + weak couplings + the "+i" share of every distributed F neighbour.
+// strong C neighbours of i's strong F neighbours (distance two); type 7 takes the second kind only from an F
+// neighbour that shares no strong C neighbour with i, after all of the first kind (two passes).  Weights:
+//   w_ij = -( a_ij + sum_{k in F_i^s} a_ik a^-_kj / sum_{l in D} a^-_kl ) / a~_ii
+// with D = C^_i u {i} and a~_ii = a_ii + weak couplings + the "+i" share of every distributed F neighbour for types
+// 6 and 7; D = C^_i and no such share for type 14.
 // ===========================================================================
-HYPRE_Int hypre_BoomerAMGBuildExtPIInterp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, hypre_ParCSRMatrix *S,
-                                          HYPRE_BigInt *num_cpts_global, HYPRE_Int num_functions,
-                                          HYPRE_Int *dof_func, HYPRE_Int debug_flag, HYPRE_Real trunc_factor,
-                                          HYPRE_Int max_elmts, hypre_ParCSRMatrix **P_ptr)
+static HYPRE_Int build_ext_family_interp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, hypre_ParCSRMatrix *S,
+                                         HYPRE_BigInt *num_cpts_global, HYPRE_Int num_functions,
+                                         HYPRE_Int *dof_func, HYPRE_Real trunc_factor,
+                                         HYPRE_Int max_elmts, HYPRE_Int interp_type, hypre_ParCSRMatrix **P_ptr)
 {
-   (void) debug_flag;
+   if (num_functions > 1 && interp_type != 6)
+   {
+      hypre_error_w_msg(HYPRE_ERROR_GENERIC, interp_type == 14 ? "hypre_BoomerAMGBuildExtInterp: systems (num_functions > 1) are supported with interp_type 6 only"
+                                                               : "hypre_BoomerAMGBuildExtPICCInterp: systems (num_functions > 1) are supported with interp_type 6 only");
+      return hypre_error_flag;
+   }
    if (num_functions > 1 && !dof_func)
    {
       hypre_error_w_msg(HYPRE_ERROR_GENERIC, "hypre_BoomerAMGBuildExtPIInterp: num_functions > 1 needs the function of every row");
       return hypre_error_flag;
    }
+   const bool plus_i = interp_type != 14, common_c = interp_type == 7;
    const bool sys = num_functions > 1;
    MPI_Comm comm = A->comm;
    if (comm_size(comm) > 1)
@@ -1010,11 +1021,11 @@ HYPRE_Int hypre_BoomerAMGBuildExtPIInterp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_m
       {
          // P_ptr comes back empty (error flag clear) when some rank's rows did not fit the kernel's tables: the caller
          // repeats the level's interpolation with the host routine
-         dist_device_extpi_interp(A, CF_marker, S, num_cpts_global, ends.back(), trunc_factor, max_elmts, g_device_interp_on - 1, P_ptr);
+         dist_device_extpi_interp(A, CF_marker, S, num_cpts_global, ends.back(), trunc_factor, max_elmts, g_device_interp_on - 1, interp_type, P_ptr);
          if (*P_ptr) { g_device_interp_count++; }
          return hypre_error_flag;
       }
-      return dist_build_extpi_interp(A, CF_marker, S, num_cpts_global, ends.back(), sys ? dof_func : nullptr, trunc_factor, max_elmts, P_ptr);
+      return dist_build_extpi_interp(A, CF_marker, S, num_cpts_global, ends.back(), sys ? dof_func : nullptr, trunc_factor, max_elmts, interp_type, P_ptr);
    }
    hypre_CSRMatrix *Ad = A->diag;
    const HYPRE_Int n = Ad->num_rows;
@@ -1033,7 +1044,7 @@ HYPRE_Int hypre_BoomerAMGBuildExtPIInterp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_m
       HYPRE_Int *dF2C = hypre_TAlloc(HYPRE_Int, (size_t) n, HYPRE_MEMORY_DEVICE);
       device_coarse_numbering(n, dCF, dF2C, st);
       DevCSRBlock Pb;
-      const bool ok = device_extpi(n, dA->i, dA->j, dA->data, dS->i, dS->j, dCF, dF2C, trunc_factor, max_elmts, g_device_interp_on - 1, &Pb.i.p, &Pb.j.p, &Pb.a.p, &Pb.nnz, st);
+      const bool ok = device_extpi(n, dA->i, dA->j, dA->data, dS->i, dS->j, dCF, dF2C, trunc_factor, max_elmts, g_device_interp_on - 1, interp_type, &Pb.i.p, &Pb.j.p, &Pb.a.p, &Pb.nnz, st);
       if (!S_there) { hypre_CSRMatrixDestroy(dS); }
       hypre_Free(dF2C, HYPRE_MEMORY_DEVICE);
       if (ok)
@@ -1095,6 +1106,16 @@ HYPRE_Int hypre_BoomerAMGBuildExtPIInterp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_m
          else if (CF_marker[i] != -3)
          {
             strong_f--;
+            // type 7: the strong C neighbours first; they then sit at the positions below `direct`
+            if (common_c)
+            {
+               for (HYPRE_Int jj = Si[i]; jj < Si[i + 1]; jj++)
+               {
+                  const HYPRE_Int i1 = Sj[jj];
+                  if (CF_marker[i1] >= 0 && marker.get(i1) < begin) { marker.set(i1, (long long) pj.size()); pj.push_back(f2c[(size_t) i1]); pa.push_back(0.0); }
+               }
+            }
+            const long long direct = (long long) pj.size();
             for (HYPRE_Int jj = Si[i]; jj < Si[i + 1]; jj++)
             {
                const HYPRE_Int i1 = Sj[jj];
@@ -1105,7 +1126,13 @@ HYPRE_Int hypre_BoomerAMGBuildExtPIInterp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_m
                else if (CF_marker[i1] != -3)
                {
                   marker.set(i1, strong_f);
-                  for (HYPRE_Int kk = Si[i1]; kk < Si[i1 + 1]; kk++)
+                  bool extends = true;
+                  for (HYPRE_Int kk = Si[i1]; kk < Si[i1 + 1] && common_c && extends; kk++)
+                  {
+                     const long long m = marker.get(Sj[kk]);
+                     extends = !(m >= begin && m < direct);
+                  }
+                  for (HYPRE_Int kk = Si[i1]; kk < Si[i1 + 1] && extends; kk++)
                   {
                      const HYPRE_Int k1 = Sj[kk];
                      if (CF_marker[k1] >= 0 && marker.get(k1) < begin)
@@ -1127,7 +1154,7 @@ HYPRE_Int hypre_BoomerAMGBuildExtPIInterp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_m
                   for (HYPRE_Int j1 = Ai[i1] + 1; j1 < Ai[i1 + 1]; j1++)
                   {
                      const HYPRE_Int i2 = Aj[j1];
-                     if ((marker.get(i2) >= begin || i2 == i) && (sgn * Aa[j1]) < 0) { sum += Aa[j1]; }
+                     if ((marker.get(i2) >= begin || (plus_i && i2 == i)) && (sgn * Aa[j1]) < 0) { sum += Aa[j1]; }
                   }
                   if (sum != 0)
                   {
@@ -1136,7 +1163,7 @@ HYPRE_Int hypre_BoomerAMGBuildExtPIInterp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_m
                      {
                         const HYPRE_Int i2 = Aj[j1];
                         if (marker.get(i2) >= begin && (sgn * Aa[j1]) < 0) { pa[(size_t) marker.get(i2)] += distribute * Aa[j1]; }
-                        if (i2 == i && (sgn * Aa[j1]) < 0) { diagonal += distribute * Aa[j1]; }
+                        if (plus_i && i2 == i && (sgn * Aa[j1]) < 0) { diagonal += distribute * Aa[j1]; }
                      }
                   }
                   else { diagonal += Aa[jj]; }
@@ -1160,6 +1187,33 @@ HYPRE_Int hypre_BoomerAMGBuildExtPIInterp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_m
    hypre_CSRMatrixSetRownnz(P->offd);
    *P_ptr = P;
    return hypre_error_flag;
+}
+
+HYPRE_Int hypre_BoomerAMGBuildExtPIInterp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, hypre_ParCSRMatrix *S,
+                                          HYPRE_BigInt *num_cpts_global, HYPRE_Int num_functions,
+                                          HYPRE_Int *dof_func, HYPRE_Int debug_flag, HYPRE_Real trunc_factor,
+                                          HYPRE_Int max_elmts, hypre_ParCSRMatrix **P_ptr)
+{
+   (void) debug_flag;
+   return build_ext_family_interp(A, CF_marker, S, num_cpts_global, num_functions, dof_func, trunc_factor, max_elmts, 6, P_ptr);
+}
+
+HYPRE_Int hypre_BoomerAMGBuildExtInterp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, hypre_ParCSRMatrix *S,
+                                        HYPRE_BigInt *num_cpts_global, HYPRE_Int num_functions,
+                                        HYPRE_Int *dof_func, HYPRE_Int debug_flag, HYPRE_Real trunc_factor,
+                                        HYPRE_Int max_elmts, hypre_ParCSRMatrix **P_ptr)
+{
+   (void) debug_flag;
+   return build_ext_family_interp(A, CF_marker, S, num_cpts_global, num_functions, dof_func, trunc_factor, max_elmts, 14, P_ptr);
+}
+
+HYPRE_Int hypre_BoomerAMGBuildExtPICCInterp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, hypre_ParCSRMatrix *S,
+                                            HYPRE_BigInt *num_cpts_global, HYPRE_Int num_functions,
+                                            HYPRE_Int *dof_func, HYPRE_Int debug_flag, HYPRE_Real trunc_factor,
+                                            HYPRE_Int max_elmts, hypre_ParCSRMatrix **P_ptr)
+{
+   (void) debug_flag;
+   return build_ext_family_interp(A, CF_marker, S, num_cpts_global, num_functions, dof_func, trunc_factor, max_elmts, 7, P_ptr);
 }
 
 // Direct interpolation (par_interp.c hypre_BoomerAMGBuildDirInterpHost, interp_type 3):
@@ -1812,7 +1866,7 @@ HYPRE_Int hypre_BoomerAMGSetup(void *amg_vdata, hypre_ParCSRMatrix *A, hypre_Par
    auto level_runs_on_device = [&](hypre_ParCSRMatrix *M, HYPRE_Int ct)
    {
       if (!(target == HYPRE_MEMORY_DEVICE && g_device_coarsen_on && g_device_interp_on && g_device_rap_on &&
-            d->num_functions <= 1 && (ct == 8 || ct == 9) && d->interp_type == 6)) { return false; }
+            d->num_functions <= 1 && (ct == 8 || ct == 9) && (d->interp_type == 6 || d->interp_type == 7 || d->interp_type == 14))) { return false; }
       if (single_rank)
       {
          return M->offd->num_cols == 0 && M->offd->num_nonzeros == 0 && M->diag->num_rows >= g_device_rap_min_rows && M->diag->num_nonzeros > 0;
@@ -1935,9 +1989,9 @@ HYPRE_Int hypre_BoomerAMGSetup(void *amg_vdata, hypre_ParCSRMatrix *A, hypre_Par
       if (coarse_size < (HYPRE_BigInt) d->min_coarse_size) { drop_level(true); break; }
       const double t_i0 = omp_get_wtime();
       hypre_ParCSRMatrix *P = nullptr;
-      if (d->interp_type == 6)
+      if (d->interp_type == 6 || d->interp_type == 7 || d->interp_type == 14)
       {
-         hypre_BoomerAMGBuildExtPIInterp(Al, CF, S, cpts, d->num_functions, dofs, 0, d->trunc_factor, d->P_max_elmts, &P);
+         build_ext_family_interp(Al, CF, S, cpts, d->num_functions, dofs, d->trunc_factor, d->P_max_elmts, d->interp_type, &P);
          if (!P && !hypre_error_flag)
          {
             // the device kernel declined (a row beyond its tables) and the level lives on the device: host copies, host loop
@@ -1952,7 +2006,7 @@ HYPRE_Int hypre_BoomerAMGSetup(void *amg_vdata, hypre_ParCSRMatrix *A, hypre_Par
                g_level_on_device = false;
                hypre_BoomerAMGCreateS(Al, d->strong_threshold, d->max_row_sum, d->num_functions, dofs, &S);
             }
-            hypre_BoomerAMGBuildExtPIInterp(Al, CF, S, cpts, d->num_functions, dofs, 0, d->trunc_factor, d->P_max_elmts, &P);
+            build_ext_family_interp(Al, CF, S, cpts, d->num_functions, dofs, d->trunc_factor, d->P_max_elmts, d->interp_type, &P);
          }
       }
       else if (d->interp_type == 3)
@@ -1961,7 +2015,7 @@ HYPRE_Int hypre_BoomerAMGSetup(void *amg_vdata, hypre_ParCSRMatrix *A, hypre_Par
       }
       else
       {
-         hypre_error_w_msg(HYPRE_ERROR_GENERIC, "hypre_BoomerAMGSetup: interp_type must be 6 (extended+i) or 3 (direct)");
+         hypre_error_w_msg(HYPRE_ERROR_GENERIC, "hypre_BoomerAMGSetup: interp_type must be 6 (extended+i), 7 (extended+i if no common C point), 14 (extended) or 3 (direct)");
       }
       destroy_with_twins(S);
       if (!P || hypre_error_flag) { break; }

@@ -209,13 +209,15 @@ struct ExtPIGhosts
 namespace hamd {
 
 // ===========================================================================
-// extended+i interpolation, distributed (par_lr_interp.c:1024-1700)
+// extended+i (6), extended (14) and extended+i "if no common C point" (7) interpolation, distributed
+// (par_lr_interp.c:1024-1700, 4777-5520, 1931-2920): one walk, as in build_ext_family_interp (par_amg_setup.cpp)
 // ===========================================================================
 HYPRE_Int dist_build_extpi_interp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, hypre_ParCSRMatrix *S,
                                   HYPRE_BigInt *num_cpts_global, HYPRE_BigInt total_global_cpts,
                                   const HYPRE_Int *dof_func, HYPRE_Real trunc_factor, HYPRE_Int max_elmts,
-                                  hypre_ParCSRMatrix **P_ptr)
+                                  HYPRE_Int interp_type, hypre_ParCSRMatrix **P_ptr)
 {
+   const bool plus_i = interp_type != 14, common_c = interp_type == 7;
    MPI_Comm comm = A->comm;
    if (!A->comm_pkg) { hypre_MatvecCommPkgCreate(A); }
    hypre_ParCSRCommPkg *pkg = A->comm_pkg;
@@ -273,6 +275,23 @@ HYPRE_Int dist_build_extpi_interp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, h
       else if (CF_marker[i] != -3)
       {
          strong_f--;
+         // type 7: the strong C neighbours first, local and off-rank; they then sit at the positions below dd / od
+         if (common_c)
+         {
+            for (HYPRE_Int jj = Sdi[i]; jj < Sdi[i + 1]; jj++)
+            {
+               const HYPRE_Int i1 = Sdj[jj];
+               if (CF_marker[i1] >= 0 && mk[(size_t) i1] < bd) { mk[(size_t) i1] = (long long) pdj.size(); pdj.push_back(f2c[(size_t) i1]); pda.push_back(0.0); }
+            }
+            for (HYPRE_Int jj = Soi[i]; jj < Soi[i + 1]; jj++)
+            {
+               const HYPRE_Int i1 = Soj[jj];
+               if (CF_offd[(size_t) i1] >= 0 && mko[(size_t) i1] < bo) { mko[(size_t) i1] = (long long) poj.size(); poj.push_back(i1); poa.push_back(0.0); }
+            }
+         }
+         const long long dd = (long long) pdj.size(), od = (long long) poj.size();
+         auto direct_d = [&](HYPRE_Int k) { return mk[(size_t) k] >= bd && mk[(size_t) k] < dd; };
+         auto direct_o = [&](HYPRE_Int k) { return mko[(size_t) k] >= bo && mko[(size_t) k] < od; };
          for (HYPRE_Int jj = Sdi[i]; jj < Sdi[i + 1]; jj++)
          {
             const HYPRE_Int i1 = Sdj[jj];
@@ -283,6 +302,10 @@ HYPRE_Int dist_build_extpi_interp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, h
             else if (CF_marker[i1] != -3)
             {
                mk[(size_t) i1] = strong_f;
+               bool shared = false;
+               for (HYPRE_Int kk = Sdi[i1]; kk < Sdi[i1 + 1] && common_c && !shared; kk++) { shared = direct_d(Sdj[kk]); }
+               for (HYPRE_Int kk = Soi[i1]; kk < Soi[i1 + 1] && common_c && !shared; kk++) { shared = direct_o(Soj[kk]); }
+               if (shared) { continue; }
                for (HYPRE_Int kk = Sdi[i1]; kk < Sdi[i1 + 1]; kk++)
                {
                   const HYPRE_Int k1 = Sdj[kk];
@@ -305,6 +328,13 @@ HYPRE_Int dist_build_extpi_interp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, h
             else if (CF_offd[(size_t) i1] != -3)
             {
                mko[(size_t) i1] = strong_f;
+               bool shared = false;
+               for (HYPRE_Int kk = Sop.i[(size_t) i1]; kk < Sop.i[(size_t) i1 + 1] && common_c && !shared; kk++)
+               {
+                  const HYPRE_BigInt g = Sop.j[(size_t) kk];
+                  shared = (g >= col_1 && g < col_n) ? direct_d((HYPRE_Int) (g - col_1)) : direct_o((HYPRE_Int) (-g - 1));
+               }
+               if (shared) { continue; }
                for (HYPRE_Int kk = Sop.i[(size_t) i1]; kk < Sop.i[(size_t) i1 + 1]; kk++)
                {
                   const HYPRE_BigInt g = Sop.j[(size_t) kk];
@@ -333,7 +363,7 @@ HYPRE_Int dist_build_extpi_interp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, h
                for (HYPRE_Int j1 = Adi[i1] + 1; j1 < Adi[i1 + 1]; j1++)
                {
                   const HYPRE_Int i2 = Adj[j1];
-                  if ((mk[(size_t) i2] >= bd || i2 == i) && (sgn * Ada[j1]) < 0) { sum += Ada[j1]; }
+                  if ((mk[(size_t) i2] >= bd || (plus_i && i2 == i)) && (sgn * Ada[j1]) < 0) { sum += Ada[j1]; }
                }
                for (HYPRE_Int j1 = Aoi[i1]; j1 < Aoi[i1 + 1]; j1++)
                {
@@ -347,7 +377,7 @@ HYPRE_Int dist_build_extpi_interp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, h
                   {
                      const HYPRE_Int i2 = Adj[j1];
                      if (mk[(size_t) i2] >= bd && (sgn * Ada[j1]) < 0) { pda[(size_t) mk[(size_t) i2]] += distribute * Ada[j1]; }
-                     if (i2 == i && (sgn * Ada[j1]) < 0) { diagonal += distribute * Ada[j1]; }
+                     if (plus_i && i2 == i && (sgn * Ada[j1]) < 0) { diagonal += distribute * Ada[j1]; }
                   }
                   for (HYPRE_Int j1 = Aoi[i1]; j1 < Aoi[i1 + 1]; j1++)
                   {
@@ -372,7 +402,7 @@ HYPRE_Int dist_build_extpi_interp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, h
                   if (g >= col_1 && g < col_n)
                   {
                      const HYPRE_Int lc = (HYPRE_Int) (g - col_1);
-                     if (mk[(size_t) lc] >= bd || lc == i) { sum += Aext.a[(size_t) j1]; }
+                     if (mk[(size_t) lc] >= bd || (plus_i && lc == i)) { sum += Aext.a[(size_t) j1]; }
                   }
                   else
                   {
@@ -390,7 +420,7 @@ HYPRE_Int dist_build_extpi_interp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, h
                      {
                         const HYPRE_Int lc = (HYPRE_Int) (g - col_1);
                         if (mk[(size_t) lc] >= bd) { pda[(size_t) mk[(size_t) lc]] += distribute * Aext.a[(size_t) j1]; }
-                        if (lc == i) { diagonal += distribute * Aext.a[(size_t) j1]; }
+                        if (plus_i && lc == i) { diagonal += distribute * Aext.a[(size_t) j1]; }
                      }
                      else
                      {
@@ -714,7 +744,7 @@ HYPRE_Int dist_device_pmis(hypre_ParCSRMatrix *S, hypre_ParCSRMatrix *A, HYPRE_I
 // (2) the end — Pd and Po gave their arrays to P (adopt_device_blocks), the extra package goes with gh.
 HYPRE_Int dist_device_extpi_interp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, hypre_ParCSRMatrix *S,
                                    HYPRE_BigInt *num_cpts_global, HYPRE_BigInt total_global_cpts, HYPRE_Real trunc_factor,
-                                   HYPRE_Int max_elmts, HYPRE_Int first_rung, hypre_ParCSRMatrix **P_ptr)
+                                   HYPRE_Int max_elmts, HYPRE_Int first_rung, HYPRE_Int interp_type, hypre_ParCSRMatrix **P_ptr)
 {
    *P_ptr = nullptr;
    MPI_Comm comm = A->comm;
@@ -814,7 +844,7 @@ HYPRE_Int dist_device_extpi_interp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, 
          HIP_CHECK(hipMemcpyAsync(dF2Cx + n, f2c_g.data(), sizeof(int) * (size_t) full_off, hipMemcpyHostToDevice, st));
       }
       HIP_CHECK(hipStreamSynchronize(st));
-      ok = device_extpi(n, E.i, E.j, E.a, SE.i, SE.j, dCFf, dF2Cx, trunc_factor, max_elmts, first_rung, &Pd.i.p, &Pd.j.p, &Pd.a.p, &Pd.nnz, st,
+      ok = device_extpi(n, E.i, E.j, E.a, SE.i, SE.j, dCFf, dF2Cx, trunc_factor, max_elmts, first_rung, interp_type, &Pd.i.p, &Pd.j.p, &Pd.a.p, &Pd.nnz, st,
                         ncP, &Po.i.p, &Po.j.p, &Po.a.p, &Po.nnz);
    }
    dF2Cx.reset();

@@ -369,6 +369,10 @@ def parse_cli(argv):
         # two ids: tests/test_cogmres_cli.py pins them as outside its scope
         raise SystemExit("ij: -solver %d is outside the scope of this driver (0 AMG, 1 AMG-PCG, 2 DS-PCG, 3 AMG-GMRES, 4 DS-GMRES, "
                          "16 AMG-COGMRES, 17 DS-COGMRES)" % opt.solver)
+    if opt.interp_type not in (6, 3):
+        # extended (14) and ext+i-if-no-common-C (7) are served by run() for options built in code; the command line keeps
+        # refusing them: tests/test_ij_cli.py pins -interptype 7 as outside its scope
+        raise SystemExit("ij: -interptype %d is outside the scope of this driver (6 ext+i, 3 direct)" % opt.interp_type)
     return check_options(opt)
 
 
@@ -395,8 +399,9 @@ def check_options(opt):
         why = multivector_amg_refusal(opt)
         if why:
             raise SystemExit("ij: -nc %d with -solver %d: %s" % (opt.num_components, opt.solver, why))
-    if opt.interp_type not in (6, 3):
-        raise SystemExit("ij: -interptype %d is outside the scope of this driver (6 ext+i, 3 direct)" % opt.interp_type)
+    if opt.interp_type not in (6, 7, 14, 3):
+        raise SystemExit("ij: interp_type %d is outside the scope of this driver (6 ext+i, 7 ext+i if no common C point, "
+                         "14 extended, 3 direct)" % opt.interp_type)
     smoothers = (-1, 0, 3, 4, 6, 7, 8, 11, 12, 13, 14, 15, 16, 17, 18, 88, 89)
     for name in ("relax_type", "relax_down", "relax_up"):
         if getattr(opt, name) not in smoothers:

@@ -381,6 +381,14 @@ HYPRE_Int hypre_BoomerAMGBuildExtPIInterp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_m
                                           HYPRE_BigInt *num_cpts_global, HYPRE_Int num_functions,
                                           HYPRE_Int *dof_func, HYPRE_Int debug_flag, HYPRE_Real trunc_factor,
                                           HYPRE_Int max_elmts, hypre_ParCSRMatrix **P_ptr);
+HYPRE_Int hypre_BoomerAMGBuildExtInterp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, hypre_ParCSRMatrix *S,
+                                        HYPRE_BigInt *num_cpts_global, HYPRE_Int num_functions,
+                                        HYPRE_Int *dof_func, HYPRE_Int debug_flag, HYPRE_Real trunc_factor,
+                                        HYPRE_Int max_elmts, hypre_ParCSRMatrix **P_ptr);
+HYPRE_Int hypre_BoomerAMGBuildExtPICCInterp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, hypre_ParCSRMatrix *S,
+                                            HYPRE_BigInt *num_cpts_global, HYPRE_Int num_functions,
+                                            HYPRE_Int *dof_func, HYPRE_Int debug_flag, HYPRE_Real trunc_factor,
+                                            HYPRE_Int max_elmts, hypre_ParCSRMatrix **P_ptr);
 HYPRE_Int hypre_BoomerAMGBuildDirInterp(hypre_ParCSRMatrix *A, HYPRE_Int *CF_marker, hypre_ParCSRMatrix *S,
                                         HYPRE_BigInt *num_cpts_global, HYPRE_Int num_functions,
                                         HYPRE_Int *dof_func, HYPRE_Int debug_flag, HYPRE_Real trunc_factor,
