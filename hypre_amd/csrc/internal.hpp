@@ -385,6 +385,14 @@ void launch_axpy_dot(double a, const double *x, double *y, const double *z, size
 // launch_dot(y, y); z = a (x - y), the bits of launch_copy(z, x), launch_scale(z, -1), launch_axpy(1, y, z), launch_scale(z, -a)
 void launch_copy_norm2(const double *x, double *y, size_t n, double *d_out, hipStream_t s);
 void launch_scaled_diff(double a, const double *x, const double *y, double *z, size_t n, hipStream_t s);
+// the vector work of a BiCGSTAB iteration (mass_kernels.hip).  The first two return where their two sums lie in device
+// scratch, valid until the next reduction: <x, y> and <y, y>, the bits of launch_dot(x, y) and launch_dot(y, y);
+// x += a v, r += b s with <r, r> and <r0, r> of the updated r, the bits of two launch_axpy and two launch_dot.  The third:
+// p = r + c (p + g q), the bits of launch_axpy(g, q, p), hypre_SeqVectorScale's scaling by c, launch_axpy(1, r, p).
+double *launch_dot_with_norm2(const double *x, const double *y, size_t n, hipStream_t s);
+double *launch_bicgstab_update(double a, const double *v, double *x, double b, const double *sv, double *r, const double *r0, size_t n,
+                               hipStream_t s);
+void launch_bicgstab_direction(double g, const double *q, double c, const double *r, double *p, size_t n, hipStream_t s);
 // batched BLAS-1 (mass_kernels.hip): k vectors in chunks of MASS_CHUNK, every vector read once per chunk.  The dots
 // return where their k (2 k: <x, z_j> first, <y, z_j> behind) sums lie in device scratch, valid until the next
 // reduction; sum j has the bits of launch_dot(x, y_j), the update those of k launch_axpy calls in order.

@@ -3,6 +3,9 @@
 // on: step i of a restart cycle needs <p_i, p_j> for all j < i and p_i -= sum_j h_j p_j, which as separate dots and
 // axpys is 5 i vector passes and i read-backs; batched it is 2 i + 2 passes and one read-back.
 //
+// Beside them the fused vector passes of the other Krylov callers: the Gram-Schmidt step of FlexGMRES, the end of an
+// LGMRES cycle, and the two-sum passes and the direction update of BiCGSTAB (par_bicgstab.cpp).
+//
 // Replaces (behaviourally) the host loops of
 //   seq_mv/vector_batched.c   hypre_SeqVectorMassInnerProd / MassDotpTwo / MassAxpy (and their 4- and 8-fold unrollings)
 //
@@ -213,6 +216,84 @@ __global__ void scaled_diff_kernel(double na, const double *__restrict__ x, cons
    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) { z[n - 1] = __dmul_rn(__dsub_rn(y[n - 1], x[n - 1]), na); }
 }
 
+// The vector work of a BiCGSTAB iteration outside its two preconditioner applications and two products with A
+// (par_bicgstab.cpp, krylov/bicgstab.c:473-560), three kernels.
+//
+// <x, y> and <y, y> in one pass over x and y: the partials dot_partial_kernel leaves for each (accumulator 0 and 1), y
+// read once.
+__global__ __launch_bounds__(256)
+void dot_with_norm2_kernel(const double *__restrict__ x, const double *__restrict__ y, size_t n, double *__restrict__ partial)
+{
+   __shared__ double wsum[2][4];
+   double acc[2] = {0.0, 0.0};
+   VEC_LOOP_BEGIN
+      const double2 xv = reinterpret_cast<const double2 *>(x)[i];
+      const double2 yv = reinterpret_cast<const double2 *>(y)[i];
+      acc[0] += dot_pair(xv, yv);
+      acc[1] += dot_pair(yv, yv);
+   VEC_LOOP_END
+   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
+   {
+      acc[0] = dot_last(x[n - 1], y[n - 1], acc[0]);
+      acc[1] = dot_last(y[n - 1], y[n - 1], acc[1]);
+   }
+   MASS_FOLD(acc, wsum, 2)
+}
+
+// x += a v and r += b s, each rounded like axpy_kernel rounds it (the same expression under the same contraction rule),
+// and the partials of <r, r> (accumulator 0) and <r0, r> (accumulator 1) of the updated r, walked and folded like
+// dot_partial_kernel walks and folds them.  The six vectors are distinct.
+__global__ __launch_bounds__(256)
+void bicgstab_update_kernel(double a, const double *__restrict__ v, double *__restrict__ x, double b, const double *__restrict__ s,
+                            double *__restrict__ r, const double *__restrict__ r0, size_t n, double *__restrict__ partial)
+{
+   __shared__ double wsum[2][4];
+   double acc[2] = {0.0, 0.0};
+   VEC_LOOP_BEGIN
+      const double2 vv = reinterpret_cast<const double2 *>(v)[i];
+      const double2 sv = reinterpret_cast<const double2 *>(s)[i];
+      const double2 zv = reinterpret_cast<const double2 *>(r0)[i];
+      double2 xv = reinterpret_cast<double2 *>(x)[i];
+      double2 rv = reinterpret_cast<double2 *>(r)[i];
+      xv.x += a * vv.x; xv.y += a * vv.y;
+      rv.x += b * sv.x; rv.y += b * sv.y;
+      reinterpret_cast<double2 *>(x)[i] = xv;
+      reinterpret_cast<double2 *>(r)[i] = rv;
+      acc[0] += dot_pair(rv, rv);
+      acc[1] += dot_pair(zv, rv);
+   VEC_LOOP_END
+   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
+   {
+      x[n - 1] += a * v[n - 1];
+      double t = r[n - 1];
+      t += b * s[n - 1];
+      r[n - 1] = t;
+      acc[0] = dot_last(t, t, acc[0]);
+      acc[1] = dot_last(r0[n - 1], t, acc[1]);
+   }
+   MASS_FOLD(acc, wsum, 2)
+}
+
+// p = r + c (p + g q), three roundings spelled out so that nothing is contracted across them: the fused multiply-add of
+// axpy_kernel for p + g q, the product of scale_kernel, the sum axpy_kernel leaves for a coefficient of 1.  c == 0 is
+// the shortcut of hypre_SeqVectorScale (zero whatever p + g q holds); at c == 1, its other one, the product is exact.
+__device__ __forceinline__ double bicgstab_direction(double g, double q, double c, double r, double p)
+{
+   const double t = __fma_rn(g, q, p);
+   return __dadd_rn(c == 0.0 ? 0.0 : __dmul_rn(t, c), r);
+}
+__global__ void bicgstab_direction_kernel(double g, const double *__restrict__ q, double c, const double *__restrict__ r,
+                                          double *__restrict__ p, size_t n)
+{
+   VEC_LOOP_BEGIN
+      const double2 qv = reinterpret_cast<const double2 *>(q)[i];
+      const double2 rv = reinterpret_cast<const double2 *>(r)[i];
+      const double2 pv = reinterpret_cast<double2 *>(p)[i];
+      reinterpret_cast<double2 *>(p)[i] = make_double2(bicgstab_direction(g, qv.x, c, rv.x, pv.x), bicgstab_direction(g, qv.y, c, rv.y, pv.y));
+   VEC_LOOP_END
+   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) { p[n - 1] = bicgstab_direction(g, q[n - 1], c, r[n - 1], p[n - 1]); }
+}
+
 // ---------------------------------------------------------------------------
 // launchers: k vectors in chunks of MASS_CHUNK, one kernel instance per chunk length
 // ---------------------------------------------------------------------------
@@ -346,6 +427,48 @@ void launch_scaled_diff(double a, const double *x, const double *y, double *z, s
 {
    account_bytes(24.0 * n);
    if (n) { hipLaunchKernelGGL(scaled_diff_kernel, dim3(vec_grid(n)), dim3(256), 0, s, -a, x, y, z, n); }
+}
+
+// d_out[0] = <x, y>, d_out[1] = <y, y> (this rank's part): the bits of launch_dot(x, y) and launch_dot(y, y), in 16 n
+// bytes instead of 32 n; returns d_out, in device scratch and valid until the next reduction
+double *launch_dot_with_norm2(const double *x, const double *y, size_t n, hipStream_t s)
+{
+   account_bytes(16.0 * n);
+   double *partial;
+   double *out = mass_scratch(2, &partial);
+   const int nb = dot_grid(n);
+   hipLaunchKernelGGL(dot_with_norm2_kernel, dim3(nb), dim3(256), 0, s, x, y, n, partial);
+   HIP_CHECK(hipGetLastError());
+   hipLaunchKernelGGL(mass_dot_final_kernel, dim3(2), dim3(256), 0, s, partial, nb, 2, out, out);
+   HIP_CHECK(hipGetLastError());
+   return out;
+}
+
+// x += a v, r += b s, d_out[0] = <r, r>, d_out[1] = <r0, r> of the updated r (this rank's part): the bits of
+// launch_axpy(a, v, x), launch_axpy(b, s, r), launch_dot(r, r), launch_dot(r0, r), in 56 n bytes instead of 80 n and 2
+// launches instead of 6; returns d_out as above
+double *launch_bicgstab_update(double a, const double *v, double *x, double b, const double *sv, double *r, const double *r0, size_t n,
+                               hipStream_t s)
+{
+   account_bytes(56.0 * n);
+   double *partial;
+   double *out = mass_scratch(2, &partial);
+   const int nb = dot_grid(n);
+   hipLaunchKernelGGL(bicgstab_update_kernel, dim3(nb), dim3(256), 0, s, a, v, x, b, sv, r, r0, n, partial);
+   HIP_CHECK(hipGetLastError());
+   hipLaunchKernelGGL(mass_dot_final_kernel, dim3(2), dim3(256), 0, s, partial, nb, 2, out, out);
+   HIP_CHECK(hipGetLastError());
+   return out;
+}
+
+// p = r + c (p + g q); p is neither q nor r.  The bits of launch_axpy(g, q, p), launch_scale(p, c) with the shortcuts of
+// hypre_SeqVectorScale, launch_axpy(1, r, p), in 32 n bytes instead of 64 n
+void launch_bicgstab_direction(double g, const double *q, double c, const double *r, double *p, size_t n, hipStream_t s)
+{
+   account_bytes(32.0 * n);
+   if (!n) { return; }
+   hipLaunchKernelGGL(bicgstab_direction_kernel, dim3(vec_grid(n)), dim3(256), 0, s, g, q, c, r, p, n);
+   HIP_CHECK(hipGetLastError());
 }
 
 void preload_mass_kernels() { hipFuncAttributes at; (void) hipFuncGetAttributes(&at, (const void *) mass_dot_final_kernel); (void) hipGetLastError(); }

@@ -25,8 +25,8 @@ class IJOptions:
         self.sys_num_fun = 1          # -sysL <num functions>: systems version of the 7-point operator
         self.c = (1.0, 1.0, 1.0)      # -c cx cy cz
         self.a = (1.0, 1.0, 1.0)      # -a ax ay az (difconv)
-        self.solver = 0               # 0 AMG, 1 AMG-PCG, 2 DS-PCG (diagonal scaling), 3 AMG-GMRES, 4 DS-GMRES, 16 AMG-COGMRES, 17 DS-COGMRES,
-                                      # 60 DS-FlexGMRES, 61 AMG-FlexGMRES
+        self.solver = 0               # 0 AMG, 1 AMG-PCG, 2 DS-PCG (diagonal scaling), 3 AMG-GMRES, 4 DS-GMRES, 9 AMG-BiCGSTAB, 10 DS-BiCGSTAB,
+                                      # 16 AMG-COGMRES, 17 DS-COGMRES, 60 DS-FlexGMRES, 61 AMG-FlexGMRES
         self.lgmres = 0               # options only: 1 runs LGMRES in place of GMRES, solver 4 as DS-LGMRES (the reference's -solver 50),
                                       # solver 3 as AMG-LGMRES (51)
         self.neg_a = 0                # -negA 1: solve with -A (test/ij.c:4014-4017)
@@ -364,11 +364,11 @@ def parse_cli(argv):
             i += 3
         else:
             raise SystemExit("ij: option %s is outside the scope of this driver" % flag)
-    if opt.solver not in (0, 1, 2, 3, 4, 16, 17):
+    if opt.solver not in (0, 1, 2, 3, 4, 9, 10, 16, 17):
         # FlexGMRES (60 DS, 61 AMG) is served by run() for options built in code, but the command line keeps refusing the
         # two ids: tests/test_cogmres_cli.py pins them as outside its scope
         raise SystemExit("ij: -solver %d is outside the scope of this driver (0 AMG, 1 AMG-PCG, 2 DS-PCG, 3 AMG-GMRES, 4 DS-GMRES, "
-                         "16 AMG-COGMRES, 17 DS-COGMRES)" % opt.solver)
+                         "9 AMG-BiCGSTAB, 10 DS-BiCGSTAB, 16 AMG-COGMRES, 17 DS-COGMRES)" % opt.solver)
     if opt.interp_type not in (6, 3):
         # extended (14) and ext+i-if-no-common-C (7) are served by run() for options built in code; the command line keeps
         # refusing them: tests/test_ij_cli.py pins -interptype 7 as outside its scope
@@ -379,7 +379,7 @@ def parse_cli(argv):
 def check_options(opt):
     """The combinations of options this driver serves, whether they came from the command line or were set in code
     (solvers 60 / 61, FlexGMRES, and lgmres = 1, only the latter); returns opt."""
-    if opt.solver not in (0, 1, 2, 3, 4, 16, 17, 60, 61):
+    if opt.solver not in (0, 1, 2, 3, 4, 9, 10, 16, 17, 60, 61):
         raise SystemExit("ij: solver %d is outside the scope of this driver" % opt.solver)
     if opt.lgmres not in (0, 1) or (opt.lgmres and opt.solver not in (3, 4)):
         raise SystemExit("ij: lgmres = %r with solver %d: LGMRES runs as solver 4 (DS-LGMRES, the reference's 50) or solver 3 "
@@ -392,7 +392,7 @@ def check_options(opt):
     if opt.num_components > 1 and opt.solver in (16, 17):
         raise SystemExit("ij: -nc %d with -solver %d: COGMRES doesn't take multicomponent vectors in this driver (GMRES, -solver 3 | 4, does)"
                          % (opt.num_components, opt.solver))
-    if opt.num_components > 1 and opt.solver in (0, 1, 3, 61):
+    if opt.num_components > 1 and opt.solver in (0, 1, 3, 9, 61):
         # BoomerAMG on multivectors (hypre_BoomerAMGSolve with num_vectors > 1) serves l1-Jacobi / Jacobi 7 / 18 and two-stage
         # Gauss-Seidel 11 / 12 over all points with a direct coarsest-level solve; the reference refuses hybrid Gauss-Seidel
         # (the defaults 13 / 14) with multicomponent vectors as well
@@ -445,7 +445,7 @@ def run(opt, comm=0, rank=0, nprocs=1, allreduce=None, out=None):
     out = out or sys.stdout
     L = B.load_library()
     A = build_matrix(opt, comm=comm, rank=rank, nprocs=nprocs)
-    if opt.solver in (2, 4, 17, 60):
+    if opt.solver in (2, 4, 10, 17, 60):
         return run_ds_pcg(opt, A, comm=comm, rank=rank, allreduce=allreduce, out=out)
     s = create_amg(opt, memory_location=DEVICE)
     L.HYPRE_BoomerAMGSetup(s, A, None, None)
@@ -507,6 +507,9 @@ def run(opt, comm=0, rank=0, nprocs=1, allreduce=None, out=None):
     elif opt.solver == 16:
         its.value, rel.value = solve_cogmres(opt, A, db, dx, comm=comm, amg=s)
         lines += ["", "COGMRES Iterations = %d" % its.value, "Final COGMRES Relative Residual Norm = %e" % rel.value, ""]
+    elif opt.solver == 9:
+        its.value, rel.value = solve_bicgstab(opt, A, db, dx, comm=comm, amg=s)
+        lines += ["", "BiCGSTAB Iterations = %d" % its.value, "Final BiCGSTAB Relative Residual Norm = %e" % rel.value, ""]
     elif opt.solver == 61:
         its.value, rel.value = solve_flexgmres(opt, A, db, dx, comm=comm, amg=s)
         lines += ["", "FlexGMRES Iterations = %d" % its.value, "Final FlexGMRES Relative Residual Norm = %e" % rel.value, ""]
@@ -601,7 +604,7 @@ def solve_ds_gmres(opt, A, db, dx, comm=0):
 
 
 def run_ds_pcg(opt, A, comm=0, rank=0, allreduce=None, out=None):
-    """`ij -solver 2 | 4 | 17 | 60 [-nc N]` (4 with lgmres = 1: DS-LGMRES) on the device: no hierarchy; the N columns of b (test/ij.c:3483-3512: the same values in
+    """`ij -solver 2 | 4 | 10 | 17 | 60 [-nc N]` (4 with lgmres = 1: DS-LGMRES) on the device: no hierarchy; the N columns of b (test/ij.c:3483-3512: the same values in
     every component) and of the zero initial guess as multivectors."""
     L = B.load_library()
     L.hypre_ParCSRMatrixMigrate(A, DEVICE)
@@ -621,13 +624,14 @@ def run_ds_pcg(opt, A, comm=0, rank=0, allreduce=None, out=None):
     else:
         db = B.parvec_from_numpy(b, comm=comm, global_size=nglob, first=first)
         dx = B.parvec_from_numpy(x0, comm=comm, global_size=nglob, first=first)
-    solve = {2: solve_ds_pcg, 4: solve_lgmres if opt.lgmres else solve_ds_gmres, 17: solve_cogmres, 60: solve_flexgmres}[opt.solver]
+    solve = {2: solve_ds_pcg, 4: solve_lgmres if opt.lgmres else solve_ds_gmres, 10: solve_bicgstab, 17: solve_cogmres,
+             60: solve_flexgmres}[opt.solver]
     its, rel = solve(opt, A, db, dx, comm=comm)
     L.HYPRE_ClearError(256)
     B.check()
     L.hypre_ParVectorDestroy(db); L.hypre_ParVectorDestroy(dx)
     if rank == 0:
-        tag = {4: "LGMRES " if opt.lgmres else "GMRES ", 17: "COGMRES ", 60: "FlexGMRES "}.get(opt.solver, "")
+        tag = {4: "LGMRES " if opt.lgmres else "GMRES ", 10: "BiCGSTAB ", 17: "COGMRES ", 60: "FlexGMRES "}.get(opt.solver, "")
         out.write("\n".join(["", "%sIterations = %d" % (tag, its), "Final %sRelative Residual Norm = %e" % (tag, rel), ""]) + "\n")
         out.flush()
     return its, rel
@@ -660,6 +664,35 @@ def solve_lgmres(opt, A, b, x, comm=0, amg=None):
     return _solve_gmres_family("LGMRES", opt, A, b, x, comm, amg, early=(("AugDim", opt.aug_dim),),
                                late=(("Logging", 1), ("PrintLevel", 3)),            # ioutdat; inert here
                                amg_max_iter=opt.mg_max_iter, check_precond=True)
+
+
+def solve_bicgstab(opt, A, b, x, comm=0, amg=None):
+    """test/ij.c:8002-8172, 8324-8367: BiCGSTAB behind BoomerAMG (solver 9, `amg` the set-up hierarchy, run as a preconditioner:
+    SetTol 0, SetMaxIter precon_cycles; the iteration limit is then mg_max_iter, test/ij.c:8156) or behind the diagonal
+    scaling preconditioner (solver 10); b and x may be multivectors (-nc N).  The reference driver also asks for the
+    solver's table of norms (ioutdat); this one prints the closing lines alone, as for its other solvers."""
+    L = B.load_library()
+    g = C.c_void_p()
+    L.HYPRE_ParCSRBiCGSTABCreate(comm, C.byref(g))
+    L.HYPRE_BiCGSTABSetMaxIter(g, opt.max_iter)
+    L.HYPRE_BiCGSTABSetTol(g, opt.tol)
+    L.HYPRE_BiCGSTABSetAbsoluteTol(g, 0.0)
+    L.HYPRE_BiCGSTABSetLogging(g, 1)
+    L.HYPRE_BiCGSTABSetPrintLevel(g, 0)
+    if amg is not None:
+        L.HYPRE_BoomerAMGSetTol(amg, 0.0)
+        L.HYPRE_BoomerAMGSetMaxIter(amg, opt.precon_cycles)
+        L.HYPRE_BiCGSTABSetMaxIter(g, opt.mg_max_iter)
+        L.HYPRE_BiCGSTABSetPrecond(g, C.cast(L.HYPRE_BoomerAMGSolve, C.c_void_p), None, amg)
+    else:
+        L.HYPRE_BiCGSTABSetPrecond(g, C.cast(L.HYPRE_ParCSRDiagScale, C.c_void_p), C.cast(L.HYPRE_ParCSRDiagScaleSetup, C.c_void_p), None)
+    L.HYPRE_BiCGSTABSetup(g, A, b, x)
+    L.HYPRE_BiCGSTABSolve(g, A, b, x)
+    its, rel = C.c_int(), C.c_double()
+    L.HYPRE_BiCGSTABGetNumIterations(g, C.byref(its))
+    L.HYPRE_BiCGSTABGetFinalRelativeResidualNorm(g, C.byref(rel))
+    L.HYPRE_ParCSRBiCGSTABDestroy(g)
+    return its.value, rel.value
 
 
 def main(argv=None):

@@ -679,6 +679,75 @@ HYPRE_Int hypre_amd_ParVectorScaledCopy(HYPRE_Complex a, hypre_ParVector *x, hyp
 HYPRE_Int hypre_amd_ParVectorCopyThenInnerProd(hypre_ParVector *x, hypre_ParVector *y, HYPRE_Real *result);
 HYPRE_Int hypre_amd_ParVectorScaledDifference(HYPRE_Complex a, hypre_ParVector *x, hypre_ParVector *y, hypre_ParVector *z);
 
+/* ---- BiCGSTAB: the short-recurrence solver for non-symmetric operators (the reference's `ij -solver 9 | 10`) ----
+ * krylov/bicgstab.c:225-578, krylov/HYPRE_bicgstab.c, parcsr_ls/HYPRE_parcsr_bicgstab.c; defaults of hypre_BiCGSTABCreate
+ * (bicgstab.c:75-84): tol 1e-6, a_tol 0, cf_tol 0, min_iter 0, max_iter 1000, stop_crit 0.  An iteration applies the
+ * preconditioner twice and A twice and keeps six work vectors shaped like x, whatever the iteration count.  Operands are
+ * in device memory and may be multivectors (the flat inner product over all columns).  It stops at
+ * |r| <= max(a_tol, tol |b|) (|r_0| for |b| when b is zero; with stop_crit the absolute a_tol, or tol if a_tol is 0) once
+ * min_iter iterations are done, and then only if b - A x computed from x passes the same test; with cf_tol > 0 also when
+ * the average convergence factor (|r| / |r_0|)^(1 / (2 iter)) stays above cf_tol.  HYPRE_ERROR_CONV when max_iter is
+ * reached above the tolerance.  The three breakdowns (<r0, A M^-1 p>, <r0, r> or the step length gamma below the smallest
+ * normal number) raise HYPRE_ERROR_GENERIC with a message and, as in the reference, return without storing the iteration
+ * count or the norm.  Logging or PrintLevel > 0 keeps |r| of every iteration; PrintLevel > 0 prints the reference's table
+ * on rank 0. */
+HYPRE_Int HYPRE_ParCSRBiCGSTABCreate(MPI_Comm comm, HYPRE_Solver *solver);
+HYPRE_Int HYPRE_ParCSRBiCGSTABDestroy(HYPRE_Solver solver);
+HYPRE_Int HYPRE_ParCSRBiCGSTABSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_ParCSRBiCGSTABSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_ParCSRBiCGSTABSetTol(HYPRE_Solver solver, HYPRE_Real tol);
+HYPRE_Int HYPRE_ParCSRBiCGSTABSetAbsoluteTol(HYPRE_Solver solver, HYPRE_Real a_tol);
+HYPRE_Int HYPRE_ParCSRBiCGSTABSetMinIter(HYPRE_Solver solver, HYPRE_Int min_iter);
+HYPRE_Int HYPRE_ParCSRBiCGSTABSetMaxIter(HYPRE_Solver solver, HYPRE_Int max_iter);
+HYPRE_Int HYPRE_ParCSRBiCGSTABSetStopCrit(HYPRE_Solver solver, HYPRE_Int stop_crit);
+HYPRE_Int HYPRE_ParCSRBiCGSTABSetPrecond(HYPRE_Solver solver, HYPRE_PtrToSolverFcn precond,
+                                         HYPRE_PtrToSolverFcn precond_setup, HYPRE_Solver precond_solver);
+HYPRE_Int HYPRE_ParCSRBiCGSTABGetPrecond(HYPRE_Solver solver, HYPRE_Solver *precond_data_ptr);
+HYPRE_Int HYPRE_ParCSRBiCGSTABSetLogging(HYPRE_Solver solver, HYPRE_Int logging);
+HYPRE_Int HYPRE_ParCSRBiCGSTABSetPrintLevel(HYPRE_Solver solver, HYPRE_Int level);
+HYPRE_Int HYPRE_ParCSRBiCGSTABGetNumIterations(HYPRE_Solver solver, HYPRE_Int *num_iterations);
+HYPRE_Int HYPRE_ParCSRBiCGSTABGetFinalRelativeResidualNorm(HYPRE_Solver solver, HYPRE_Real *norm);
+HYPRE_Int HYPRE_ParCSRBiCGSTABGetResidual(HYPRE_Solver solver, HYPRE_ParVector *residual);
+HYPRE_Int HYPRE_BiCGSTABDestroy(HYPRE_Solver solver);
+HYPRE_Int HYPRE_BiCGSTABSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_BiCGSTABSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_BiCGSTABSetTol(HYPRE_Solver solver, HYPRE_Real tol);
+HYPRE_Int HYPRE_BiCGSTABSetAbsoluteTol(HYPRE_Solver solver, HYPRE_Real a_tol);
+HYPRE_Int HYPRE_BiCGSTABSetConvergenceFactorTol(HYPRE_Solver solver, HYPRE_Real cf_tol);
+HYPRE_Int HYPRE_BiCGSTABSetMinIter(HYPRE_Solver solver, HYPRE_Int min_iter);
+HYPRE_Int HYPRE_BiCGSTABSetMaxIter(HYPRE_Solver solver, HYPRE_Int max_iter);
+HYPRE_Int HYPRE_BiCGSTABSetStopCrit(HYPRE_Solver solver, HYPRE_Int stop_crit);
+HYPRE_Int HYPRE_BiCGSTABSetPrecond(HYPRE_Solver solver, HYPRE_PtrToSolverFcn precond,
+                                   HYPRE_PtrToSolverFcn precond_setup, HYPRE_Solver precond_solver);
+HYPRE_Int HYPRE_BiCGSTABGetPrecond(HYPRE_Solver solver, HYPRE_Solver *precond_data_ptr);
+HYPRE_Int HYPRE_BiCGSTABSetLogging(HYPRE_Solver solver, HYPRE_Int logging);
+HYPRE_Int HYPRE_BiCGSTABSetPrintLevel(HYPRE_Solver solver, HYPRE_Int level);
+HYPRE_Int HYPRE_BiCGSTABGetNumIterations(HYPRE_Solver solver, HYPRE_Int *num_iterations);
+HYPRE_Int HYPRE_BiCGSTABGetFinalRelativeResidualNorm(HYPRE_Solver solver, HYPRE_Real *norm);
+HYPRE_Int HYPRE_BiCGSTABGetResidual(HYPRE_Solver solver, void *residual);           /* a HYPRE_ParVector * */
+/* 1 (the default): of the eleven vector calls the reference makes between the two products with A, the two inner
+ * products of the step length are one pass, the second half step with the squared norm and <r0, r> of the new residual
+ * one pass, the direction update one pass; three read-backs instead of five.  The first half step stays two axpys (one
+ * launch would move the same bytes).  0: the reference's sequence of InnerProd / Axpy / Scale calls.  Either way a solve
+ * gives the same bits in x, the same iteration count and the same norms. */
+HYPRE_Int hypre_amd_BiCGSTABSetFusedUpdates(HYPRE_Solver solver, HYPRE_Int on);
+/* 1 when the last solve ended by meeting its tolerance (the reference keeps this flag without a getter). */
+HYPRE_Int hypre_amd_BiCGSTABGetConverged(HYPRE_Solver solver, HYPRE_Int *converged);
+/* The norms the last solve logged (Logging or PrintLevel > 0): |r_0|, then |r| of the recurrence after every iteration.
+ * The array belongs to the solver and holds until its next Solve or Destroy. */
+HYPRE_Int hypre_amd_BiCGSTABGetLoggedNorms(HYPRE_Solver solver, HYPRE_Int *count, const HYPRE_Real **norms);
+/* The vector operations BiCGSTAB adds, each one pass with the bits of the library calls it stands for (sums over all
+ * ranks, reduced together); device memory, equal lengths, a vector that is written distinct from every other operand.
+ *   InnerProdWithNorm         <x, y>, <y, y>                   InnerProd(x, y); InnerProd(y, y)
+ *   TwoAxpysThenInnerProds    x += a v, r += b s,              Axpy(a, v, x); Axpy(b, s, r);
+ *                             <r, r>, <r0, r>                  InnerProd(r, r); InnerProd(r0, r)
+ *   AxpyScaleAxpy             p = r + c (p + g q)              Axpy(g, q, p); Scale(c, p); Axpy(1, r, p) */
+HYPRE_Int hypre_amd_ParVectorInnerProdWithNorm(hypre_ParVector *x, hypre_ParVector *y, HYPRE_Real *xy, HYPRE_Real *yy);
+HYPRE_Int hypre_amd_ParVectorTwoAxpysThenInnerProds(HYPRE_Complex a, hypre_ParVector *v, hypre_ParVector *x, HYPRE_Complex b,
+                                                    hypre_ParVector *s, hypre_ParVector *r, hypre_ParVector *r0, HYPRE_Real *rr,
+                                                    HYPRE_Real *r0r);
+HYPRE_Int hypre_amd_ParVectorAxpyScaleAxpy(HYPRE_Complex g, hypre_ParVector *q, HYPRE_Complex c, hypre_ParVector *r, hypre_ParVector *p);
+
 #ifdef __cplusplus
 }
 #endif
