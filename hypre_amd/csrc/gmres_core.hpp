@@ -54,6 +54,13 @@ struct GMRESParams
    // ends at max_iter above its tolerance is "not converged" also when both tolerances are zero (a fixed number of
    // iterations), so callers of such runs clear the flag
    bool conv_error_at_zero_tol = false;
+   // gmres.c:597-615: after every step, give up when the weighted average convergence factor of the recurrence's norm
+   // exceeds cf_tol (0: never).  The rule is the caller's (krylov_common.hpp has the one copy PCG and BiCGSTAB use too):
+   // cf_exit(factor now, factor one step ago, cf_tol).  The correction of the cycle under way is not added to x.
+   double cf_tol = 0.0;
+   bool (*cf_exit)(double, double, double) = nullptr;
+   // the diagonally scaled phase of the hybrid solver may end at max_iter without "not converged" (gmres.c:901, hybrid == -1)
+   bool quiet_at_max_iter = false;
 };
 
 enum { GMRES_OK = 0, GMRES_NOT_A_NUMBER = 1, GMRES_NOT_CONVERGED = 2 };
@@ -217,7 +224,10 @@ GMRESResult gmres_iterate(const GMRESParams &prm, Ops &ops, V b, V x, V r, V w, 
    const KrylovStart st = krylov_start(ops, b, x, p[0], prm.tol, prm.a_tol);
    if (st.not_a_number) { res.status = GMRES_NOT_A_NUMBER; return res; }
    const double b_norm = st.b_norm, den_norm = st.den_norm, epsilon = st.epsilon;
-   double t, r_norm = st.r_norm, real_r_norm_old = b_norm;
+   double t, r_norm = st.r_norm, real_r_norm_old = b_norm, cf_ave_0 = 0.0, cf_ave_1 = 0.0;
+   const double r_norm_0 = st.r_norm;
+   const bool watch_cf = prm.cf_tol > 0.0 && prm.cf_exit;
+   bool gave_up = false;
 
    while (iter < max_iter)
    {
@@ -275,8 +285,15 @@ GMRESResult gmres_iterate(const GMRESParams &prm, Ops &ops, V b, V x, V r, V w, 
                break;
          }
          r_norm = H.close_column(ops, p[i], i, t);
+         if (watch_cf)
+         {
+            cf_ave_0 = cf_ave_1;
+            cf_ave_1 = std::pow(r_norm / r_norm_0, 1.0 / (2.0 * iter));
+            if (prm.cf_exit(cf_ave_1, cf_ave_0, prm.cf_tol)) { gave_up = true; break; }
+         }
          if (r_norm <= epsilon && iter >= min_iter) { break; }
       }
+      if (gave_up) { break; }
       H.solve(i);
       // the correction, last direction first
       ops.copy(dir[i - 1], w);
@@ -313,6 +330,7 @@ GMRESResult gmres_iterate(const GMRESParams &prm, Ops &ops, V b, V x, V r, V w, 
       restart_residual(ops, p, i, H);
    }
    krylov_finish(res, iter, r_norm, b_norm, epsilon, max_iter, prm.conv_error_at_zero_tol);
+   if (prm.quiet_at_max_iter && res.status == GMRES_NOT_CONVERGED) { res.status = GMRES_OK; }
    return res;
 }
 

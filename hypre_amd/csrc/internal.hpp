@@ -393,6 +393,13 @@ double *launch_dot_with_norm2(const double *x, const double *y, size_t n, hipStr
 double *launch_bicgstab_update(double a, const double *v, double *x, double b, const double *sv, double *r, const double *r0, size_t n,
                                hipStream_t s);
 void launch_bicgstab_direction(double g, const double *q, double c, const double *r, double *p, size_t n, hipStream_t s);
+// the vector work of a diagonally scaled CG iteration in one pass (mass_kernels.hip): x += a p, r += na s, s = r ./ d with
+// <r, r> and <r, s> in d_out[0..1], the bits of launch_pcg_update, launch_diag_first_scale and launch_dot(r, s); d is the
+// diagonal launch_pack_first_entries packed (it raises *d_flag at a row without entries)
+void launch_dscg_step(double a, double na, const double *p, const double *d, double *sv, double *x, double *r, size_t n, double *d_out,
+                      hipStream_t s);
+void launch_pack_first_entries(const int *Ai, const double *Aa, double *d, size_t n, int *d_flag, hipStream_t s);
+size_t dot_grid_pass_elements();
 // batched BLAS-1 (mass_kernels.hip): k vectors in chunks of MASS_CHUNK, every vector read once per chunk.  The dots
 // return where their k (2 k: <x, z_j> first, <y, z_j> behind) sums lie in device scratch, valid until the next
 // reduction; sum j has the bits of launch_dot(x, y_j), the update those of k launch_axpy calls in order.

@@ -2,8 +2,32 @@
 // preconditioner an application hands to HYPRE_*SetPrecond, and how a Solve begins.
 #pragma once
 #include "amg_internal.hpp"
+#include <algorithm>
+#include <cmath>
+
+// the hybrid solver (par_hybrid.cpp) tells the Krylov solver it drives which phase it is in, as the reference's
+// hypre_PCGSetHybrid / hypre_GMRESSetHybrid / hypre_BiCGSTABSetHybrid do (krylov.h:1654, 1284, 1225): -1 is the
+// diagonally scaled phase, which may end at its iteration limit without HYPRE_ERROR_CONV (pcg.c:988, gmres.c:901,
+// bicgstab.c:573)
+extern "C" {
+HYPRE_Int hypre_PCGSetHybrid(HYPRE_Solver solver, HYPRE_Int level);
+HYPRE_Int hypre_GMRESSetHybrid(HYPRE_Solver solver, HYPRE_Int level);
+HYPRE_Int hypre_BiCGSTABSetHybrid(HYPRE_Solver solver, HYPRE_Int level);
+}
 
 namespace hamd {
+
+// The convergence-factor exit of PCG, GMRES and BiCGSTAB (pcg.c:941-950, gmres.c:600-614, bicgstab.c:533-543): cf_ave_1 is
+// the average convergence factor after this iteration, (|r_i| / |r_0|)^(1 / (2 i)) in the norm the solver tests, cf_ave_0
+// the one after the iteration before (0 before the first).  The weight trusts the estimate the more the less it moved;
+// true: convergence is slower than cf_tol allows, the solve gives up.  Callers look at it for cf_tol > 0 only.
+inline bool convergence_factor_exceeds(double cf_ave_1, double cf_ave_0, double cf_tol)
+{
+   double weight = std::fabs(cf_ave_1 - cf_ave_0);
+   weight = weight / std::max(cf_ave_1, cf_ave_0);
+   weight = 1.0 - weight;
+   return weight * cf_ave_1 > cf_tol;
+}
 
 // a work vector shaped like x: as many columns as a multivector x has (`ij -nc N`), at x's memory location (CreateVector
 // of krylov/pcg.c:226-260, gmres.c:204-215, cogmres.c:220-231, flexgmres.c:230-250)

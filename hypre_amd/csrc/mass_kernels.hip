@@ -4,7 +4,8 @@
 // axpys is 5 i vector passes and i read-backs; batched it is 2 i + 2 passes and one read-back.
 //
 // Beside them the fused vector passes of the other Krylov callers: the Gram-Schmidt step of FlexGMRES, the end of an
-// LGMRES cycle, and the two-sum passes and the direction update of BiCGSTAB (par_bicgstab.cpp).
+// LGMRES cycle, the two-sum passes and the direction update of BiCGSTAB (par_bicgstab.cpp), and the step of diagonally
+// scaled CG: update, scaling and both sums in one pass over a packed diagonal (par_pcg.cpp).
 //
 // Replaces (behaviourally) the host loops of
 //   seq_mv/vector_batched.c   hypre_SeqVectorMassInnerProd / MassDotpTwo / MassAxpy (and their 4- and 8-fold unrollings)
@@ -294,6 +295,60 @@ __global__ void bicgstab_direction_kernel(double g, const double *__restrict__ q
    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) { p[n - 1] = bicgstab_direction(g, q[n - 1], c, r[n - 1], p[n - 1]); }
 }
 
+// The vector work of a diagonally scaled CG iteration between the product with A and the direction update (par_pcg.cpp,
+// krylov/pcg.c:716-760 behind HYPRE_ParCSRDiagScale), one kernel.  On entry s holds A p.
+//
+// x += a p and r += na s with the expressions of pcg_update_kernel, s = r ./ d with the division of
+// diag_first_scale_kernel, and the partials of <r, r> (accumulator 0, the term of pcg_update_kernel) and of <r, s>
+// (accumulator 1, the term of dot_partial_kernel), walked and folded like those two walk and fold them.  d is the packed
+// diagonal; the five vectors are distinct.
+__global__ __launch_bounds__(256)
+void dscg_step_kernel(double a, double na, const double *__restrict__ p, const double *__restrict__ d, double *__restrict__ s,
+                      double *__restrict__ x, double *__restrict__ r, size_t n, double *__restrict__ partial)
+{
+   __shared__ double wsum[2][4];
+   double acc[2] = {0.0, 0.0};
+   VEC_LOOP_BEGIN
+      const double2 pv = reinterpret_cast<const double2 *>(p)[i];
+      const double2 dv = reinterpret_cast<const double2 *>(d)[i];
+      double2 sv = reinterpret_cast<double2 *>(s)[i];
+      double2 xv = reinterpret_cast<double2 *>(x)[i];
+      double2 rv = reinterpret_cast<double2 *>(r)[i];
+      xv.x += a * pv.x; xv.y += a * pv.y;
+      rv.x += na * sv.x; rv.y += na * sv.y;
+      sv.x = rv.x / dv.x; sv.y = rv.y / dv.y;
+      reinterpret_cast<double2 *>(x)[i] = xv;
+      reinterpret_cast<double2 *>(r)[i] = rv;
+      reinterpret_cast<double2 *>(s)[i] = sv;
+      acc[0] += rv.x * rv.x + rv.y * rv.y;
+      acc[1] += dot_pair(rv, sv);
+   VEC_LOOP_END
+   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
+   {
+      x[n - 1] += a * p[n - 1];
+      const double rl = r[n - 1] + na * s[n - 1];
+      const double sl = rl / d[n - 1];
+      r[n - 1] = rl;
+      s[n - 1] = sl;
+      acc[0] += rl * rl;
+      acc[1] = dot_last(rl, sl, acc[1]);
+   }
+   MASS_FOLD(acc, wsum, 2)
+}
+
+// d[i] = the first entry of row i of the local block, which is its diagonal (par_csr_matop.c:6479-6575), where the row
+// has one; a row without entries gets 1 and raises the flag: the caller then keeps to the plain diagonal scaling
+__global__ void pack_first_entries_kernel(const int *__restrict__ Ai, const double *__restrict__ Aa, double *__restrict__ d, size_t n,
+                                          int *__restrict__ flag)
+{
+   for (size_t i = blockIdx.x * (size_t) blockDim.x + threadIdx.x; i < n; i += (size_t) gridDim.x * blockDim.x)
+   {
+      const int k = Ai[i];
+      if (k < Ai[i + 1]) { d[i] = Aa[k]; }
+      else { d[i] = 1.0; *flag = 1; }
+   }
+}
+
 // ---------------------------------------------------------------------------
 // launchers: k vectors in chunks of MASS_CHUNK, one kernel instance per chunk length
 // ---------------------------------------------------------------------------
@@ -470,6 +525,38 @@ void launch_bicgstab_direction(double g, const double *q, double c, const double
    hipLaunchKernelGGL(bicgstab_direction_kernel, dim3(vec_grid(n)), dim3(256), 0, s, g, q, c, r, p, n);
    HIP_CHECK(hipGetLastError());
 }
+
+// x += a p, r += na s, s = r ./ d, d_out[0] = <r, r>, d_out[1] = <r, s> (this rank's part; d_out is the caller's): the
+// bits of launch_pcg_update(a, na, p, s, x, r), launch_diag_first_scale on the rows d was packed from and
+// launch_dot(r, s), in 64 n bytes (p, d, s, x, r read; x, r, s written) instead of 48 n + 28 n + 16 n, the 28 with the
+// row pointer and the gathered value, and 2 launches instead of 5
+void launch_dscg_step(double a, double na, const double *p, const double *d, double *sv, double *x, double *r, size_t n, double *d_out,
+                      hipStream_t s)
+{
+   account_bytes(64.0 * n);
+   double *partial;
+   (void) mass_scratch(2, &partial);
+   const int nb = dot_grid(n);
+   hipLaunchKernelGGL(dscg_step_kernel, dim3(nb), dim3(256), 0, s, a, na, p, d, sv, x, r, n, partial);
+   HIP_CHECK(hipGetLastError());
+   hipLaunchKernelGGL(mass_dot_final_kernel, dim3(2), dim3(256), 0, s, partial, nb, 2, d_out, d_out);
+   HIP_CHECK(hipGetLastError());
+}
+
+// d[0..n) = the diagonal of the n rows (their first entries); *d_flag, a device int the caller has cleared, is raised
+// when a row has no entry
+void launch_pack_first_entries(const int *Ai, const double *Aa, double *d, size_t n, int *d_flag, hipStream_t s)
+{
+   account_bytes(20.0 * n);
+   if (!n) { return; }
+   size_t g = (n + 255) / 256;
+   if (g > 2048) { g = 2048; }
+   hipLaunchKernelGGL(pack_first_entries_kernel, dim3((unsigned) g), dim3(256), 0, s, Ai, Aa, d, n, d_flag);
+   HIP_CHECK(hipGetLastError());
+}
+
+// what the tests need to know of the launch shape: the elements one pass of the dot-product grid covers
+size_t dot_grid_pass_elements() { return (size_t) DOT_BLOCKS * 256 * 2; }
 
 void preload_mass_kernels() { hipFuncAttributes at; (void) hipFuncGetAttributes(&at, (const void *) mass_dot_final_kernel); (void) hipGetLastError(); }
 

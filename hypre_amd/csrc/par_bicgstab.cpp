@@ -26,6 +26,7 @@ struct hypre_amd_BiCGSTABData
    HYPRE_Real tol = 1e-6, a_tol = 0.0, cf_tol = 0.0;
    HYPRE_Int min_iter = 0, max_iter = 1000, stop_crit = 0, logging = 0, print_level = 0;
    HYPRE_Int fused = 1;
+   HYPRE_Int hybrid = 0;                   // -1: the diagonally scaled phase of the hybrid solver (hypre_BiCGSTABSetHybrid)
    KrylovPrecond pc;
    hypre_ParVector *p = nullptr, *q = nullptr, *r = nullptr, *r0 = nullptr, *s = nullptr, *v = nullptr;
    std::vector<HYPRE_Real> norms;          // |r| before the first iteration and after every one, with logging or print_level > 0
@@ -149,6 +150,10 @@ HYPRE_Int hypre_amd_BiCGSTABSetFusedUpdates(HYPRE_Solver s, HYPRE_Int on)
    return hypre_error_flag;
 }
 HYPRE_Int hypre_amd_BiCGSTABGetConverged(HYPRE_Solver s, HYPRE_Int *v) { *v = D(s)->converged; return hypre_error_flag; }
+// the same under the name the other Krylov solvers give it (the reference has hypre_BiCGSTABGetConverged only, krylov.h:1227)
+HYPRE_Int HYPRE_BiCGSTABGetConverged(HYPRE_Solver s, HYPRE_Int *v) { return hypre_amd_BiCGSTABGetConverged(s, v); }
+HYPRE_Int HYPRE_BiCGSTABGetConvergenceFactorTol(HYPRE_Solver s, HYPRE_Real *v) { *v = D(s)->cf_tol; return hypre_error_flag; }
+HYPRE_Int hypre_BiCGSTABSetHybrid(HYPRE_Solver s, HYPRE_Int level) { D(s)->hybrid = level; return hypre_error_flag; }
 HYPRE_Int hypre_amd_BiCGSTABGetLoggedNorms(HYPRE_Solver s, HYPRE_Int *count, const HYPRE_Real **norms)
 {
    *count = (HYPRE_Int) D(s)->norms.size();
@@ -200,7 +205,7 @@ HYPRE_Int HYPRE_ParCSRBiCGSTABSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, H
    HYPRE_Int my_id = 0, iter = 0;
    hypre_MPI_Comm_rank(A->comm, &my_id);
    const bool print = print_level > 0 && my_id == 0;
-   HYPRE_Real alpha, beta, gamma, epsilon, temp, res, r_norm, b_norm, ieee_check = 0., cf_ave_0 = 0.0, cf_ave_1 = 0.0, weight, r_norm_0,
+   HYPRE_Real alpha, beta, gamma, epsilon, temp, res, r_norm, b_norm, ieee_check = 0., cf_ave_0 = 0.0, cf_ave_1 = 0.0, r_norm_0,
               den_norm, gamma_numer, gamma_denom;
    std::vector<HYPRE_Real> &norms = d->norms;
    d->converged = 0;
@@ -326,10 +331,7 @@ HYPRE_Int HYPRE_ParCSRBiCGSTABSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, H
       {
          cf_ave_0 = cf_ave_1;
          cf_ave_1 = std::pow(r_norm / r_norm_0, 1.0 / (2.0 * iter));
-         weight = std::fabs(cf_ave_1 - cf_ave_0);
-         weight = weight / std::max(cf_ave_1, cf_ave_0);
-         weight = 1.0 - weight;
-         if (weight * cf_ave_1 > cf_tol) { break; }
+         if (convergence_factor_exceeds(cf_ave_1, cf_ave_0, cf_tol)) { break; }
       }
       if (std::fabs(res) >= epsmac) { beta = 1.0 / res; }
       else { return broke_down("BiCGSTAB broke down!! res=0 \n"); }
@@ -355,7 +357,7 @@ HYPRE_Int HYPRE_ParCSRBiCGSTABSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, H
    d->num_iterations = iter;
    if (b_norm > 0.0) { d->rel_residual_norm = r_norm / b_norm; }
    if (b_norm == 0.0) { d->rel_residual_norm = r_norm; }
-   if (iter >= max_iter && r_norm > epsilon && epsilon > 0) { hypre_error(HYPRE_ERROR_CONV); }
+   if (iter >= max_iter && r_norm > epsilon && epsilon > 0 && d->hybrid != -1) { hypre_error(HYPRE_ERROR_CONV); }
    return hypre_error_flag;
 }
 

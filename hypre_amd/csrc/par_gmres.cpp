@@ -8,7 +8,8 @@
 // product ending in one scalar read-back, and the entry points (work vectors, preconditioner and the start of a solve
 // as PCG has them: krylov_common.hpp).  The first three differ in the GMRESParams their Create fills in (the table is in DESIGN.md) and in two
 // refusals: COGMRES Setup takes no multivectors, FlexGMRES Solve no host operands (LGMRES Solve neither).  The
-// relative-change and convergence-factor exits of the reference (rel_change, cf_tol) are not carried, by none of the four.
+// relative-change exit of the reference (rel_change) is carried by none of the four, the convergence-factor exit (cf_tol)
+// by GMRES alone, which the hybrid solver drives with it (par_hybrid.cpp).
 //
 // Modified Gram-Schmidt, fused (the FlexGMRES default): step i is one hypre_ParVectorInnerProd and i launches of
 // launch_axpy_dot, each subtracting the projection on p[j] and leaving <p[j + 1], p[i]> (the last one |p[i]|^2) in the
@@ -237,6 +238,15 @@ HYPRE_Int HYPRE_GMRESSetRelChange(HYPRE_Solver s, HYPRE_Int v)
 HYPRE_Int HYPRE_GMRESGetNumIterations(HYPRE_Solver s, HYPRE_Int *v) { *v = D(s)->num_iterations; return hypre_error_flag; }
 HYPRE_Int HYPRE_GMRESGetFinalRelativeResidualNorm(HYPRE_Solver s, HYPRE_Real *v) { *v = D(s)->rel_residual_norm; return hypre_error_flag; }
 HYPRE_Int HYPRE_GMRESGetConverged(HYPRE_Solver s, HYPRE_Int *v) { *v = D(s)->converged; return hypre_error_flag; }
+// gmres.c:597-615, 1016-1035: 0.0 (the default) computes nothing and changes no iteration
+HYPRE_Int HYPRE_GMRESSetConvergenceFactorTol(HYPRE_Solver s, HYPRE_Real v)
+{
+   D(s)->prm.cf_tol = v;
+   D(s)->prm.cf_exit = convergence_factor_exceeds;
+   return hypre_error_flag;
+}
+HYPRE_Int HYPRE_GMRESGetConvergenceFactorTol(HYPRE_Solver s, HYPRE_Real *v) { *v = D(s)->prm.cf_tol; return hypre_error_flag; }
+HYPRE_Int hypre_GMRESSetHybrid(HYPRE_Solver s, HYPRE_Int level) { D(s)->prm.quiet_at_max_iter = level == -1; return hypre_error_flag; }
 
 HYPRE_Int HYPRE_ParCSRGMRESSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x)
 {

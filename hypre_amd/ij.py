@@ -29,6 +29,10 @@ class IJOptions:
                                       # 16 AMG-COGMRES, 17 DS-COGMRES, 60 DS-FlexGMRES, 61 AMG-FlexGMRES
         self.lgmres = 0               # options only: 1 runs LGMRES in place of GMRES, solver 4 as DS-LGMRES (the reference's -solver 50),
                                       # solver 3 as AMG-LGMRES (51)
+        self.hybrid = 0               # options only: 1 runs the hybrid solver (the reference's -solver 20, test/ij.c:4302-4435): a diagonally
+                                      # scaled Krylov solver first, BoomerAMG behind it only if convergence is slower than cf_tol
+        self.hybrid_solver_type = 1   # -solver_type: 1 PCG, 2 GMRES, 3 BiCGSTAB (test/ij.c:140, 1963); read with hybrid = 1 only
+        self.cf_tol = 0.9             # -cf (test/ij.c:157, 1851); read with hybrid = 1 only
         self.neg_a = 0                # -negA 1: solve with -A (test/ij.c:4014-4017)
         self.num_components = 1       # -nc: columns of b and x (multivectors; test/ij.c:874-878, 3400-3404)
         self.k_dim = 5                # -k (GMRES restart length, test/ij.c:1731)
@@ -381,6 +385,15 @@ def check_options(opt):
     (solvers 60 / 61, FlexGMRES, and lgmres = 1, only the latter); returns opt."""
     if opt.solver not in (0, 1, 2, 3, 4, 9, 10, 16, 17, 60, 61):
         raise SystemExit("ij: solver %d is outside the scope of this driver" % opt.solver)
+    if opt.hybrid not in (0, 1) or (opt.hybrid and opt.solver != 0):
+        raise SystemExit("ij: hybrid = %r with solver %d: the hybrid solver is chosen by hybrid = 1 alone, solver stays at its default"
+                         % (opt.hybrid, opt.solver))
+    if not opt.hybrid and (opt.hybrid_solver_type != 1 or opt.cf_tol != 0.9):
+        raise SystemExit("ij: hybrid_solver_type and cf_tol are read by the hybrid solver only (hybrid = 1)")
+    if opt.hybrid and (opt.hybrid_solver_type not in (1, 2, 3) or not 0.0 <= opt.cf_tol <= 1.0):
+        raise SystemExit("ij: hybrid_solver_type is 1 (PCG), 2 (GMRES) or 3 (BiCGSTAB), cf_tol lies in [0, 1]")
+    if opt.hybrid and (opt.num_components > 1 or opt.lgmres):
+        raise SystemExit("ij: the hybrid solver takes one component and no LGMRES")
     if opt.lgmres not in (0, 1) or (opt.lgmres and opt.solver not in (3, 4)):
         raise SystemExit("ij: lgmres = %r with solver %d: LGMRES runs as solver 4 (DS-LGMRES, the reference's 50) or solver 3 "
                          "(AMG-LGMRES, 51)" % (opt.lgmres, opt.solver))
@@ -445,6 +458,8 @@ def run(opt, comm=0, rank=0, nprocs=1, allreduce=None, out=None):
     out = out or sys.stdout
     L = B.load_library()
     A = build_matrix(opt, comm=comm, rank=rank, nprocs=nprocs)
+    if opt.hybrid:
+        return run_hybrid(opt, A, comm=comm, rank=rank, allreduce=allreduce, out=out)
     if opt.solver in (2, 4, 10, 17, 60):
         return run_ds_pcg(opt, A, comm=comm, rank=rank, allreduce=allreduce, out=out)
     s = create_amg(opt, memory_location=DEVICE)
@@ -635,6 +650,91 @@ def run_ds_pcg(opt, A, comm=0, rank=0, allreduce=None, out=None):
         out.write("\n".join(["", "%sIterations = %d" % (tag, its), "Final %sRelative Residual Norm = %e" % (tag, rel), ""]) + "\n")
         out.flush()
     return its, rel
+
+
+def create_hybrid(opt):
+    """test/ij.c:4308-4360: the setter sequence of solver 20, everything the reference driver hands over.  Logging is the
+    driver's ioutdat (3); of its poutdat (1) the Krylov solver's digit is dropped, so that BiCGSTAB prints no table of
+    norms: this driver prints the closing lines alone, as for its other solvers."""
+    L = B.load_library()
+    h = C.c_void_p()
+    L.HYPRE_ParCSRHybridCreate(C.byref(h))
+    L.HYPRE_ParCSRHybridSetTol(h, opt.tol)
+    L.HYPRE_ParCSRHybridSetAbsoluteTol(h, 0.0)
+    L.HYPRE_ParCSRHybridSetConvergenceTol(h, opt.cf_tol)
+    L.HYPRE_ParCSRHybridSetSolverType(h, opt.hybrid_solver_type)
+    L.HYPRE_ParCSRHybridSetRecomputeResidual(h, 0)
+    L.HYPRE_ParCSRHybridSetLogging(h, 3)
+    L.HYPRE_ParCSRHybridSetPrintLevel(h, 0)
+    L.HYPRE_ParCSRHybridSetDSCGMaxIter(h, opt.max_iter)
+    L.HYPRE_ParCSRHybridSetPCGMaxIter(h, opt.mg_max_iter)
+    L.HYPRE_ParCSRHybridSetCoarsenType(h, opt.coarsen_type)
+    L.HYPRE_ParCSRHybridSetStrongThreshold(h, opt.strong_threshold)
+    L.HYPRE_ParCSRHybridSetTruncFactor(h, opt.trunc_factor)
+    L.HYPRE_ParCSRHybridSetPMaxElmts(h, opt.P_max_elmts)
+    L.HYPRE_ParCSRHybridSetMaxLevels(h, opt.max_levels)
+    L.HYPRE_ParCSRHybridSetMaxRowSum(h, opt.max_row_sum)
+    L.HYPRE_ParCSRHybridSetNumSweeps(h, opt.num_sweeps)
+    L.HYPRE_ParCSRHybridSetInterpType(h, opt.interp_type)
+    if opt.relax_type > -1:
+        L.HYPRE_ParCSRHybridSetRelaxType(h, opt.relax_type)
+    L.HYPRE_ParCSRHybridSetAggNumLevels(h, 0)
+    L.HYPRE_ParCSRHybridSetAggInterpType(h, 4)
+    L.HYPRE_ParCSRHybridSetNumPaths(h, 1)
+    L.HYPRE_ParCSRHybridSetNumFunctions(h, opt.num_functions)
+    L.HYPRE_ParCSRHybridSetNodal(h, 0)
+    for k, t in ((1, opt.relax_down), (2, opt.relax_up), (3, opt.relax_coarse)):
+        if t > -1:
+            L.HYPRE_ParCSRHybridSetCycleRelaxType(h, t, k)
+    L.HYPRE_ParCSRHybridSetRelaxOrder(h, opt.relax_order)
+    L.HYPRE_ParCSRHybridSetKeepTranspose(h, opt.keep_transpose)
+    L.HYPRE_ParCSRHybridSetMaxCoarseSize(h, opt.coarse_threshold)
+    L.HYPRE_ParCSRHybridSetMinCoarseSize(h, 0)
+    L.HYPRE_ParCSRHybridSetSeqThreshold(h, 0)
+    L.HYPRE_ParCSRHybridSetRelaxWt(h, opt.relax_wt)
+    L.HYPRE_ParCSRHybridSetOuterWt(h, opt.outer_wt)
+    if opt.level_w is not None:
+        L.HYPRE_ParCSRHybridSetLevelRelaxWt(h, opt.level_w[0], opt.level_w[1])
+    if opt.level_ow is not None:
+        L.HYPRE_ParCSRHybridSetLevelOuterWt(h, opt.level_ow[0], opt.level_ow[1])
+    L.HYPRE_ParCSRHybridSetNonGalerkinTol(h, 0, None)
+    B.check()
+    return h
+
+
+def run_hybrid(opt, A, comm=0, rank=0, allreduce=None, out=None):
+    """hybrid = 1 (the reference's `ij -solver 20 [-cf v] [-solver_type t]`) on the device; the closing lines of
+    test/ij.c:4419-4432.  Returns (iterations, AMG iterations, diagonally scaled iterations, final relative residual norm)."""
+    L = B.load_library()
+    L.hypre_ParCSRMatrixMigrate(A, DEVICE)
+    Am = A.contents
+    first, nglob = int(Am.row_starts[0]), int(Am.global_num_rows)
+    b, x0 = build_rhs_host(opt, A, rank=rank, allreduce=allreduce)
+    if b is None:
+        ones = B.parvec_from_numpy(np.ones(len(x0)), comm=comm, global_size=nglob, first=first)
+        db = B.parvec_from_numpy(np.zeros(len(x0)), comm=comm, global_size=nglob, first=first)
+        L.hypre_ParCSRMatrixMatvec(1.0, A, ones, 0.0, db)
+        L.hypre_ParVectorDestroy(ones)
+    else:
+        db = B.parvec_from_numpy(b, comm=comm, global_size=nglob, first=first)
+    dx = B.parvec_from_numpy(x0, comm=comm, global_size=nglob, first=first)
+    h = create_hybrid(opt)
+    L.HYPRE_ParCSRHybridSetup(h, A, db, dx)
+    L.HYPRE_ParCSRHybridSolve(h, A, db, dx)
+    L.HYPRE_ClearError(256)
+    B.check()
+    its, pcg_its, dscg_its, rel = C.c_int(), C.c_int(), C.c_int(), C.c_double()
+    L.HYPRE_ParCSRHybridGetNumIterations(h, C.byref(its))
+    L.HYPRE_ParCSRHybridGetPCGNumIterations(h, C.byref(pcg_its))
+    L.HYPRE_ParCSRHybridGetDSCGNumIterations(h, C.byref(dscg_its))
+    L.HYPRE_ParCSRHybridGetFinalRelativeResidualNorm(h, C.byref(rel))
+    L.HYPRE_ParCSRHybridDestroy(h)
+    L.hypre_ParVectorDestroy(db); L.hypre_ParVectorDestroy(dx)
+    if rank == 0:
+        out.write("\n".join(["", "Iterations = %d" % its.value, "PCG_Iterations = %d" % pcg_its.value,
+                             "DSCG_Iterations = %d" % dscg_its.value, "Final Relative Residual Norm = %e" % rel.value, ""]) + "\n")
+        out.flush()
+    return its.value, pcg_its.value, dscg_its.value, rel.value
 
 
 def solve_gmres(opt, amg, A, b, x, comm=0):

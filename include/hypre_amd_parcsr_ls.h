@@ -498,6 +498,27 @@ HYPRE_Int HYPRE_ParCSRPCGSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_
 HYPRE_Int HYPRE_ParCSRPCGSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
 HYPRE_Int HYPRE_PCGGetNumIterations(HYPRE_Solver solver, HYPRE_Int *num_iterations);
 HYPRE_Int HYPRE_PCGGetFinalRelativeResidualNorm(HYPRE_Solver solver, HYPRE_Real *norm);
+/* pcg.c:893-950: with cf_tol > 0 the solve gives up, without an error, when the average convergence factor
+ * cf = (i_prod / i_prod_0)^(1 / (2 i)), weighted by 1 - |cf - cf_before| / max(cf, cf_before), exceeds cf_tol; 0 (the
+ * default) computes nothing.  Converged is 1 when the last solve ended by meeting its tolerance: not at the
+ * convergence-factor exit, a breakdown or max_iter (pcg.c:841). */
+HYPRE_Int HYPRE_PCGSetConvergenceFactorTol(HYPRE_Solver solver, HYPRE_Real cf_tol);
+HYPRE_Int HYPRE_PCGGetConvergenceFactorTol(HYPRE_Solver solver, HYPRE_Real *cf_tol);
+HYPRE_Int HYPRE_PCGGetConverged(HYPRE_Solver solver, HYPRE_Int *converged);
+/* Behind HYPRE_ParCSRDiagScale on vectors of one column in device memory, the update of x and r, the diagonal scaling
+ * and the inner product of an iteration are one launch over a copy of the diagonal that Setup packs (64 bytes per
+ * element instead of 92, 2 launches instead of 5); x, r, the iteration count and the norms have the same bits.  Set
+ * before Setup; 1 is the default (measured in DESIGN.md 6b).  The packed diagonal is that of the matrix Setup saw: after changing the values, call Setup again.
+ * GetFusedDiagScaleUsed, valid after Setup: 1 when the solves of this Setup take it; 0 for another preconditioner, a
+ * multivector, host operands or a matrix with a row that has no entry. */
+HYPRE_Int hypre_amd_PCGSetFusedDiagScale(HYPRE_Solver solver, HYPRE_Int on);
+HYPRE_Int hypre_amd_PCGGetFusedDiagScaleUsed(HYPRE_Solver solver, HYPRE_Int *used);
+/* That step on its own, s holding A p on entry: x += alpha p, r -= alpha s, s = r ./ diag(A), rr = <r, r>, rs = <r, s>
+ * over all ranks; fused 1 the one launch, 0 the three it stands for.  The same bits.  hypre_amd_DotGridPassElements: the
+ * elements one trip of its grid covers. */
+HYPRE_Int hypre_amd_ParVectorDiagScaledCGStep(HYPRE_Int fused, HYPRE_Complex alpha, hypre_ParCSRMatrix *A, hypre_ParVector *p,
+                                              hypre_ParVector *s, hypre_ParVector *x, hypre_ParVector *r, HYPRE_Real *rr, HYPRE_Real *rs);
+HYPRE_BigInt hypre_amd_DotGridPassElements(void);
 
 /* ---- GMRES with BoomerAMG as right preconditioner (`ij -solver 3`) ----
  * krylov/gmres.c:274-1000, krylov/HYPRE_gmres.c, parcsr_ls/HYPRE_parcsr_gmres.c; defaults of
@@ -522,6 +543,11 @@ HYPRE_Int HYPRE_ParCSRGMRESSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPR
 HYPRE_Int HYPRE_GMRESGetNumIterations(HYPRE_Solver solver, HYPRE_Int *num_iterations);
 HYPRE_Int HYPRE_GMRESGetFinalRelativeResidualNorm(HYPRE_Solver solver, HYPRE_Real *norm);
 HYPRE_Int HYPRE_GMRESGetConverged(HYPRE_Solver solver, HYPRE_Int *converged);
+/* gmres.c:597-615: the convergence-factor exit as for PCG above, on the norm of the recurrence, looked at after every
+ * step; the correction of the restart cycle under way is not added to x.  GMRES only: COGMRES and LGMRES have no such
+ * setter, FlexGMRES takes 0.0 only. */
+HYPRE_Int HYPRE_GMRESSetConvergenceFactorTol(HYPRE_Solver solver, HYPRE_Real cf_tol);
+HYPRE_Int HYPRE_GMRESGetConvergenceFactorTol(HYPRE_Solver solver, HYPRE_Real *cf_tol);
 
 /* ---- COGMRES: restarted GMRES whose Gram-Schmidt step is batched (`ij -solver 16 | 17`) ----
  * krylov/cogmres.c:274-900, krylov/HYPRE_cogmres.c, parcsr_ls/HYPRE_parcsr_cogmres.c; defaults of hypre_COGMRESCreate
@@ -747,6 +773,83 @@ HYPRE_Int hypre_amd_ParVectorTwoAxpysThenInnerProds(HYPRE_Complex a, hypre_ParVe
                                                     hypre_ParVector *s, hypre_ParVector *r, hypre_ParVector *r0, HYPRE_Real *rr,
                                                     HYPRE_Real *r0r);
 HYPRE_Int hypre_amd_ParVectorAxpyScaleAxpy(HYPRE_Complex g, hypre_ParVector *q, HYPRE_Complex c, hypre_ParVector *r, hypre_ParVector *p);
+/* hypre_amd_BiCGSTABGetConverged under the name the other Krylov solvers use, and the getter of cf_tol */
+HYPRE_Int HYPRE_BiCGSTABGetConverged(HYPRE_Solver solver, HYPRE_Int *converged);
+HYPRE_Int HYPRE_BiCGSTABGetConvergenceFactorTol(HYPRE_Solver solver, HYPRE_Real *cf_tol);
+
+/* ---- Hybrid: diagonal scaling first, BoomerAMG only if convergence is slow (the reference's `ij -solver 20`) ----
+ * parcsr_ls/amg_hybrid.c, parcsr_ls/HYPRE_parcsr_hybrid.c; defaults of hypre_AMGHybridCreate (amg_hybrid.c:99-160): tol 1e-6,
+ * a_tol 0, cf_tol 0.9, dscg_max_its 1000, pcg_max_its 200, solver_type 1, k_dim 5, setup_type 1, logging 0; for the
+ * preconditioner strong_threshold 0.25, max_row_sum 0.9, trunc_factor 0, P_max_elmts 4, max_levels 25, coarsen_type 10,
+ * interp_type 6, cycle_type 1, relax_order 0, keep_transpose 0, max_coarse_size 9, min_coarse_size 1, smoothers 13 / 14 / 9.
+ * Solve (amg_hybrid.c:1770-2310) runs the Krylov solver of solver_type (1 PCG, 2 GMRES, 3 BiCGSTAB) behind
+ * HYPRE_ParCSRDiagScale with the convergence-factor exit cf_tol and dscg_max_its; if it reports converged that is the
+ * answer and no hierarchy is built.  Otherwise cf_tol becomes 0, BoomerAMG is created from the stored options and set
+ * up, and the same solver goes on from the current x with pcg_max_its.  A second Solve builds a new hierarchy unless
+ * SetSetupType(0) was called: then an existing one is kept and the solve starts behind it at once.  The diagonally
+ * scaled PCG phase takes the fused step of hypre_amd_PCGSetFusedDiagScale when that is the default.
+ * Operands are in device memory, one column.  Options the library does not build (AggNumLevels, Nodal, SeqThreshold,
+ * NonGalerkinTol other than 0, ...) are stored and raise the error of the BoomerAMG setter when the preconditioner is
+ * created; RelChange, RecomputeResidual and StopCrit other than 0, and SetPrecond, are refused at once.  Setup does
+ * nothing but look at the operands, as in the reference.  The final norm is stored with Logging > 0 only
+ * (amg_hybrid.c:2073, 2243).  PrintLevel xy: y goes to the Krylov solver, x to BoomerAMG. */
+HYPRE_Int HYPRE_ParCSRHybridCreate(HYPRE_Solver *solver);
+HYPRE_Int HYPRE_ParCSRHybridDestroy(HYPRE_Solver solver);
+HYPRE_Int HYPRE_ParCSRHybridSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_ParCSRHybridSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_ParCSRHybridSetTol(HYPRE_Solver solver, HYPRE_Real tol);
+HYPRE_Int HYPRE_ParCSRHybridSetAbsoluteTol(HYPRE_Solver solver, HYPRE_Real a_tol);
+HYPRE_Int HYPRE_ParCSRHybridSetConvergenceTol(HYPRE_Solver solver, HYPRE_Real cf_tol);
+HYPRE_Int HYPRE_ParCSRHybridSetDSCGMaxIter(HYPRE_Solver solver, HYPRE_Int dscg_max_its);
+HYPRE_Int HYPRE_ParCSRHybridSetPCGMaxIter(HYPRE_Solver solver, HYPRE_Int pcg_max_its);
+HYPRE_Int HYPRE_ParCSRHybridSetSetupType(HYPRE_Solver solver, HYPRE_Int setup_type);
+HYPRE_Int HYPRE_ParCSRHybridSetSolverType(HYPRE_Solver solver, HYPRE_Int solver_type);
+HYPRE_Int HYPRE_ParCSRHybridSetKDim(HYPRE_Solver solver, HYPRE_Int k_dim);
+HYPRE_Int HYPRE_ParCSRHybridSetTwoNorm(HYPRE_Solver solver, HYPRE_Int two_norm);
+HYPRE_Int HYPRE_ParCSRHybridSetStopCrit(HYPRE_Solver solver, HYPRE_Int stop_crit);                  /* 0 only */
+HYPRE_Int HYPRE_ParCSRHybridSetRelChange(HYPRE_Solver solver, HYPRE_Int rel_change);                /* 0 only */
+HYPRE_Int HYPRE_ParCSRHybridSetRecomputeResidual(HYPRE_Solver solver, HYPRE_Int recompute_residual); /* 0 only */
+HYPRE_Int HYPRE_ParCSRHybridGetRecomputeResidual(HYPRE_Solver solver, HYPRE_Int *recompute_residual);
+HYPRE_Int HYPRE_ParCSRHybridSetPrecond(HYPRE_Solver solver, HYPRE_PtrToSolverFcn precond, HYPRE_PtrToSolverFcn precond_setup,
+                                       HYPRE_Solver precond_solver);                                /* refused */
+HYPRE_Int HYPRE_ParCSRHybridSetLogging(HYPRE_Solver solver, HYPRE_Int logging);
+HYPRE_Int HYPRE_ParCSRHybridSetPrintLevel(HYPRE_Solver solver, HYPRE_Int print_level);
+HYPRE_Int HYPRE_ParCSRHybridSetStrongThreshold(HYPRE_Solver solver, HYPRE_Real strong_threshold);
+HYPRE_Int HYPRE_ParCSRHybridSetMaxRowSum(HYPRE_Solver solver, HYPRE_Real max_row_sum);
+HYPRE_Int HYPRE_ParCSRHybridSetTruncFactor(HYPRE_Solver solver, HYPRE_Real trunc_factor);
+HYPRE_Int HYPRE_ParCSRHybridSetPMaxElmts(HYPRE_Solver solver, HYPRE_Int P_max_elmts);
+HYPRE_Int HYPRE_ParCSRHybridSetMaxLevels(HYPRE_Solver solver, HYPRE_Int max_levels);
+HYPRE_Int HYPRE_ParCSRHybridSetMeasureType(HYPRE_Solver solver, HYPRE_Int measure_type);
+HYPRE_Int HYPRE_ParCSRHybridSetCoarsenType(HYPRE_Solver solver, HYPRE_Int coarsen_type);
+HYPRE_Int HYPRE_ParCSRHybridSetInterpType(HYPRE_Solver solver, HYPRE_Int interp_type);
+HYPRE_Int HYPRE_ParCSRHybridSetCycleType(HYPRE_Solver solver, HYPRE_Int cycle_type);
+HYPRE_Int HYPRE_ParCSRHybridSetNumSweeps(HYPRE_Solver solver, HYPRE_Int num_sweeps);
+HYPRE_Int HYPRE_ParCSRHybridSetCycleNumSweeps(HYPRE_Solver solver, HYPRE_Int num_sweeps, HYPRE_Int k);
+HYPRE_Int HYPRE_ParCSRHybridSetRelaxType(HYPRE_Solver solver, HYPRE_Int relax_type);
+HYPRE_Int HYPRE_ParCSRHybridSetCycleRelaxType(HYPRE_Solver solver, HYPRE_Int relax_type, HYPRE_Int k);
+HYPRE_Int HYPRE_ParCSRHybridSetRelaxOrder(HYPRE_Solver solver, HYPRE_Int relax_order);
+HYPRE_Int HYPRE_ParCSRHybridSetKeepTranspose(HYPRE_Solver solver, HYPRE_Int keepT);
+HYPRE_Int HYPRE_ParCSRHybridSetMaxCoarseSize(HYPRE_Solver solver, HYPRE_Int max_coarse_size);
+HYPRE_Int HYPRE_ParCSRHybridSetMinCoarseSize(HYPRE_Solver solver, HYPRE_Int min_coarse_size);
+HYPRE_Int HYPRE_ParCSRHybridSetSeqThreshold(HYPRE_Solver solver, HYPRE_Int seq_threshold);
+HYPRE_Int HYPRE_ParCSRHybridSetRelaxWt(HYPRE_Solver solver, HYPRE_Real relax_wt);
+HYPRE_Int HYPRE_ParCSRHybridSetOuterWt(HYPRE_Solver solver, HYPRE_Real outer_wt);
+HYPRE_Int HYPRE_ParCSRHybridSetLevelRelaxWt(HYPRE_Solver solver, HYPRE_Real relax_wt, HYPRE_Int level);
+HYPRE_Int HYPRE_ParCSRHybridSetLevelOuterWt(HYPRE_Solver solver, HYPRE_Real outer_wt, HYPRE_Int level);
+HYPRE_Int HYPRE_ParCSRHybridSetNumPaths(HYPRE_Solver solver, HYPRE_Int num_paths);
+HYPRE_Int HYPRE_ParCSRHybridSetAggNumLevels(HYPRE_Solver solver, HYPRE_Int agg_num_levels);
+HYPRE_Int HYPRE_ParCSRHybridSetAggInterpType(HYPRE_Solver solver, HYPRE_Int agg_interp_type);
+HYPRE_Int HYPRE_ParCSRHybridSetNumFunctions(HYPRE_Solver solver, HYPRE_Int num_functions);
+HYPRE_Int HYPRE_ParCSRHybridSetNodal(HYPRE_Solver solver, HYPRE_Int nodal);
+HYPRE_Int HYPRE_ParCSRHybridSetNonGalerkinTol(HYPRE_Solver solver, HYPRE_Int num_levels, HYPRE_Real *nongalerkin_tol);
+HYPRE_Int HYPRE_ParCSRHybridGetNumIterations(HYPRE_Solver solver, HYPRE_Int *num_its);             /* both phases */
+HYPRE_Int HYPRE_ParCSRHybridGetDSCGNumIterations(HYPRE_Solver solver, HYPRE_Int *dscg_num_its);
+HYPRE_Int HYPRE_ParCSRHybridGetPCGNumIterations(HYPRE_Solver solver, HYPRE_Int *pcg_num_its);
+HYPRE_Int HYPRE_ParCSRHybridGetFinalRelativeResidualNorm(HYPRE_Solver solver, HYPRE_Real *norm);
+HYPRE_Int HYPRE_ParCSRHybridGetSetupSolveTime(HYPRE_Solver solver, HYPRE_Real *time);              /* 4 values: setup 1, solve 1, setup 2, solve 2 */
+/* the hierarchy (null while no solve has needed one) and the Krylov solver the hybrid solver keeps; they stay its own */
+HYPRE_Int hypre_amd_ParCSRHybridGetPrecond(HYPRE_Solver solver, HYPRE_Solver *amg);
+HYPRE_Int hypre_amd_ParCSRHybridGetKrylovSolver(HYPRE_Solver solver, HYPRE_Solver *krylov);
 
 #ifdef __cplusplus
 }
