@@ -26,7 +26,7 @@ class IJOptions:
         self.c = (1.0, 1.0, 1.0)      # -c cx cy cz
         self.a = (1.0, 1.0, 1.0)      # -a ax ay az (difconv)
         self.solver = 0               # 0 AMG, 1 AMG-PCG, 2 DS-PCG (diagonal scaling), 3 AMG-GMRES, 4 DS-GMRES, 9 AMG-BiCGSTAB, 10 DS-BiCGSTAB,
-                                      # 16 AMG-COGMRES, 17 DS-COGMRES, 60 DS-FlexGMRES, 61 AMG-FlexGMRES
+                                      # 16 AMG-COGMRES, 17 DS-COGMRES, 60 DS-FlexGMRES, 61 AMG-FlexGMRES, 80 ILU, 81 ILU-GMRES, 82 ILU-FlexGMRES
         self.lgmres = 0               # options only: 1 runs LGMRES in place of GMRES, solver 4 as DS-LGMRES (the reference's -solver 50),
                                       # solver 3 as AMG-LGMRES (51)
         self.hybrid = 0               # options only: 1 runs the hybrid solver (the reference's -solver 20, test/ij.c:4302-4435): a diagonally
@@ -79,6 +79,11 @@ class IJOptions:
         self.cheby_variant = 0        # -cheby_variant
         self.cheby_scale = 1          # -cheby_scale
         self.cheby_fraction = 0.3     # -cheby_fraction
+        self.ilu_type = 0             # -ilu_type       (test/ij.c:447-457 defaults); 0, block Jacobi with ILU(k), is what this driver serves
+        self.ilu_lfil = 0             # -ilu_lfil       level of fill k
+        self.ilu_reordering = 1       # -ilu_reordering 0 none, 1 reverse Cuthill-McKee on the diagonal block
+        self.ilu_tri_solve = 1        # -ilu_tri_solve  1 direct triangular solves (0, iterative, is refused)
+        self.ilu_sm_max_iter = 1      # -ilu_sm_max_iter: sweeps of ILU as a BoomerAMG smoother (-smtype 5, refused): accepted, no effect
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise TypeError("unknown ij option %r" % k)
@@ -321,6 +326,9 @@ _VALUE_FLAGS = {
     "-cheby_order": ("cheby_order", int, 1), "-cheby_eig_est": ("cheby_eig_est", int, 1),
     "-cheby_variant": ("cheby_variant", int, 1), "-cheby_scale": ("cheby_scale", int, 1),
     "-cheby_fraction": ("cheby_fraction", float, 1),
+    "-ilu_type": ("ilu_type", int, 1), "-ilu_lfil": ("ilu_lfil", int, 1), "-ilu_reordering": ("ilu_reordering", int, 1),
+    "-ilu_tri_solve": ("ilu_tri_solve", int, 1), "-ilu_trisolve": ("ilu_tri_solve", int, 1),    # the reference parses the second spelling, its help shows the first
+    "-ilu_sm_max_iter": ("ilu_sm_max_iter", int, 1),
     "-n": ("n", int, 3), "-P": ("P", int, 3), "-c": ("c", float, 3), "-a": ("a", float, 3),
     # extensions of this driver (no reference counterpart)
     "-amd_threads": ("num_threads", int, 1),
@@ -366,13 +374,18 @@ def parse_cli(argv):
             if lev > -1:        # test/ij.c:4543-4550 applies the level weight only for level > -1
                 setattr(opt, "level_w" if flag == "-wl" else "level_ow", (val, lev))
             i += 3
+        elif flag.startswith("-ilu_"):
+            # -ilu_droptol, -ilu_max_row_nnz (ILUT), -ilu_schur_max_iter, -ilu_nsh_droptol (Schur types), -ilu_ljac_iters,
+            # -ilu_ujac_iters (iterative triangular solves), -ilu_iter_setup_* (iterative setup)
+            raise SystemExit("ij: option %s is outside the scope of this driver (ILU: -ilu_type 0, -ilu_lfil, -ilu_reordering, "
+                             "-ilu_tri_solve 1, -ilu_sm_max_iter)" % flag)
         else:
             raise SystemExit("ij: option %s is outside the scope of this driver" % flag)
-    if opt.solver not in (0, 1, 2, 3, 4, 9, 10, 16, 17):
+    if opt.solver not in (0, 1, 2, 3, 4, 9, 10, 16, 17, 80, 81, 82):
         # FlexGMRES (60 DS, 61 AMG) is served by run() for options built in code, but the command line keeps refusing the
         # two ids: tests/test_cogmres_cli.py pins them as outside its scope
         raise SystemExit("ij: -solver %d is outside the scope of this driver (0 AMG, 1 AMG-PCG, 2 DS-PCG, 3 AMG-GMRES, 4 DS-GMRES, "
-                         "9 AMG-BiCGSTAB, 10 DS-BiCGSTAB, 16 AMG-COGMRES, 17 DS-COGMRES)" % opt.solver)
+                         "9 AMG-BiCGSTAB, 10 DS-BiCGSTAB, 16 AMG-COGMRES, 17 DS-COGMRES, 80 ILU, 81 ILU-GMRES, 82 ILU-FlexGMRES)" % opt.solver)
     if opt.interp_type not in (6, 3):
         # extended (14) and ext+i-if-no-common-C (7) are served by run() for options built in code; the command line keeps
         # refusing them: tests/test_ij_cli.py pins -interptype 7 as outside its scope
@@ -383,8 +396,17 @@ def parse_cli(argv):
 def check_options(opt):
     """The combinations of options this driver serves, whether they came from the command line or were set in code
     (solvers 60 / 61, FlexGMRES, and lgmres = 1, only the latter); returns opt."""
-    if opt.solver not in (0, 1, 2, 3, 4, 9, 10, 16, 17, 60, 61):
+    if opt.solver not in (0, 1, 2, 3, 4, 9, 10, 16, 17, 60, 61, 80, 81, 82):
         raise SystemExit("ij: solver %d is outside the scope of this driver" % opt.solver)
+    if opt.ilu_type != 0:
+        raise SystemExit("ij: -ilu_type %d is outside the scope of this driver (0: block Jacobi with ILU(k); ILUT and the Schur, NSH, "
+                         "RAS, ddPQ and RAP types are not served)" % opt.ilu_type)
+    if opt.ilu_tri_solve != 1:
+        raise SystemExit("ij: -ilu_tri_solve %d is outside the scope of this driver (1: direct triangular solves)" % opt.ilu_tri_solve)
+    if opt.ilu_lfil < 0 or opt.ilu_reordering not in (0, 1):
+        raise SystemExit("ij: -ilu_lfil takes a level of fill >= 0, -ilu_reordering 0 (none) or 1 (reverse Cuthill-McKee)")
+    if opt.solver in (80, 81, 82) and (opt.num_components > 1 or opt.lgmres or opt.hybrid):
+        raise SystemExit("ij: -solver %d (ILU) takes one component, and neither LGMRES nor the hybrid solver" % opt.solver)
     if opt.hybrid not in (0, 1) or (opt.hybrid and opt.solver != 0):
         raise SystemExit("ij: hybrid = %r with solver %d: the hybrid solver is chosen by hybrid = 1 alone, solver stays at its default"
                          % (opt.hybrid, opt.solver))
@@ -462,6 +484,8 @@ def run(opt, comm=0, rank=0, nprocs=1, allreduce=None, out=None):
         return run_hybrid(opt, A, comm=comm, rank=rank, allreduce=allreduce, out=out)
     if opt.solver in (2, 4, 10, 17, 60):
         return run_ds_pcg(opt, A, comm=comm, rank=rank, allreduce=allreduce, out=out)
+    if opt.solver in (80, 81, 82):
+        return run_ilu(opt, A, comm=comm, rank=rank, allreduce=allreduce, out=out)
     s = create_amg(opt, memory_location=DEVICE)
     L.HYPRE_BoomerAMGSetup(s, A, None, None)
     B.check()
@@ -573,11 +597,12 @@ def solve_ds_pcg(opt, A, db, dx, comm=0):
     return its.value, rel.value
 
 
-def _solve_gmres_family(name, opt, A, b, x, comm, amg, early=(), late=(), amg_first=False, amg_max_iter=None, check_precond=False):
+def _solve_gmres_family(name, opt, A, b, x, comm, amg, early=(), late=(), amg_first=False, amg_max_iter=None, check_precond=False, ilu=None):
     """Create, set, Setup, Solve, read back and Destroy one HYPRE_ParCSR<name> solver (GMRES, COGMRES, FlexGMRES, LGMRES), in the
     order of library calls the reference driver makes: KDim, the `early` setters, MaxIter, Tol, AbsoluteTol, the `late`
     setters; then BoomerAMG (`amg`, tuned as a preconditioner: SetTol 0, SetMaxIter precon_cycles; before Create if
-    `amg_first`, MaxIter set once more to `amg_max_iter` if given) or the diagonal scaling preconditioner."""
+    `amg_first`, MaxIter set once more to `amg_max_iter` if given), the ILU object `ilu` (HYPRE_ILUSolve / HYPRE_ILUSetup) or the
+    diagonal scaling preconditioner."""
     L = B.load_library()
     fn = lambda stem: getattr(L, "HYPRE_%s%s" % (name, stem))
     par = lambda stem: getattr(L, "HYPRE_ParCSR%s%s" % (name, stem))
@@ -597,12 +622,14 @@ def _solve_gmres_family(name, opt, A, b, x, comm, amg, early=(), late=(), amg_fi
         if amg_max_iter is not None:
             fn("SetMaxIter")(g, amg_max_iter)
         fn("SetPrecond")(g, C.cast(L.HYPRE_BoomerAMGSolve, C.c_void_p), None, amg)
+    elif ilu is not None:
+        fn("SetPrecond")(g, C.cast(L.HYPRE_ILUSolve, C.c_void_p), C.cast(L.HYPRE_ILUSetup, C.c_void_p), ilu)
     else:
         fn("SetPrecond")(g, C.cast(L.HYPRE_ParCSRDiagScale, C.c_void_p), C.cast(L.HYPRE_ParCSRDiagScaleSetup, C.c_void_p), None)
     if check_precond:
         gotten = C.c_void_p()
         fn("GetPrecond")(g, C.byref(gotten))
-        if gotten.value != (amg.value if amg is not None else None):
+        if gotten.value != (amg.value if amg is not None else ilu.value if ilu is not None else None):
             raise SystemExit("HYPRE_%sGetPrecond got bad precond" % name)
     par("Setup")(g, A, b, x)
     par("Solve")(g, A, b, x)
@@ -648,6 +675,73 @@ def run_ds_pcg(opt, A, comm=0, rank=0, allreduce=None, out=None):
     if rank == 0:
         tag = {4: "LGMRES " if opt.lgmres else "GMRES ", 10: "BiCGSTAB ", 17: "COGMRES ", 60: "FlexGMRES "}.get(opt.solver, "")
         out.write("\n".join(["", "%sIterations = %d" % (tag, its), "Final %sRelative Residual Norm = %e" % (tag, rel), ""]) + "\n")
+        out.flush()
+    return its, rel
+
+
+def create_ilu(opt, preconditioner=False):
+    """test/ij.c:9210-9233 (solver 80) and :7162-7186, 7861-7883 (the preconditioner of 81 / 82: one application, tolerance 0)
+    as far as block-Jacobi ILU(k) has parameters.  The reference driver asks solver 80 for print level 2, the solver's own
+    table; this one prints the closing lines alone, as for its other solvers."""
+    L = B.load_library()
+    s = C.c_void_p()
+    L.HYPRE_ILUCreate(C.byref(s))
+    L.HYPRE_ILUSetType(s, opt.ilu_type)
+    L.HYPRE_ILUSetLevelOfFill(s, opt.ilu_lfil)
+    L.HYPRE_ILUSetLocalReordering(s, opt.ilu_reordering)
+    L.HYPRE_ILUSetTriSolve(s, opt.ilu_tri_solve)
+    L.HYPRE_ILUSetPrintLevel(s, 0)
+    L.HYPRE_ILUSetMaxIter(s, 1 if preconditioner else opt.max_iter)
+    L.HYPRE_ILUSetTol(s, 0.0 if preconditioner else opt.tol)
+    B.check()
+    return s
+
+
+def run_ilu(opt, A, comm=0, rank=0, allreduce=None, out=None, memory_location=DEVICE):
+    """`ij -solver 80 | 81 | 82`: ILU alone (test/ij.c:9204-9286), ILU-GMRES (:6710-6727, 7156-7195) and ILU-FlexGMRES
+    (:7565-7578, 7855-7890).  memory_location HOST runs solver 80 on the library's host path (the Krylov solvers have none)."""
+    import sys
+    out = out or sys.stdout
+    L = B.load_library()
+    if memory_location == DEVICE:
+        L.hypre_ParCSRMatrixMigrate(A, DEVICE)
+    elif opt.solver != 80:
+        raise SystemExit("ij: -solver %d in host memory: the Krylov solvers run on the device only" % opt.solver)
+    Am = A.contents
+    first, nglob = int(Am.row_starts[0]), int(Am.global_num_rows)
+    b, x0 = build_rhs_host(opt, A, rank=rank, allreduce=allreduce)
+    vec = lambda v: B.parvec_from_numpy(v, comm=comm, global_size=nglob, first=first, location=memory_location)
+    if b is None:
+        if memory_location != DEVICE:
+            raise SystemExit("ij: -xisone needs a product with A, which runs on the device only")
+        ones, db = vec(np.ones(len(x0))), vec(np.zeros(len(x0)))
+        L.hypre_ParCSRMatrixMatvec(1.0, A, ones, 0.0, db)
+        L.hypre_ParVectorDestroy(ones)
+    else:
+        db = vec(b)
+    dx = vec(x0)
+    ilu = create_ilu(opt, preconditioner=opt.solver != 80)
+    if opt.solver == 80:
+        L.HYPRE_ILUSetup(ilu, A, db, dx)
+        L.HYPRE_ILUSolve(ilu, A, db, dx)
+        its, rel = C.c_int(), C.c_double()
+        L.HYPRE_ILUGetNumIterations(ilu, C.byref(its))
+        L.HYPRE_ILUGetFinalRelativeResidualNorm(ilu, C.byref(rel))
+        its, rel = its.value, rel.value
+        lines = ["", "hypre_ILU Iterations = %d" % its, "Final Relative Residual Norm = %e" % rel, ""]
+    elif opt.solver == 81:
+        its, rel = _solve_gmres_family("GMRES", opt, A, db, dx, comm, None, ilu=ilu)
+        lines = ["", "GMRES Iterations = %d" % its, "Final GMRES Relative Residual Norm = %e" % rel, ""]
+    else:
+        its, rel = _solve_gmres_family("FlexGMRES", opt, A, db, dx, comm, None, late=(("Logging", 1), ("PrintLevel", 3)), check_precond=True,
+                                       ilu=ilu)
+        lines = ["", "FlexGMRES Iterations = %d" % its, "Final FlexGMRES Relative Residual Norm = %e" % rel, ""]
+    L.HYPRE_ClearError(256)
+    B.check()
+    L.HYPRE_ILUDestroy(ilu)
+    L.hypre_ParVectorDestroy(db); L.hypre_ParVectorDestroy(dx)
+    if rank == 0:
+        out.write("\n".join(lines) + "\n")
         out.flush()
     return its, rel
 

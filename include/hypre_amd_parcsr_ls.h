@@ -851,6 +851,58 @@ HYPRE_Int HYPRE_ParCSRHybridGetSetupSolveTime(HYPRE_Solver solver, HYPRE_Real *t
 HYPRE_Int hypre_amd_ParCSRHybridGetPrecond(HYPRE_Solver solver, HYPRE_Solver *amg);
 HYPRE_Int hypre_amd_ParCSRHybridGetKrylovSolver(HYPRE_Solver solver, HYPRE_Solver *krylov);
 
+/* ---- ILU: block-Jacobi ILU(k), a solver and a preconditioner (the reference's `ij -solver 80 | 81 | 82`, -ilu_type 0) ----
+ * parcsr_ls/HYPRE_parcsr_ilu.c, par_ilu.c, par_ilu_setup.c, par_ilu_solve.c; defaults of hypre_ILUCreate (par_ilu.c:61-106):
+ * ilu_type 0, level of fill 0, local reordering 1 (reverse Cuthill-McKee), tri_solve 1 (direct), max_iter 20, tol 1e-7,
+ * print level 0, logging 0.  Every rank factors its diagonal block; couplings to other ranks are dropped in the factors
+ * and appear only in the residual product with A.  Setup orders, factors (unit L, inverse D, U in the permuted order;
+ * a pivot below 1e-14 in magnitude becomes 1e-6) and computes the dependency levels of L and U on the host, whatever
+ * memory A is in; the factors travel to the device in level order when A is there, or with the first Solve on device
+ * vectors.  Solve (hypre_ILUSolve) iterates  u += (L D^-1 U)^-1 (f - A u)  until the relative residual norm is below tol,
+ * at least once and at most max_iter times (HYPRE_ERROR_CONV at max_iter with tol > 0); a zero right-hand side gives
+ * u = 0; with tol 0 and print level and logging at most 1 (a preconditioner) no norm is computed.  Setup and Solve have
+ * the HYPRE_PtrToSolverFcn signature: hand them to any *SetPrecond.  A, f and u lie all in device memory (level-scheduled
+ * kernels) or all in host memory (the host solve, which the kernels reproduce bit for bit); one column.
+ * Outside the scope, refused by the setter: ilu_type other than 0 (ILUT, Schur-GMRES, NSH, RAS, ddPQ, RAP), tri_solve 0
+ * (iterative triangular solves).  Iterative setup and ILU as a BoomerAMG smoother have no entry point. */
+HYPRE_Int HYPRE_ILUCreate(HYPRE_Solver *solver);
+HYPRE_Int HYPRE_ILUDestroy(HYPRE_Solver solver);
+HYPRE_Int HYPRE_ILUSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_ILUSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
+HYPRE_Int HYPRE_ILUSetType(HYPRE_Solver solver, HYPRE_Int ilu_type);                    /* 0 only */
+HYPRE_Int HYPRE_ILUSetLevelOfFill(HYPRE_Solver solver, HYPRE_Int lfil);
+HYPRE_Int HYPRE_ILUSetLocalReordering(HYPRE_Solver solver, HYPRE_Int reordering_type);   /* 0 none, 1 RCM */
+HYPRE_Int HYPRE_ILUSetTriSolve(HYPRE_Solver solver, HYPRE_Int tri_solve);               /* 1 only */
+HYPRE_Int HYPRE_ILUSetMaxIter(HYPRE_Solver solver, HYPRE_Int max_iter);
+HYPRE_Int HYPRE_ILUSetTol(HYPRE_Solver solver, HYPRE_Real tol);
+HYPRE_Int HYPRE_ILUSetPrintLevel(HYPRE_Solver solver, HYPRE_Int print_level);
+HYPRE_Int HYPRE_ILUSetLogging(HYPRE_Solver solver, HYPRE_Int logging);
+HYPRE_Int HYPRE_ILUGetNumIterations(HYPRE_Solver solver, HYPRE_Int *num_iterations);
+HYPRE_Int HYPRE_ILUGetFinalRelativeResidualNorm(HYPRE_Solver solver, HYPRE_Real *res_norm);
+/* the parameters as they stand (a new object: the defaults above); any pointer may be NULL */
+HYPRE_Int hypre_amd_ILUGetParameters(HYPRE_Solver solver, HYPRE_Int *ilu_type, HYPRE_Int *lfil, HYPRE_Int *reordering, HYPRE_Int *tri_solve,
+                                     HYPRE_Int *max_iter, HYPRE_Real *tol, HYPRE_Int *print_level, HYPRE_Int *logging);
+/* Levels of L and of U, the launches of the last application by kernel form (run: one workgroup sweeps consecutive levels
+ * of at most 1024 rows; level: a grid for one wider level; both factors together; 0 after a host solve) and the entries
+ * of L and U.  Host counters; any pointer may be NULL. */
+HYPRE_Int hypre_amd_ILUGetSolveStats(HYPRE_Solver solver, HYPRE_Int *levels_L, HYPRE_Int *levels_U, HYPRE_Int *run_launches,
+                                     HYPRE_Int *level_launches, HYPRE_Int *nnz_L, HYPRE_Int *nnz_U);
+/* The two triangular solves alone, u += (L D^-1 U)^-1 f without the product with A, in the memory f and u lie in (device
+ * vectors: after a Setup with A in device memory or a Solve on device vectors).  The kernels reproduce the host solve bit
+ * for bit; the residual product of a Solve is summed in another order on the device than on the host. */
+HYPRE_Int hypre_amd_ILUApplyFactors(HYPRE_Solver solver, HYPRE_ParVector f, HYPRE_ParVector u);
+/* The residual f - A u that the last application on the device started from: the solver's own device vector (NULL before
+ * the factors are on the device).  With hypre_amd_ILUApplyFactors on host vectors a test can repeat every application of a
+ * device Solve on the host from the device's own residual. */
+HYPRE_Int hypre_amd_ILUGetResidual(HYPRE_Solver solver, HYPRE_ParVector *residual);
+/* The factors of the last Setup on the host, in the permuted numbering (row ii is row perm[ii] of A): unit L strictly
+ * lower with ascending columns, U strictly upper, D the inverse pivots.  The arrays stay the solver's. */
+HYPRE_Int hypre_amd_ILUGetFactors(HYPRE_Solver solver, HYPRE_Int *n, const HYPRE_Int **perm, const HYPRE_Int **L_i, const HYPRE_Int **L_j,
+                                  const HYPRE_Real **L_data, const HYPRE_Real **D_inv, const HYPRE_Int **U_i, const HYPRE_Int **U_j,
+                                  const HYPRE_Real **U_data);
+/* hypre_ILUGetLocalPerm on its own: perm[new] = old for an n x n pattern in host memory */
+HYPRE_Int hypre_amd_ILULocalRCM(HYPRE_Int n, const HYPRE_Int *A_i, const HYPRE_Int *A_j, HYPRE_Int *perm);
+
 #ifdef __cplusplus
 }
 #endif
