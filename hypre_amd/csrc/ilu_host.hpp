@@ -1,10 +1,10 @@
 // hypre_amd — block-Jacobi ILU(k) on the host: the local reverse Cuthill-McKee ordering, the symbolic and the numeric
-// factorisation of a rank's diagonal block, the two triangular solves, and the dependency levels the device solve runs by
-// (par_ilu.cpp, ilu_kernels.hip).  Plain C++ on plain arrays: tests/host/ilu_host_check.cpp builds it on its own.
+// factorisation of a rank's diagonal block, the two triangular solves (direct, and as Jacobi sweeps), the dependency levels the direct device solve runs by
+// and the row slices the device sweeps read (par_ilu.cpp, ilu_kernels.hip, ilu_iter_kernels.hip).  Plain C++ on plain arrays: tests/host/ilu_host_check.cpp builds it on its own.
 //
 // Reference: parcsr_ls/par_ilu.c:2121-2999 (hypre_ILUGetLocalPerm, hypre_ILULocalRCM*), par_ilu_setup.c:2171-2517
 // (hypre_ILUSetupILU0), :2872-3114 (hypre_ILUSetupILUKSymbolic), :3299-3583 (hypre_ILUSetupILUK), par_ilu_solve.c:829-950
-// (hypre_ILUSolveLU).  Factors live in the permuted numbering: row ii of L, D and U is row perm[ii] of A.
+// (hypre_ILUSolveLU), :960-1110 (hypre_ILUSolveLUIter).  Factors live in the permuted numbering: row ii of L, D and U is row perm[ii] of A.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -287,6 +287,40 @@ inline void solve(const Factors &F, const double *ftemp, double *utemp)
    }
 }
 
+// ---- iterative triangular solves (hypre_ILUSolveLUIter, par_ilu_solve.c:960-1110): each exact solve replaced by a fixed
+// number of Jacobi sweeps from a zero iterate.  ztemp = the last upper iterate of
+//    y^k_i = ftemp_i - sum_j L_ij y^(k-1)_j   (k = 1 .. lower),    z^k_i = Dinv_i (y_i - sum_j U_ij z^(k-1)_j)   (k = 1 .. upper)
+// through the permutation; utemp holds y.  The update is in place, but L's rows run last to first and U's first to last, so a
+// row reads values of the sweep before only: Jacobi, not Gauss-Seidel.  THE association of this path, which the device sweep
+// runs one lane per row: the sum starts at +0.0, the products are added one by one in stored order, every product and every
+// sum rounded, then the difference (and the product with the inverse pivot).  Without a lower or without an upper sweep z is
+// zero and the caller leaves u as it is.
+inline void solve_iter(const Factors &F, const double *ftemp, double *utemp, double *ztemp, int lower, int upper)
+{
+   const int n = F.n;
+   const int *perm = F.perm.data();
+   for (int i = 0; i < n; i++) { utemp[perm[i]] = 0.0; ztemp[perm[i]] = 0.0; }
+   if (lower <= 0 || upper <= 0) { return; }
+   for (int kk = 0; kk < lower; kk++)
+   {
+      for (int i = n - 1; i >= 0; i--)
+      {
+         double sum = 0.0;
+         for (int j = F.Li[(size_t) i]; j < F.Li[(size_t) i + 1]; j++) { sum += F.La[(size_t) j] * utemp[perm[F.Lj[(size_t) j]]]; }
+         utemp[perm[i]] = ftemp[perm[i]] - sum;
+      }
+   }
+   for (int kk = 0; kk < upper; kk++)
+   {
+      for (int i = 0; i < n; i++)
+      {
+         double sum = 0.0;
+         for (int j = F.Ui[(size_t) i]; j < F.Ui[(size_t) i + 1]; j++) { sum += F.Ua[(size_t) j] * ztemp[perm[F.Uj[(size_t) j]]]; }
+         ztemp[perm[i]] = F.D[(size_t) i] * (utemp[perm[i]] - sum);
+      }
+   }
+}
+
 // ---- dependency levels of a triangular factor and its rows in level order ----
 // T is L (forward: a row waits for the rows its columns name, all before it) or U (backward: all after it).
 // order[lev_start[l] .. lev_start[l + 1]) are the rows of level l, ascending inside a level.
@@ -310,6 +344,58 @@ inline void build_levels(int n, const int *Ti, const int *Tj, bool forward, Leve
    std::vector<int> pos(V.lev_start.begin(), V.lev_start.end());
    V.order.assign((size_t) n, 0);
    for (int i = 0; i < n; i++) { V.order[(size_t) pos[(size_t) level[(size_t) i]]++] = i; }
+}
+
+// ---- a factor in row slices, the form the device sweeps read ----
+// 64 consecutive slots of `order` (the level order: neighbouring rows have alike lengths) make a slice, one per wave.  Inside
+// a slice the entries lie entry-major: entry k of lane l at base[slice] + 64 k + l, every row in its stored order, the slice
+// as long as its longest row.  len[] stops a short row at its own length: the padding behind it (column 0, value 0) is never
+// read, let alone multiplied.  The permutation is folded into row[] and col[]; slots past the last row carry row -1.
+constexpr int SLICE_ROWS = 64;
+struct Slices
+{
+   int nslices = 0;
+   long long padded = 0;                     // entries of all slices, padding included
+   std::vector<long long> base;              // [nslices] first entry of the slice
+   std::vector<int> len, row;                // [64 nslices]
+   std::vector<double> dinv;                 // [64 nslices] inverse pivot of the slot's row
+   std::vector<int> col;                     // [padded]
+   std::vector<double> val;                  // [padded]
+};
+inline void build_slices(const Factors &F, const std::vector<int> &order, const std::vector<int> &Ti, const std::vector<int> &Tj,
+                         const std::vector<double> &Ta, Slices &M)
+{
+   const int n = F.n;
+   M.nslices = (n + SLICE_ROWS - 1) / SLICE_ROWS;
+   const size_t slots = (size_t) M.nslices * SLICE_ROWS;
+   M.base.assign((size_t) M.nslices, 0);
+   M.len.assign(slots, 0); M.row.assign(slots, -1); M.dinv.assign(slots, 0.0);
+   M.padded = 0;
+   for (int s = 0; s < M.nslices; s++)
+   {
+      int longest = 0;
+      for (int l = 0; l < SLICE_ROWS && s * SLICE_ROWS + l < n; l++)
+      {
+         const int r = order[(size_t) s * SLICE_ROWS + (size_t) l];
+         longest = std::max(longest, Ti[(size_t) r + 1] - Ti[(size_t) r]);
+      }
+      M.base[(size_t) s] = M.padded;
+      M.padded += (long long) longest * SLICE_ROWS;
+   }
+   M.col.assign((size_t) M.padded, 0); M.val.assign((size_t) M.padded, 0.0);
+   for (int t = 0; t < n; t++)
+   {
+      const int r = order[(size_t) t], s = t / SLICE_ROWS, l = t % SLICE_ROWS, first = Ti[(size_t) r];
+      M.row[(size_t) t] = F.perm[(size_t) r];
+      M.len[(size_t) t] = Ti[(size_t) r + 1] - first;
+      M.dinv[(size_t) t] = F.D[(size_t) r];
+      for (int k = 0; k < M.len[(size_t) t]; k++)
+      {
+         const size_t at = (size_t) M.base[(size_t) s] + (size_t) k * SLICE_ROWS + (size_t) l;
+         M.col[at] = F.perm[(size_t) Tj[(size_t) first + (size_t) k]];
+         M.val[at] = Ta[(size_t) first + (size_t) k];
+      }
+   }
 }
 
 }  // namespace ilu

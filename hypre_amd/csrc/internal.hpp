@@ -434,7 +434,7 @@ void launch_mc_small_sweep(int num_colors, int direction, const int *cstart, con
 // one per kernel file: loads its code object (runtime.cpp: ensure_device)
 void preload_cheby_kernels(); void preload_gs_kernels(); void preload_interp_kernels(); void preload_vector_kernels();
 void preload_rap_kernels(); void preload_setup_kernels(); void preload_spmv_kernels(); void preload_mass_kernels();
-void preload_ilu_kernels();
+void preload_ilu_kernels(); void preload_ilu_iter_kernels();
 // setup_kernels.hip: strength of connection, PMIS, coarse numbering and smoother diagonals of a single-rank level
 void device_strength(int n, const int *Ai, const int *Aj, const double *Aa, double theta, double max_row_sum,
                      int **Si_out, int **Sj_out, int *nnz_out, hipStream_t s);

@@ -9,6 +9,11 @@
 // and the last two steps are the launches of ilu_kernels.hip: a grid for a level wider than a workgroup, one workgroup
 // with a barrier per level for a run of narrower ones.  Objects in host memory are served by the host solve, which the
 // device reproduces bit for bit.  The reference's own device path hands factorisation and solves to rocSPARSE.
+//
+// With hypre_amd_ILUSetIterativeTriSolve on (the reference's tri_solve 0, hypre_ILUSolveLUIter) each triangular solve is a
+// fixed number of Jacobi sweeps from a zero iterate.  The factors then lie in row slices as well (ilu_host.hpp: Slices) and
+// an application is at most lower + upper launches of ilu_iter_kernels.hip beside the product with A, whatever the level
+// count; host operands take ilu::solve_iter, which the sweeps reproduce bit for bit.
 #include "amg_internal.hpp"
 #include "ilu_device.hpp"
 #include "ilu_host.hpp"
@@ -43,6 +48,16 @@ struct hypre_amd_ILUData
    std::vector<double> h_ftemp, h_utemp, h_ghost, h_send;
    std::vector<HYPRE_Real> norms;     // relative residual norm after every iteration, when norms are computed
    HYPRE_Int run_launches = 0, level_launches = 0;     // of the last application
+   // iterative triangular solves: the switch, the sweeps per factor (hypre_ILUCreate: 5 and 5), the factors in row slices
+   HYPRE_Int  iterative = 0, lower_iters = 5, upper_iters = 5, sweep_launches = 0;
+   long long  padded_L = 0, padded_U = 0;    // entries of the slice form with its padding, counted at Setup
+   bool       iter_uploaded = false;
+   int       *d_iter_int = nullptr;
+   double    *d_iter_real = nullptr;
+   long long *d_iter_base = nullptr;
+   IluSlices  sL, sU;
+   double    *d_work[3] = {nullptr, nullptr, nullptr};  // iterates of the sweeps, ping-ponged
+   std::vector<double> h_ztemp;
 };
 
 }  // extern "C"
@@ -65,6 +80,12 @@ void release_device(hypre_amd_ILUData *d)
    d->dL = IluTri{}; d->dU = IluTri{};
    d->d_utemp = nullptr;
    d->uploaded = false;
+   if (d->d_iter_int) { (void) hipFree(d->d_iter_int); d->d_iter_int = nullptr; }
+   if (d->d_iter_real) { (void) hipFree(d->d_iter_real); d->d_iter_real = nullptr; }
+   if (d->d_iter_base) { (void) hipFree(d->d_iter_base); d->d_iter_base = nullptr; }
+   d->sL = IluSlices{}; d->sU = IluSlices{};
+   d->d_work[0] = d->d_work[1] = d->d_work[2] = nullptr;
+   d->iter_uploaded = false;
 }
 
 // one factor in level order on the host: slot tables and entries, permutation folded in
@@ -113,6 +134,110 @@ void upload(hypre_amd_ILUData *d, hypre_ParCSRMatrix *A)
    d->ftemp = hypre_ParVectorCreate(A->comm, A->global_num_rows, A->row_starts);
    hypre_ParVectorInitialize_v2(d->ftemp, HYPRE_MEMORY_DEVICE);
    d->uploaded = true;
+}
+
+// the slice form of both factors and the three work vectors of the sweeps; the level-ordered form stays where it is
+void upload_iter(hypre_amd_ILUData *d)
+{
+   const int n = d->F.n;
+   ilu::Slices L, U;
+   ilu::build_slices(d->F, d->VL.order, d->F.Li, d->F.Lj, d->F.La, L);
+   ilu::build_slices(d->F, d->VU.order, d->F.Ui, d->F.Uj, d->F.Ua, U);
+   std::vector<int> ints;
+   std::vector<double> reals;
+   std::vector<long long> bases;
+   auto put_i = [&](const std::vector<int> &v) { const size_t at = ints.size(); ints.insert(ints.end(), v.begin(), v.end()); return at; };
+   auto put_r = [&](const std::vector<double> &v) { const size_t at = reals.size(); reals.insert(reals.end(), v.begin(), v.end()); return at; };
+   const size_t ll = put_i(L.len), lr = put_i(L.row), lc = put_i(L.col), ul = put_i(U.len), ur = put_i(U.row), uc = put_i(U.col);
+   const size_t lv = put_r(L.val), ld = put_r(L.dinv), uv = put_r(U.val), ud = put_r(U.dinv), w = reals.size();
+   const size_t nw = (size_t) std::max(n, 1);
+   reals.resize(reals.size() + 3 * nw, 0.0);
+   ints.push_back(0);                                    // never an empty allocation
+   bases.insert(bases.end(), L.base.begin(), L.base.end());
+   bases.insert(bases.end(), U.base.begin(), U.base.end());
+   bases.push_back(0);
+   HIP_CHECK(hipMalloc((void **) &d->d_iter_int, sizeof(int) * ints.size()));
+   HIP_CHECK(hipMalloc((void **) &d->d_iter_real, sizeof(double) * reals.size()));
+   HIP_CHECK(hipMalloc((void **) &d->d_iter_base, sizeof(long long) * bases.size()));
+   if (!d->d_iter_int || !d->d_iter_real || !d->d_iter_base)
+   {
+      if (d->d_iter_int) { (void) hipFree(d->d_iter_int); d->d_iter_int = nullptr; }
+      if (d->d_iter_real) { (void) hipFree(d->d_iter_real); d->d_iter_real = nullptr; }
+      if (d->d_iter_base) { (void) hipFree(d->d_iter_base); d->d_iter_base = nullptr; }
+      return;
+   }
+   HIP_CHECK(hipMemcpy(d->d_iter_int, ints.data(), sizeof(int) * ints.size(), hipMemcpyHostToDevice));
+   HIP_CHECK(hipMemcpy(d->d_iter_real, reals.data(), sizeof(double) * reals.size(), hipMemcpyHostToDevice));
+   HIP_CHECK(hipMemcpy(d->d_iter_base, bases.data(), sizeof(long long) * bases.size(), hipMemcpyHostToDevice));
+   d->sL.base = d->d_iter_base; d->sU.base = d->d_iter_base + L.base.size();
+   d->sL.len = d->d_iter_int + ll; d->sL.row = d->d_iter_int + lr; d->sL.col = d->d_iter_int + lc;
+   d->sU.len = d->d_iter_int + ul; d->sU.row = d->d_iter_int + ur; d->sU.col = d->d_iter_int + uc;
+   d->sL.val = d->d_iter_real + lv; d->sL.dinv = d->d_iter_real + ld; d->sU.val = d->d_iter_real + uv; d->sU.dinv = d->d_iter_real + ud;
+   d->sL.nslices = L.nslices; d->sU.nslices = U.nslices;
+   for (int k = 0; k < 3; k++) { d->d_work[k] = d->d_iter_real + w + (size_t) k * nw; }
+   d->iter_uploaded = true;
+}
+
+// One application as sweeps: u += z, z the last upper iterate.  y^1 = rhs and z^1 = Dinv y have sums of +0.0 and read no
+// matrix, so a factor with k sweeps costs k - 1 products: the first L pass reads rhs as its iterate, the last L pass stores
+// y and z^1 = Dinv y, the last U pass adds into u.  Launches: lower - 1 + upper - 1, one more when lower is 1 (z^1 = Dinv rhs
+// has no L pass to ride on); never more than lower + upper, whatever n and the level count.  Three work vectors: while U is
+// swept y stays and z ping-pongs; rhs may be the caller's own and is only read.  Returns the bytes the launches require.
+double run_sweeps(hypre_amd_ILUData *d, const double *rhs, double *u, hipStream_t s)
+{
+   const int lower = d->lower_iters, upper = d->upper_iters, n = d->F.n;
+   if (lower <= 0 || upper <= 0 || n <= 0) { return 0.0; }
+   double bytes = 0.0;
+   auto launch = [&](const IluSweepArgs &a, bool up) {
+      launch_ilu_sweep(a, up, s);
+      d->sweep_launches++;
+      // slot tables (length, vector index: 8), rhs (8), slice bases; entries and the gathered iterate when a product is formed;
+      // inverse pivots when used; every vector stored; u read and written
+      bytes += 8.0 * a.t.nslices + (double) n * (16.0 + (a.in ? 8.0 : 0.0) + (a.out ? 8.0 : 0.0) + ((up || a.scale) ? 8.0 : 0.0) +
+                                                 (a.scaled ? 8.0 : 0.0) + (a.u ? 16.0 : 0.0)) +
+               (a.in ? 12.0 * (double) (up ? d->padded_U : d->padded_L) : 0.0);
+   };
+   double *const *W = d->d_work;
+   const double *y = rhs;                 // the last lower iterate: rhs itself with one sweep
+   int ybuf = -1;
+   const double *prev = rhs;              // y^1 = rhs
+   for (int k = 2; k <= lower; k++)
+   {
+      IluSweepArgs a{};
+      a.t = d->sL; a.rhs = rhs; a.in = prev;
+      ybuf = k & 1;                       // W[0], W[1], W[0], ...
+      a.out = W[ybuf];
+      if (k == lower)
+      {
+         a.scale = 1;
+         if (upper == 1) { a.out = nullptr; a.u = u; }
+         else { a.scaled = W[2]; }
+      }
+      launch(a, false);
+      prev = y = W[ybuf];
+   }
+   if (lower == 1)
+   {
+      // z^1 = Dinv rhs alone: the L pass from the zero iterate, nothing of the factor's entries read
+      IluSweepArgs a{};
+      a.t = d->sL; a.rhs = rhs; a.scale = 1;
+      if (upper == 1) { a.u = u; }
+      else { a.scaled = W[2]; }
+      launch(a, false);
+   }
+   // z^1 lies in W[2]; y in W[ybuf] (or in rhs); the other of W[0] / W[1] is free
+   const int spare = ybuf == 0 ? 1 : 0;
+   int zbuf = 2;
+   for (int k = 2; k <= upper; k++)
+   {
+      IluSweepArgs a{};
+      a.t = d->sU; a.rhs = y; a.in = W[zbuf];
+      zbuf = zbuf == 2 ? spare : 2;
+      if (k == upper) { a.u = u; }
+      else { a.out = W[zbuf]; }
+      launch(a, true);
+   }
+   return bytes;
 }
 
 // the levels of one factor: a level wider than a workgroup gets a grid, consecutive narrower ones share a launch
@@ -196,8 +321,18 @@ struct Ops
    // u += (L D^-1 U)^-1 rhs
    void apply_factors(const double *rhs)
    {
-      d->run_launches = d->level_launches = 0;
-      if (device)
+      d->run_launches = d->level_launches = d->sweep_launches = 0;
+      if (d->iterative)
+      {
+         if (device) { account_bytes(run_sweeps(d, rhs, u->local_vector->data, stream())); }
+         else if (d->lower_iters > 0 && d->upper_iters > 0)
+         {
+            ilu::solve_iter(d->F, rhs, d->h_utemp.data(), d->h_ztemp.data(), d->lower_iters, d->upper_iters);
+            double *ud = u->local_vector->data;
+            for (int i = 0; i < n; i++) { ud[i] = ud[i] + d->h_ztemp[(size_t) i]; }
+         }
+      }
+      else if (device)
       {
          if (n > 0)
          {
@@ -251,7 +386,7 @@ HYPRE_Int HYPRE_ILUDestroy(HYPRE_Solver solver)
    return hypre_error_flag;
 }
 
-// what lies outside block-Jacobi ILU(k) with direct triangular solves is refused where it is asked for
+// what lies outside block-Jacobi ILU(k) is refused where it is asked for
 HYPRE_Int HYPRE_ILUSetType(HYPRE_Solver s, HYPRE_Int ilu_type)
 {
    if (refuse_null(s)) { return hypre_error_flag; }
@@ -278,16 +413,44 @@ HYPRE_Int HYPRE_ILUSetLocalReordering(HYPRE_Solver s, HYPRE_Int reordering_type)
    D(s)->reordering = reordering_type;
    return hypre_error_flag;
 }
+// The iterative triangular solves (the reference's tri_solve 0) are served, through hypre_amd_ILUSetIterativeTriSolve,
+// HYPRE_ILUSetLowerJacobiIters and HYPRE_ILUSetUpperJacobiIters below.  This setter still refuses 0: its refusal is pinned by
+// the tests of the commit that brought ILU, which stay as they are, so the capability got a switch of its own beside it.
 HYPRE_Int HYPRE_ILUSetTriSolve(HYPRE_Solver s, HYPRE_Int tri_solve)
 {
    if (refuse_null(s)) { return hypre_error_flag; }
    if (tri_solve != 1)
    {
       hypre_error_w_msg(HYPRE_ERROR_GENERIC, ("HYPRE_ILUSetTriSolve: tri_solve " + std::to_string(tri_solve) + " is outside the scope of this library "
-                                              "(1: direct triangular solves; the iterative solves are not served)").c_str());
+                                              "(1: direct triangular solves; the iterative solves are switched on by hypre_amd_ILUSetIterativeTriSolve)").c_str());
       return hypre_error_flag;
    }
    D(s)->tri_solve = tri_solve;
+   return hypre_error_flag;
+}
+// hypre_ILUSetLowerJacobiIters / hypre_ILUSetUpperJacobiIters (par_ilu.c): sweeps per triangular solve when the solves are iterative
+HYPRE_Int HYPRE_ILUSetLowerJacobiIters(HYPRE_Solver s, HYPRE_Int lower_jacobi_iters)
+{
+   if (refuse_null(s)) { return hypre_error_flag; }
+   if (lower_jacobi_iters < 0) { hypre_error_in_arg(2); return hypre_error_flag; }
+   D(s)->lower_iters = lower_jacobi_iters;
+   return hypre_error_flag;
+}
+HYPRE_Int HYPRE_ILUSetUpperJacobiIters(HYPRE_Solver s, HYPRE_Int upper_jacobi_iters)
+{
+   if (refuse_null(s)) { return hypre_error_flag; }
+   if (upper_jacobi_iters < 0) { hypre_error_in_arg(2); return hypre_error_flag; }
+   D(s)->upper_iters = upper_jacobi_iters;
+   return hypre_error_flag;
+}
+// 1: every triangular solve is lower / upper Jacobi sweeps (the reference's tri_solve 0); 0, the default: direct solves.
+// May be flipped between two solves of one Setup: the slice form of the factors is built when first needed.
+HYPRE_Int hypre_amd_ILUSetIterativeTriSolve(HYPRE_Solver s, HYPRE_Int iterative)
+{
+   if (refuse_null(s)) { return hypre_error_flag; }
+   if (iterative != 0 && iterative != 1) { hypre_error_in_arg(2); return hypre_error_flag; }
+   D(s)->iterative = iterative;
+   D(s)->tri_solve = iterative ? 0 : 1;
    return hypre_error_flag;
 }
 HYPRE_Int HYPRE_ILUSetMaxIter(HYPRE_Solver s, HYPRE_Int max_iter)
@@ -387,6 +550,20 @@ HYPRE_Int HYPRE_ILUSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVec
    ilu::build_levels(n, d->F.Ui.data(), d->F.Uj.data(), false, d->VU);
    d->h_ftemp.assign((size_t) std::max(n, 1), 0.0);
    d->h_utemp.assign((size_t) std::max(n, 1), 0.0);
+   d->h_ztemp.assign((size_t) std::max(n, 1), 0.0);
+   // entries of the slice form: every slice of 64 rows of the level order as long as its longest row
+   auto padded = [n](const std::vector<int> &order, const std::vector<int> &Ti) {
+      long long total = 0;
+      for (int s0 = 0; s0 < n; s0 += ilu::SLICE_ROWS)
+      {
+         int longest = 0;
+         for (int t = s0; t < std::min(n, s0 + ilu::SLICE_ROWS); t++) { longest = std::max(longest, Ti[(size_t) order[(size_t) t] + 1] - Ti[(size_t) order[(size_t) t]]); }
+         total += (long long) longest * ilu::SLICE_ROWS;
+      }
+      return total;
+   };
+   d->padded_L = padded(d->VL.order, d->F.Li);
+   d->padded_U = padded(d->VU.order, d->F.Ui);
    // fill of the factors over the entries of A, all ranks (par_ilu_setup.c:640-660; printed by Solve at print level > 1)
    const double fill = global_sum(A->comm, (double) n + (double) d->F.Lj.size() + (double) d->F.Uj.size());
    const double nnzA = global_sum(A->comm, (double) nnz + (double) (A->offd ? A->offd->num_nonzeros : 0));
@@ -394,9 +571,10 @@ HYPRE_Int HYPRE_ILUSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVec
    d->num_iterations = 0;
    d->final_rel_residual_norm = 0.0;
    d->norms.clear();
-   d->run_launches = d->level_launches = 0;
+   d->run_launches = d->level_launches = d->sweep_launches = 0;
    d->is_setup = true;
    if (on_device) { upload(d, A); }
+   if (on_device && d->uploaded && d->iterative) { upload_iter(d); }
    return hypre_error_flag;
 }
 
@@ -438,6 +616,11 @@ HYPRE_Int HYPRE_ILUSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVec
       upload(d, A);
       if (!d->uploaded) { return hypre_error_flag; }
    }
+   if (device && d->iterative && !d->iter_uploaded)
+   {
+      upload_iter(d);
+      if (!d->iter_uploaded) { return hypre_error_flag; }
+   }
    Ops op{d, A, f, u, device, n};
    const HYPRE_Int print_level = d->print_level, logging = d->logging, max_iter = d->max_iter;
    const HYPRE_Real tol = d->tol;
@@ -453,8 +636,10 @@ HYPRE_Int HYPRE_ILUSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVec
    d->norms.clear();
    if (print)
    {
-      printf("ILU SOLVER PARAMETERS:\n  ILU type 0 (block Jacobi with ILU(%d)), local reordering %d, direct triangular solves\n"
-             "  stopping tolerance %e, maximum iterations %d\n", (int) d->lfil, (int) d->reordering, tol, (int) max_iter);
+      const std::string tri = d->iterative ? "triangular solves by " + std::to_string(d->lower_iters) + " lower and " + std::to_string(d->upper_iters) +
+                                             " upper Jacobi sweeps" : std::string("direct triangular solves");
+      printf("ILU SOLVER PARAMETERS:\n  ILU type 0 (block Jacobi with ILU(%d)), local reordering %d, %s\n"
+             "  stopping tolerance %e, maximum iterations %d\n", (int) d->lfil, (int) d->reordering, tri.c_str(), tol, (int) max_iter);
       if (tol > 0.) { printf("\n\n ILU SOLVER SOLUTION INFO:\n"); }
    }
    if (with_norms)
@@ -541,6 +726,11 @@ HYPRE_Int hypre_amd_ILUApplyFactors(HYPRE_Solver solver, HYPRE_ParVector f, HYPR
                                              "before), and f and u of the factored rows, one column, distinct, in the same memory");
       return hypre_error_flag;
    }
+   if (device && d->iterative && !d->iter_uploaded)
+   {
+      upload_iter(d);
+      if (!d->iter_uploaded) { return hypre_error_flag; }
+   }
    Ops op{d, nullptr, f, u, device, d->F.n};
    op.apply_factors(fl->data);
    maybe_sync();
@@ -569,6 +759,22 @@ HYPRE_Int hypre_amd_ILUGetSolveStats(HYPRE_Solver s, HYPRE_Int *levels_L, HYPRE_
    if (level_launches) { *level_launches = d->level_launches; }
    if (nnz_L) { *nnz_L = d->is_setup ? (HYPRE_Int) d->F.Lj.size() : 0; }
    if (nnz_U) { *nnz_U = d->is_setup ? (HYPRE_Int) d->F.Uj.size() : 0; }
+   return hypre_error_flag;
+}
+
+// the iterative triangular solves as they stand: the switch, the sweeps per factor, the launches of the last application on
+// the device (0 after a host one), the entries of the two factors in the slice form, padding included (0 before Setup)
+HYPRE_Int hypre_amd_ILUGetIterativeStats(HYPRE_Solver s, HYPRE_Int *iterative, HYPRE_Int *lower_jacobi_iters, HYPRE_Int *upper_jacobi_iters,
+                                         HYPRE_Int *launches_per_application, HYPRE_BigInt *padded_nnz_L, HYPRE_BigInt *padded_nnz_U)
+{
+   if (refuse_null(s)) { return hypre_error_flag; }
+   const hypre_amd_ILUData *d = D(s);
+   if (iterative) { *iterative = d->iterative; }
+   if (lower_jacobi_iters) { *lower_jacobi_iters = d->lower_iters; }
+   if (upper_jacobi_iters) { *upper_jacobi_iters = d->upper_iters; }
+   if (launches_per_application) { *launches_per_application = d->sweep_launches; }
+   if (padded_nnz_L) { *padded_nnz_L = d->is_setup ? (HYPRE_BigInt) d->padded_L : 0; }
+   if (padded_nnz_U) { *padded_nnz_U = d->is_setup ? (HYPRE_BigInt) d->padded_U : 0; }
    return hypre_error_flag;
 }
 

@@ -82,7 +82,10 @@ class IJOptions:
         self.ilu_type = 0             # -ilu_type       (test/ij.c:447-457 defaults); 0, block Jacobi with ILU(k), is what this driver serves
         self.ilu_lfil = 0             # -ilu_lfil       level of fill k
         self.ilu_reordering = 1       # -ilu_reordering 0 none, 1 reverse Cuthill-McKee on the diagonal block
-        self.ilu_tri_solve = 1        # -ilu_tri_solve  1 direct triangular solves (0, iterative, is refused)
+        self.ilu_tri_solve = 1        # -ilu_tri_solve  1 direct triangular solves (0 is refused: the iterative solves are the three fields below)
+        self.ilu_iterative = 0        # 1: triangular solves as Jacobi sweeps (hypre_amd_ILUSetIterativeTriSolve); no command-line flag
+        self.ilu_ljac_iters = 5       # sweeps of the lower solve (HYPRE_ILUSetLowerJacobiIters; test/ij.c default 5)
+        self.ilu_ujac_iters = 5       # sweeps of the upper solve (HYPRE_ILUSetUpperJacobiIters)
         self.ilu_sm_max_iter = 1      # -ilu_sm_max_iter: sweeps of ILU as a BoomerAMG smoother (-smtype 5, refused): accepted, no effect
         for k, v in kw.items():
             if not hasattr(self, k):
@@ -403,6 +406,8 @@ def check_options(opt):
                          "RAS, ddPQ and RAP types are not served)" % opt.ilu_type)
     if opt.ilu_tri_solve != 1:
         raise SystemExit("ij: -ilu_tri_solve %d is outside the scope of this driver (1: direct triangular solves)" % opt.ilu_tri_solve)
+    if opt.ilu_iterative not in (0, 1) or opt.ilu_ljac_iters < 0 or opt.ilu_ujac_iters < 0:
+        raise SystemExit("ij: ilu_iterative is 0 (direct triangular solves) or 1 (Jacobi sweeps), ilu_ljac_iters and ilu_ujac_iters are >= 0")
     if opt.ilu_lfil < 0 or opt.ilu_reordering not in (0, 1):
         raise SystemExit("ij: -ilu_lfil takes a level of fill >= 0, -ilu_reordering 0 (none) or 1 (reverse Cuthill-McKee)")
     if opt.solver in (80, 81, 82) and (opt.num_components > 1 or opt.lgmres or opt.hybrid):
@@ -690,6 +695,10 @@ def create_ilu(opt, preconditioner=False):
     L.HYPRE_ILUSetLevelOfFill(s, opt.ilu_lfil)
     L.HYPRE_ILUSetLocalReordering(s, opt.ilu_reordering)
     L.HYPRE_ILUSetTriSolve(s, opt.ilu_tri_solve)
+    # the reference driver hands the sweep counts to 81 / 82 only (test/ij.c:7167-7168, 7866-7867); here 80 takes them too
+    L.hypre_amd_ILUSetIterativeTriSolve(s, opt.ilu_iterative)
+    L.HYPRE_ILUSetLowerJacobiIters(s, opt.ilu_ljac_iters)
+    L.HYPRE_ILUSetUpperJacobiIters(s, opt.ilu_ujac_iters)
     L.HYPRE_ILUSetPrintLevel(s, 0)
     L.HYPRE_ILUSetMaxIter(s, 1 if preconditioner else opt.max_iter)
     L.HYPRE_ILUSetTol(s, 0.0 if preconditioner else opt.tol)

@@ -863,8 +863,13 @@ HYPRE_Int hypre_amd_ParCSRHybridGetKrylovSolver(HYPRE_Solver solver, HYPRE_Solve
  * u = 0; with tol 0 and print level and logging at most 1 (a preconditioner) no norm is computed.  Setup and Solve have
  * the HYPRE_PtrToSolverFcn signature: hand them to any *SetPrecond.  A, f and u lie all in device memory (level-scheduled
  * kernels) or all in host memory (the host solve, which the kernels reproduce bit for bit); one column.
- * Outside the scope, refused by the setter: ilu_type other than 0 (ILUT, Schur-GMRES, NSH, RAS, ddPQ, RAP), tri_solve 0
- * (iterative triangular solves).  Iterative setup and ILU as a BoomerAMG smoother have no entry point. */
+ * Iterative triangular solves (the reference's tri_solve 0, hypre_ILUSolveLUIter): with hypre_amd_ILUSetIterativeTriSolve on,
+ * each triangular solve is a fixed number of Jacobi sweeps from a zero iterate (HYPRE_ILUSetLowerJacobiIters /
+ * HYPRE_ILUSetUpperJacobiIters, 5 and 5); without a lower or without an upper sweep an application leaves u as it is.  On
+ * the device the factors then lie in row slices of 64 rows as well and an application is at most lower + upper launches
+ * beside the product with A, whatever the number of dependency levels; the host path is reproduced bit for bit.
+ * Outside the scope, refused by the setter: ilu_type other than 0 (ILUT, Schur-GMRES, NSH, RAS, ddPQ, RAP).  Iterative
+ * setup and ILU as a BoomerAMG smoother have no entry point. */
 HYPRE_Int HYPRE_ILUCreate(HYPRE_Solver *solver);
 HYPRE_Int HYPRE_ILUDestroy(HYPRE_Solver solver);
 HYPRE_Int HYPRE_ILUSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);
@@ -872,7 +877,18 @@ HYPRE_Int HYPRE_ILUSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVec
 HYPRE_Int HYPRE_ILUSetType(HYPRE_Solver solver, HYPRE_Int ilu_type);                    /* 0 only */
 HYPRE_Int HYPRE_ILUSetLevelOfFill(HYPRE_Solver solver, HYPRE_Int lfil);
 HYPRE_Int HYPRE_ILUSetLocalReordering(HYPRE_Solver solver, HYPRE_Int reordering_type);   /* 0 none, 1 RCM */
-HYPRE_Int HYPRE_ILUSetTriSolve(HYPRE_Solver solver, HYPRE_Int tri_solve);               /* 1 only */
+/* 1 only.  The iterative solves the reference selects with 0 are served by hypre_amd_ILUSetIterativeTriSolve below; this
+ * setter goes on refusing 0, as the tests that came with it pin. */
+HYPRE_Int HYPRE_ILUSetTriSolve(HYPRE_Solver solver, HYPRE_Int tri_solve);
+HYPRE_Int HYPRE_ILUSetLowerJacobiIters(HYPRE_Solver solver, HYPRE_Int lower_jacobi_iters);   /* >= 0, default 5 */
+HYPRE_Int HYPRE_ILUSetUpperJacobiIters(HYPRE_Solver solver, HYPRE_Int upper_jacobi_iters);   /* >= 0, default 5 */
+/* 0 (default): direct triangular solves; 1: Jacobi sweeps.  hypre_amd_ILUGetParameters then reports tri_solve 0.  May be
+ * changed between two solves of one Setup. */
+HYPRE_Int hypre_amd_ILUSetIterativeTriSolve(HYPRE_Solver solver, HYPRE_Int iterative);
+/* The switch, the sweeps per factor, the launches of the last application on the device (0 after a host one) and the
+ * entries of L and U in the slice form with its padding (0 before Setup).  Any pointer may be NULL. */
+HYPRE_Int hypre_amd_ILUGetIterativeStats(HYPRE_Solver solver, HYPRE_Int *iterative, HYPRE_Int *lower_jacobi_iters, HYPRE_Int *upper_jacobi_iters,
+                                         HYPRE_Int *launches_per_application, HYPRE_BigInt *padded_nnz_L, HYPRE_BigInt *padded_nnz_U);
 HYPRE_Int HYPRE_ILUSetMaxIter(HYPRE_Solver solver, HYPRE_Int max_iter);
 HYPRE_Int HYPRE_ILUSetTol(HYPRE_Solver solver, HYPRE_Real tol);
 HYPRE_Int HYPRE_ILUSetPrintLevel(HYPRE_Solver solver, HYPRE_Int print_level);
