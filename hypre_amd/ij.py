@@ -3,7 +3,11 @@
 
 Everything numerical happens in libhypre_amd.so; this module only translates
 driver options into HYPRE_* calls, the way test/ij.c does.
+
+A new Krylov solver is added in two places: a row of SOLVERS, and a `solve_<method>(opt, A, b, x, comm=0, amg=None)`
+wrapper of _solve_krylov that lists its setters.  The command line, check_options, run and the closing lines read the row.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -11,6 +15,28 @@ import numpy as np
 from . import binding as B
 
 HOST, DEVICE = B.HYPRE_MEMORY_HOST, B.HYPRE_MEMORY_DEVICE
+
+# method: None (BoomerAMG alone), "ILU" (ILU alone) or the Krylov solver, which run() reaches as solve_<method in lower case>;
+# precond: "amg" (BoomerAMG), "ds" (diagonal scaling) or "ilu"; tag: what the closing lines call the solver; cli: whether
+# the command line takes the id (60 / 61 are served for options built in code only: tests/test_cogmres_cli.py pins the refusal).
+# LGMRES is no row: lgmres = 1 runs it in place of GMRES on 3 and 4.  The hybrid solver is chosen by hybrid = 1.
+Solver = collections.namedtuple("Solver", "method precond tag cli")
+SOLVERS = {
+    0: Solver(None, "amg", "BoomerAMG ", True),
+    1: Solver("PCG", "amg", "", True),
+    2: Solver("PCG", "ds", "", True),
+    3: Solver("GMRES", "amg", "GMRES ", True),
+    4: Solver("GMRES", "ds", "GMRES ", True),
+    9: Solver("BiCGSTAB", "amg", "BiCGSTAB ", True),
+    10: Solver("BiCGSTAB", "ds", "BiCGSTAB ", True),
+    16: Solver("COGMRES", "amg", "COGMRES ", True),
+    17: Solver("COGMRES", "ds", "COGMRES ", True),
+    60: Solver("FlexGMRES", "ds", "FlexGMRES ", False),
+    61: Solver("FlexGMRES", "amg", "FlexGMRES ", False),
+    80: Solver("ILU", "ilu", "hypre_ILU ", True),
+    81: Solver("GMRES", "ilu", "GMRES ", True),
+    82: Solver("FlexGMRES", "ilu", "FlexGMRES ", True),
+}
 
 
 class IJOptions:
@@ -25,8 +51,7 @@ class IJOptions:
         self.sys_num_fun = 1          # -sysL <num functions>: systems version of the 7-point operator
         self.c = (1.0, 1.0, 1.0)      # -c cx cy cz
         self.a = (1.0, 1.0, 1.0)      # -a ax ay az (difconv)
-        self.solver = 0               # 0 AMG, 1 AMG-PCG, 2 DS-PCG (diagonal scaling), 3 AMG-GMRES, 4 DS-GMRES, 9 AMG-BiCGSTAB, 10 DS-BiCGSTAB,
-                                      # 16 AMG-COGMRES, 17 DS-COGMRES, 60 DS-FlexGMRES, 61 AMG-FlexGMRES, 80 ILU, 81 ILU-GMRES, 82 ILU-FlexGMRES
+        self.solver = 0               # -solver: a key of SOLVERS
         self.lgmres = 0               # options only: 1 runs LGMRES in place of GMRES, solver 4 as DS-LGMRES (the reference's -solver 50),
                                       # solver 3 as AMG-LGMRES (51)
         self.hybrid = 0               # options only: 1 runs the hybrid solver (the reference's -solver 20, test/ij.c:4302-4435): a diagonally
@@ -384,9 +409,7 @@ def parse_cli(argv):
                              "-ilu_tri_solve 1, -ilu_sm_max_iter)" % flag)
         else:
             raise SystemExit("ij: option %s is outside the scope of this driver" % flag)
-    if opt.solver not in (0, 1, 2, 3, 4, 9, 10, 16, 17, 80, 81, 82):
-        # FlexGMRES (60 DS, 61 AMG) is served by run() for options built in code, but the command line keeps refusing the
-        # two ids: tests/test_cogmres_cli.py pins them as outside its scope
+    if not (opt.solver in SOLVERS and SOLVERS[opt.solver].cli):
         raise SystemExit("ij: -solver %d is outside the scope of this driver (0 AMG, 1 AMG-PCG, 2 DS-PCG, 3 AMG-GMRES, 4 DS-GMRES, "
                          "9 AMG-BiCGSTAB, 10 DS-BiCGSTAB, 16 AMG-COGMRES, 17 DS-COGMRES, 80 ILU, 81 ILU-GMRES, 82 ILU-FlexGMRES)" % opt.solver)
     if opt.interp_type not in (6, 3):
@@ -399,8 +422,9 @@ def parse_cli(argv):
 def check_options(opt):
     """The combinations of options this driver serves, whether they came from the command line or were set in code
     (solvers 60 / 61, FlexGMRES, and lgmres = 1, only the latter); returns opt."""
-    if opt.solver not in (0, 1, 2, 3, 4, 9, 10, 16, 17, 60, 61, 80, 81, 82):
+    if opt.solver not in SOLVERS:
         raise SystemExit("ij: solver %d is outside the scope of this driver" % opt.solver)
+    spec = SOLVERS[opt.solver]
     if opt.ilu_type != 0:
         raise SystemExit("ij: -ilu_type %d is outside the scope of this driver (0: block Jacobi with ILU(k); ILUT and the Schur, NSH, "
                          "RAS, ddPQ and RAP types are not served)" % opt.ilu_type)
@@ -410,7 +434,7 @@ def check_options(opt):
         raise SystemExit("ij: ilu_iterative is 0 (direct triangular solves) or 1 (Jacobi sweeps), ilu_ljac_iters and ilu_ujac_iters are >= 0")
     if opt.ilu_lfil < 0 or opt.ilu_reordering not in (0, 1):
         raise SystemExit("ij: -ilu_lfil takes a level of fill >= 0, -ilu_reordering 0 (none) or 1 (reverse Cuthill-McKee)")
-    if opt.solver in (80, 81, 82) and (opt.num_components > 1 or opt.lgmres or opt.hybrid):
+    if spec.precond == "ilu" and (opt.num_components > 1 or opt.lgmres or opt.hybrid):
         raise SystemExit("ij: -solver %d (ILU) takes one component, and neither LGMRES nor the hybrid solver" % opt.solver)
     if opt.hybrid not in (0, 1) or (opt.hybrid and opt.solver != 0):
         raise SystemExit("ij: hybrid = %r with solver %d: the hybrid solver is chosen by hybrid = 1 alone, solver stays at its default"
@@ -429,10 +453,10 @@ def check_options(opt):
     if opt.num_components < 1 or (opt.num_components > 1 and (opt.rhs != "one" or opt.rhsfromfile)):
         # test/ij.c:3400-3404 takes several components with the constant right-hand sides only
         raise SystemExit("ij: -nc %d needs -rhsisone in this driver" % opt.num_components)
-    if opt.num_components > 1 and opt.solver in (16, 17):
+    if opt.num_components > 1 and spec.method == "COGMRES":
         raise SystemExit("ij: -nc %d with -solver %d: COGMRES doesn't take multicomponent vectors in this driver (GMRES, -solver 3 | 4, does)"
                          % (opt.num_components, opt.solver))
-    if opt.num_components > 1 and opt.solver in (0, 1, 3, 9, 61):
+    if opt.num_components > 1 and spec.precond == "amg":
         # BoomerAMG on multivectors (hypre_BoomerAMGSolve with num_vectors > 1) serves l1-Jacobi / Jacobi 7 / 18 and two-stage
         # Gauss-Seidel 11 / 12 over all points with a direct coarsest-level solve; the reference refuses hybrid Gauss-Seidel
         # (the defaults 13 / 14) with multicomponent vectors as well
@@ -479,6 +503,39 @@ def multivector_amg_refusal(opt):
     return ""
 
 
+def _vector(A, values, comm, nv=1, memory_location=DEVICE):
+    """This rank's `values` as a ParVector laid out like the rows of A; nv > 1: a multivector with the values in each of nv columns."""
+    Am = A.contents
+    where = dict(comm=comm, global_size=int(Am.global_num_rows), first=int(Am.row_starts[0]), location=memory_location)
+    if nv > 1:
+        return B.parmultivec_from_numpy(np.repeat(values[:, None], nv, axis=1), **where)
+    return B.parvec_from_numpy(values, **where)
+
+
+def device_vectors(opt, A, comm, rank, allreduce, memory_location=DEVICE):
+    """(b, x0) of build_rhs_host as ParVectors in `memory_location`; -nc N: as multivectors, the same values in every column
+    (test/ij.c:3483-3512).  -xisone: b = A * ones, a product on the device with the migrated A, read back and laid out like any other b."""
+    L = B.load_library()
+    b, x0 = build_rhs_host(opt, A, rank=rank, allreduce=allreduce)
+    if b is None:
+        if memory_location != DEVICE:
+            raise SystemExit("ij: -xisone needs a product with A, which runs on the device only")
+        ones, prod = _vector(A, np.ones(len(x0)), comm), _vector(A, np.zeros(len(x0)), comm)
+        L.hypre_ParCSRMatrixMatvec(1.0, A, ones, 0.0, prod)
+        b = B.parvec_to_numpy(prod)
+        L.hypre_ParVectorDestroy(ones); L.hypre_ParVectorDestroy(prod)
+    return tuple(_vector(A, v, comm, opt.num_components, memory_location) for v in (b, x0))
+
+
+def closing_lines(opt, its, rel):
+    """The driver's closing lines for every solver but the hybrid one.  The Krylov solvers are named in both lines, BoomerAMG
+    and ILU alone in the first only."""
+    spec = SOLVERS[opt.solver]
+    tag = "LGMRES " if opt.lgmres else spec.tag
+    return ["", "%sIterations = %d" % (tag, its),
+            "Final %sRelative Residual Norm = %e" % ("" if spec.method in (None, "ILU") else tag, rel), ""]
+
+
 def run(opt, comm=0, rank=0, nprocs=1, allreduce=None, out=None):
     """test/ij.c: build the problem, set up, solve on the device, print the driver's closing lines."""
     import sys
@@ -487,125 +544,70 @@ def run(opt, comm=0, rank=0, nprocs=1, allreduce=None, out=None):
     A = build_matrix(opt, comm=comm, rank=rank, nprocs=nprocs)
     if opt.hybrid:
         return run_hybrid(opt, A, comm=comm, rank=rank, allreduce=allreduce, out=out)
-    if opt.solver in (2, 4, 10, 17, 60):
-        return run_ds_pcg(opt, A, comm=comm, rank=rank, allreduce=allreduce, out=out)
-    if opt.solver in (80, 81, 82):
+    spec = SOLVERS[opt.solver]
+    if spec.precond == "ilu":
         return run_ilu(opt, A, comm=comm, rank=rank, allreduce=allreduce, out=out)
-    s = create_amg(opt, memory_location=DEVICE)
-    L.HYPRE_BoomerAMGSetup(s, A, None, None)
-    B.check()
+    amg = None
+    if spec.precond == "amg":
+        amg = create_amg(opt, memory_location=DEVICE)
+        L.HYPRE_BoomerAMGSetup(amg, A, None, None)      # on the host matrix
+        B.check()
     L.hypre_ParCSRMatrixMigrate(A, DEVICE)
-    Am = A.contents
-    first, nglob = int(Am.row_starts[0]), int(Am.global_num_rows)
-    b, x0 = build_rhs_host(opt, A, rank=rank, allreduce=allreduce)
-    nv = opt.num_components
-    if b is None:
-        ones = B.parvec_from_numpy(np.ones(len(x0)), comm=comm, global_size=nglob, first=first)
-        db = B.parvec_from_numpy(np.zeros(len(x0)), comm=comm, global_size=nglob, first=first)
-        L.hypre_ParCSRMatrixMatvec(1.0, A, ones, 0.0, db)
-        if nv > 1:
-            b = B.parvec_to_numpy(db)
-            L.hypre_ParVectorDestroy(db)
-        L.hypre_ParVectorDestroy(ones)
-    if nv > 1:
-        # -nc N: the same values in every column of b and of the initial guess (test/ij.c:3483-3512)
-        db = B.parmultivec_from_numpy(np.repeat(b[:, None], nv, axis=1), comm=comm, global_size=nglob, first=first)
-        dx = B.parmultivec_from_numpy(np.repeat(x0[:, None], nv, axis=1), comm=comm, global_size=nglob, first=first)
+    db, dx = device_vectors(opt, A, comm, rank, allreduce)
+    if spec.method is None:
+        its, rel, lines = solve_amg(opt, amg, A, db, dx, comm=comm)
     else:
-        if b is not None:
-            db = B.parvec_from_numpy(b, comm=comm, global_size=nglob, first=first)
-        dx = B.parvec_from_numpy(x0, comm=comm, global_size=nglob, first=first)
-    its, rel = C.c_int(), C.c_double()
-    lines = []
-    if opt.solver == 0:
-        # ||b - A x0|| for the average convergence factor (par_amg_solve.c:237-256, 347-355)
-        if nv > 1:
-            r0 = B.parmultivec_from_numpy(np.zeros((len(x0), nv)), comm=comm, global_size=nglob, first=first)
-        else:
-            r0 = B.parvec_from_numpy(np.zeros(len(x0)), comm=comm, global_size=nglob, first=first)
-        L.hypre_ParCSRMatrixMatvecOutOfPlace(-1.0, A, dx, 1.0, db, r0)
-        L.hypre_ParVectorInnerProd.restype = C.c_double
-        nrm0 = float(np.sqrt(L.hypre_ParVectorInnerProd(r0, r0)))
-        nrmb = float(np.sqrt(L.hypre_ParVectorInnerProd(db, db)))
-        L.HYPRE_BoomerAMGSolve(s, A, db, dx)
-        L.HYPRE_BoomerAMGGetNumIterations(s, C.byref(its))
-        L.HYPRE_BoomerAMGGetFinalRelativeResidualNorm(s, C.byref(rel))
-        g, o, cyc = C.c_double(), C.c_double(), C.c_double()
-        L.hypre_amd_BoomerAMGGetComplexities(s, C.byref(g), C.byref(o))
-        L.hypre_amd_BoomerAMGGetCycleOpCount(s, C.byref(cyc))
-        resid = rel.value * (nrmb if nrmb != 0.0 else 1.0)
-        conv = (resid / nrm0) ** (1.0 / its.value) if its.value > 0 and nrm0 != 0.0 else 1.0
-        nnz0 = float(Am.d_num_nonzeros)
-        lines += ["", " Average Convergence Factor = %f" % conv, "",
-                  "     Complexity:    grid = %f" % g.value,
-                  "                operator = %f" % o.value,
-                  "                   cycle = %f" % (cyc.value / nnz0 if nnz0 else 0.0), "", "", "",
-                  "BoomerAMG Iterations = %d" % its.value,
-                  "Final Relative Residual Norm = %e" % rel.value, ""]
-    elif opt.solver == 3 and opt.lgmres:
-        its.value, rel.value = solve_lgmres(opt, A, db, dx, comm=comm, amg=s)
-        lines += ["", "LGMRES Iterations = %d" % its.value, "Final LGMRES Relative Residual Norm = %e" % rel.value, ""]
-    elif opt.solver == 3:
-        its.value, rel.value = solve_gmres(opt, s, A, db, dx, comm=comm)
-        lines += ["", "GMRES Iterations = %d" % its.value, "Final GMRES Relative Residual Norm = %e" % rel.value, ""]
-    elif opt.solver == 16:
-        its.value, rel.value = solve_cogmres(opt, A, db, dx, comm=comm, amg=s)
-        lines += ["", "COGMRES Iterations = %d" % its.value, "Final COGMRES Relative Residual Norm = %e" % rel.value, ""]
-    elif opt.solver == 9:
-        its.value, rel.value = solve_bicgstab(opt, A, db, dx, comm=comm, amg=s)
-        lines += ["", "BiCGSTAB Iterations = %d" % its.value, "Final BiCGSTAB Relative Residual Norm = %e" % rel.value, ""]
-    elif opt.solver == 61:
-        its.value, rel.value = solve_flexgmres(opt, A, db, dx, comm=comm, amg=s)
-        lines += ["", "FlexGMRES Iterations = %d" % its.value, "Final FlexGMRES Relative Residual Norm = %e" % rel.value, ""]
-    else:
-        L.HYPRE_BoomerAMGSetTol(s, 0.0)
-        L.HYPRE_BoomerAMGSetMaxIter(s, opt.precon_cycles)
-        pcg = C.c_void_p()
-        L.HYPRE_ParCSRPCGCreate(comm, C.byref(pcg))
-        L.HYPRE_PCGSetTol(pcg, opt.tol)
-        L.HYPRE_PCGSetMaxIter(pcg, opt.max_iter)
-        L.HYPRE_PCGSetTwoNorm(pcg, opt.two_norm)
-        L.HYPRE_PCGSetFlex(pcg, opt.flex)
-        L.HYPRE_PCGSetPrecond(pcg, C.cast(L.HYPRE_BoomerAMGSolve, C.c_void_p), None, s)
-        L.HYPRE_ParCSRPCGSetup(pcg, A, db, dx)
-        L.HYPRE_ParCSRPCGSolve(pcg, A, db, dx)
-        L.HYPRE_PCGGetNumIterations(pcg, C.byref(its))
-        L.HYPRE_PCGGetFinalRelativeResidualNorm(pcg, C.byref(rel))
-        L.HYPRE_ParCSRPCGDestroy(pcg)
-        lines += ["", "Iterations = %d" % its.value, "Final Relative Residual Norm = %e" % rel.value, ""]
+        its, rel = krylov_solver(opt)(opt, A=A, b=db, x=dx, comm=comm, amg=amg)
+        lines = []
+    lines += closing_lines(opt, its, rel)
     L.HYPRE_ClearError(256)          # HYPRE_ERROR_CONV is reported through the iteration count, as the driver does
     B.check()
-    L.HYPRE_BoomerAMGDestroy(s)
+    if amg is not None:
+        L.HYPRE_BoomerAMGDestroy(amg)
+    L.hypre_ParVectorDestroy(db); L.hypre_ParVectorDestroy(dx)
     if rank == 0:
         out.write("\n".join(lines) + "\n")
         out.flush()
-    return its.value, rel.value
+    return its, rel
 
 
-def solve_ds_pcg(opt, A, db, dx, comm=0):
-    """test/ij.c:5007-5027, 5179-5191: PCG with the diagonal scaling preconditioner (solver 2); db and dx may be
-    multivectors (-nc N)."""
+def solve_amg(opt, amg, A, db, dx, comm=0):
+    """BoomerAMG alone (solver 0, test/ij.c:4440-4780): (iterations, final relative residual norm, the lines on the average
+    convergence factor and the complexities that precede the closing lines)."""
     L = B.load_library()
-    pcg = C.c_void_p()
-    L.HYPRE_ParCSRPCGCreate(comm, C.byref(pcg))
-    L.HYPRE_PCGSetTol(pcg, opt.tol)
-    L.HYPRE_PCGSetMaxIter(pcg, opt.max_iter)
-    L.HYPRE_PCGSetTwoNorm(pcg, opt.two_norm)
-    L.HYPRE_PCGSetFlex(pcg, opt.flex)
-    L.HYPRE_PCGSetPrecond(pcg, C.cast(L.HYPRE_ParCSRDiagScale, C.c_void_p), C.cast(L.HYPRE_ParCSRDiagScaleSetup, C.c_void_p), None)
-    L.HYPRE_ParCSRPCGSetup(pcg, A, db, dx)
-    L.HYPRE_ParCSRPCGSolve(pcg, A, db, dx)
+    # ||b - A x0|| for the average convergence factor (par_amg_solve.c:237-256, 347-355)
+    r0 = _vector(A, np.zeros(A.contents.diag.contents.num_rows), comm, opt.num_components)
+    L.hypre_ParCSRMatrixMatvecOutOfPlace(-1.0, A, dx, 1.0, db, r0)
+    L.hypre_ParVectorInnerProd.restype = C.c_double
+    nrm0 = float(np.sqrt(L.hypre_ParVectorInnerProd(r0, r0)))
+    nrmb = float(np.sqrt(L.hypre_ParVectorInnerProd(db, db)))
+    L.hypre_ParVectorDestroy(r0)
+    L.HYPRE_BoomerAMGSolve(amg, A, db, dx)
     its, rel = C.c_int(), C.c_double()
-    L.HYPRE_PCGGetNumIterations(pcg, C.byref(its))
-    L.HYPRE_PCGGetFinalRelativeResidualNorm(pcg, C.byref(rel))
-    L.HYPRE_ParCSRPCGDestroy(pcg)
-    return its.value, rel.value
+    L.HYPRE_BoomerAMGGetNumIterations(amg, C.byref(its))
+    L.HYPRE_BoomerAMGGetFinalRelativeResidualNorm(amg, C.byref(rel))
+    g, o, cyc = C.c_double(), C.c_double(), C.c_double()
+    L.hypre_amd_BoomerAMGGetComplexities(amg, C.byref(g), C.byref(o))
+    L.hypre_amd_BoomerAMGGetCycleOpCount(amg, C.byref(cyc))
+    resid = rel.value * (nrmb if nrmb != 0.0 else 1.0)
+    conv = (resid / nrm0) ** (1.0 / its.value) if its.value > 0 and nrm0 != 0.0 else 1.0
+    nnz0 = float(A.contents.d_num_nonzeros)
+    return its.value, rel.value, ["", " Average Convergence Factor = %f" % conv, "",
+                                  "     Complexity:    grid = %f" % g.value,
+                                  "                operator = %f" % o.value,
+                                  "                   cycle = %f" % (cyc.value / nnz0 if nnz0 else 0.0), "", ""]
 
 
-def _solve_gmres_family(name, opt, A, b, x, comm, amg, early=(), late=(), amg_first=False, amg_max_iter=None, check_precond=False, ilu=None):
-    """Create, set, Setup, Solve, read back and Destroy one HYPRE_ParCSR<name> solver (GMRES, COGMRES, FlexGMRES, LGMRES), in the
-    order of library calls the reference driver makes: KDim, the `early` setters, MaxIter, Tol, AbsoluteTol, the `late`
-    setters; then BoomerAMG (`amg`, tuned as a preconditioner: SetTol 0, SetMaxIter precon_cycles; before Create if
+def krylov_solver(opt):
+    """The solve_* wrapper of the options' Krylov method, to be called with A, b, x, comm and the preconditioner (amg or ilu) by
+    keyword: solve_gmres takes amg in second place."""
+    return globals()["solve_" + ("lgmres" if opt.lgmres else SOLVERS[opt.solver].method.lower())]
+
+
+def _solve_krylov(name, setters, opt, A, b, x, comm, amg, amg_first=False, amg_max_iter=None, check_precond=False, ilu=None):
+    """Create, set, Setup, Solve, read back and Destroy one HYPRE_ParCSR<name> solver (PCG, BiCGSTAB, GMRES, COGMRES, FlexGMRES,
+    LGMRES), in the order of library calls the reference driver makes: the `setters`, (stem, value) pairs in order; then
+    BoomerAMG (`amg`, tuned as a preconditioner: SetTol 0, SetMaxIter precon_cycles; before Create if
     `amg_first`, MaxIter set once more to `amg_max_iter` if given), the ILU object `ilu` (HYPRE_ILUSolve / HYPRE_ILUSetup) or the
     diagonal scaling preconditioner."""
     L = B.load_library()
@@ -619,7 +621,7 @@ def _solve_gmres_family(name, opt, A, b, x, comm, amg, early=(), late=(), amg_fi
         tune_amg()
     g = C.c_void_p()
     par("Create")(comm, C.byref(g))
-    for stem, value in (("KDim", opt.k_dim),) + tuple(early) + (("MaxIter", opt.max_iter), ("Tol", opt.tol), ("AbsoluteTol", 0.0)) + tuple(late):
+    for stem, value in setters:
         fn("Set" + stem)(g, value)
     if amg is not None:
         if not amg_first:
@@ -645,43 +647,65 @@ def _solve_gmres_family(name, opt, A, b, x, comm, amg, early=(), late=(), amg_fi
     return its.value, rel.value
 
 
+def solve_pcg(opt, A, b, x, comm=0, amg=None):
+    """test/ij.c:5007-5027, 5179-5200: PCG behind BoomerAMG (solver 1, `amg` the set-up hierarchy) or behind the diagonal scaling
+    preconditioner (solver 2); b and x may be multivectors (-nc N)."""
+    return _solve_krylov("PCG", (("Tol", opt.tol), ("MaxIter", opt.max_iter), ("TwoNorm", opt.two_norm), ("Flex", opt.flex)),
+                         opt, A, b, x, comm, amg, amg_first=True)
+
+
+def solve_ds_pcg(opt, A, db, dx, comm=0):
+    """PCG with the diagonal scaling preconditioner (solver 2)."""
+    return solve_pcg(opt, A, db, dx, comm=comm)
+
+
+def _gmres_setters(opt, early=(), late=()):
+    """What the reference driver sets on GMRES and its variants, in its order; `early` and `late` are the variant's own."""
+    return (("KDim", opt.k_dim),) + early + (("MaxIter", opt.max_iter), ("Tol", opt.tol), ("AbsoluteTol", 0.0)) + late
+
+
+def solve_gmres(opt, amg, A, b, x, comm=0, ilu=None):
+    """test/ij.c:6710-6790, 6919-6942, 7156-7215: GMRES(k) behind BoomerAMG (solver 3), ILU (81) or, with neither, the diagonal
+    scaling preconditioner (4); b and x may be multivectors (-nc N)."""
+    return _solve_krylov("GMRES", _gmres_setters(opt), opt, A, b, x, comm, amg, amg_first=True, ilu=ilu)
+
+
 def solve_ds_gmres(opt, A, db, dx, comm=0):
-    """test/ij.c:6710-6727, 6932-6942: GMRES(k) with the diagonal scaling preconditioner (solver 4); multivectors as above."""
-    return _solve_gmres_family("GMRES", opt, A, db, dx, comm, None)
+    """GMRES(k) with the diagonal scaling preconditioner (solver 4)."""
+    return solve_gmres(opt, None, A, db, dx, comm=comm)
 
 
-def run_ds_pcg(opt, A, comm=0, rank=0, allreduce=None, out=None):
-    """`ij -solver 2 | 4 | 10 | 17 | 60 [-nc N]` (4 with lgmres = 1: DS-LGMRES) on the device: no hierarchy; the N columns of b (test/ij.c:3483-3512: the same values in
-    every component) and of the zero initial guess as multivectors."""
-    L = B.load_library()
-    L.hypre_ParCSRMatrixMigrate(A, DEVICE)
-    Am = A.contents
-    first, nglob = int(Am.row_starts[0]), int(Am.global_num_rows)
-    b, x0 = build_rhs_host(opt, A, rank=rank, allreduce=allreduce)
-    nv = opt.num_components
-    if b is None:
-        ones = B.parvec_from_numpy(np.ones(len(x0)), comm=comm, global_size=nglob, first=first)
-        db1 = B.parvec_from_numpy(np.zeros(len(x0)), comm=comm, global_size=nglob, first=first)
-        L.hypre_ParCSRMatrixMatvec(1.0, A, ones, 0.0, db1)
-        b = B.parvec_to_numpy(db1)
-        L.hypre_ParVectorDestroy(ones); L.hypre_ParVectorDestroy(db1)
-    if nv > 1:
-        db = B.parmultivec_from_numpy(np.repeat(b[:, None], nv, axis=1), comm=comm, global_size=nglob, first=first)
-        dx = B.parmultivec_from_numpy(np.repeat(x0[:, None], nv, axis=1), comm=comm, global_size=nglob, first=first)
-    else:
-        db = B.parvec_from_numpy(b, comm=comm, global_size=nglob, first=first)
-        dx = B.parvec_from_numpy(x0, comm=comm, global_size=nglob, first=first)
-    solve = {2: solve_ds_pcg, 4: solve_lgmres if opt.lgmres else solve_ds_gmres, 10: solve_bicgstab, 17: solve_cogmres,
-             60: solve_flexgmres}[opt.solver]
-    its, rel = solve(opt, A, db, dx, comm=comm)
-    L.HYPRE_ClearError(256)
-    B.check()
-    L.hypre_ParVectorDestroy(db); L.hypre_ParVectorDestroy(dx)
-    if rank == 0:
-        tag = {4: "LGMRES " if opt.lgmres else "GMRES ", 10: "BiCGSTAB ", 17: "COGMRES ", 60: "FlexGMRES "}.get(opt.solver, "")
-        out.write("\n".join(["", "%sIterations = %d" % (tag, its), "Final %sRelative Residual Norm = %e" % (tag, rel), ""]) + "\n")
-        out.flush()
-    return its, rel
+def solve_cogmres(opt, A, b, x, comm=0, amg=None):
+    """test/ij.c:8426-8440, 8583-8598, 8710-8722: COGMRES behind BoomerAMG (solver 16, `amg` the set-up hierarchy) or behind the
+    diagonal scaling preconditioner (solver 17)."""
+    return _solve_krylov("COGMRES", _gmres_setters(opt, early=(("Unroll", opt.unroll), ("CGS", opt.cgs)),
+                                                   late=(("Logging", 3), ("PrintLevel", 3))),     # ioutdat (test/ij.c:686); inert here
+                         opt, A, b, x, comm, amg, amg_max_iter=opt.mg_max_iter)
+
+
+def solve_flexgmres(opt, A, b, x, comm=0, amg=None, ilu=None):
+    """test/ij.c:7565-7578, 7720-7724, 7855-7943: FlexGMRES behind BoomerAMG (solver 61, `amg` the set-up hierarchy), ILU (82) or
+    the diagonal scaling preconditioner (solver 60); b and x may be multivectors (-nc N).  modify_pc stays the default, which
+    changes nothing."""
+    return _solve_krylov("FlexGMRES", _gmres_setters(opt, late=(("Logging", 1), ("PrintLevel", 3))),   # ioutdat; inert here
+                         opt, A, b, x, comm, amg, amg_max_iter=opt.mg_max_iter, check_precond=True, ilu=ilu)
+
+
+def solve_lgmres(opt, A, b, x, comm=0, amg=None):
+    """test/ij.c:7338-7560: LGMRES behind BoomerAMG (the reference's solver 51, `amg` the set-up hierarchy) or behind the diagonal
+    scaling preconditioner (50); b and x may be multivectors (-nc N).  AugDim follows KDim, which it is clamped against."""
+    return _solve_krylov("LGMRES", _gmres_setters(opt, early=(("AugDim", opt.aug_dim),),
+                                                  late=(("Logging", 1), ("PrintLevel", 3))),      # ioutdat; inert here
+                         opt, A, b, x, comm, amg, amg_max_iter=opt.mg_max_iter, check_precond=True)
+
+
+def solve_bicgstab(opt, A, b, x, comm=0, amg=None):
+    """test/ij.c:8002-8172, 8324-8367: BiCGSTAB behind BoomerAMG (solver 9, `amg` the set-up hierarchy, run as a preconditioner:
+    SetTol 0, SetMaxIter precon_cycles; the iteration limit is then mg_max_iter, test/ij.c:8156) or behind the diagonal
+    scaling preconditioner (solver 10); b and x may be multivectors (-nc N).  The reference driver also asks for the
+    solver's table of norms (ioutdat); this one prints the closing lines alone, as for its other solvers."""
+    return _solve_krylov("BiCGSTAB", (("MaxIter", opt.max_iter), ("Tol", opt.tol), ("AbsoluteTol", 0.0), ("Logging", 1), ("PrintLevel", 0)),
+                         opt, A, b, x, comm, amg, amg_max_iter=opt.mg_max_iter)
 
 
 def create_ilu(opt, preconditioner=False):
@@ -712,45 +736,28 @@ def run_ilu(opt, A, comm=0, rank=0, allreduce=None, out=None, memory_location=DE
     import sys
     out = out or sys.stdout
     L = B.load_library()
+    alone = SOLVERS[opt.solver].method == "ILU"
     if memory_location == DEVICE:
         L.hypre_ParCSRMatrixMigrate(A, DEVICE)
-    elif opt.solver != 80:
+    elif not alone:
         raise SystemExit("ij: -solver %d in host memory: the Krylov solvers run on the device only" % opt.solver)
-    Am = A.contents
-    first, nglob = int(Am.row_starts[0]), int(Am.global_num_rows)
-    b, x0 = build_rhs_host(opt, A, rank=rank, allreduce=allreduce)
-    vec = lambda v: B.parvec_from_numpy(v, comm=comm, global_size=nglob, first=first, location=memory_location)
-    if b is None:
-        if memory_location != DEVICE:
-            raise SystemExit("ij: -xisone needs a product with A, which runs on the device only")
-        ones, db = vec(np.ones(len(x0))), vec(np.zeros(len(x0)))
-        L.hypre_ParCSRMatrixMatvec(1.0, A, ones, 0.0, db)
-        L.hypre_ParVectorDestroy(ones)
-    else:
-        db = vec(b)
-    dx = vec(x0)
-    ilu = create_ilu(opt, preconditioner=opt.solver != 80)
-    if opt.solver == 80:
+    db, dx = device_vectors(opt, A, comm, rank, allreduce, memory_location)
+    ilu = create_ilu(opt, preconditioner=not alone)
+    if alone:
         L.HYPRE_ILUSetup(ilu, A, db, dx)
         L.HYPRE_ILUSolve(ilu, A, db, dx)
         its, rel = C.c_int(), C.c_double()
         L.HYPRE_ILUGetNumIterations(ilu, C.byref(its))
         L.HYPRE_ILUGetFinalRelativeResidualNorm(ilu, C.byref(rel))
         its, rel = its.value, rel.value
-        lines = ["", "hypre_ILU Iterations = %d" % its, "Final Relative Residual Norm = %e" % rel, ""]
-    elif opt.solver == 81:
-        its, rel = _solve_gmres_family("GMRES", opt, A, db, dx, comm, None, ilu=ilu)
-        lines = ["", "GMRES Iterations = %d" % its, "Final GMRES Relative Residual Norm = %e" % rel, ""]
     else:
-        its, rel = _solve_gmres_family("FlexGMRES", opt, A, db, dx, comm, None, late=(("Logging", 1), ("PrintLevel", 3)), check_precond=True,
-                                       ilu=ilu)
-        lines = ["", "FlexGMRES Iterations = %d" % its, "Final FlexGMRES Relative Residual Norm = %e" % rel, ""]
+        its, rel = krylov_solver(opt)(opt, A=A, b=db, x=dx, comm=comm, amg=None, ilu=ilu)
     L.HYPRE_ClearError(256)
     B.check()
     L.HYPRE_ILUDestroy(ilu)
     L.hypre_ParVectorDestroy(db); L.hypre_ParVectorDestroy(dx)
     if rank == 0:
-        out.write("\n".join(lines) + "\n")
+        out.write("\n".join(closing_lines(opt, its, rel)) + "\n")
         out.flush()
     return its, rel
 
@@ -810,17 +817,7 @@ def run_hybrid(opt, A, comm=0, rank=0, allreduce=None, out=None):
     test/ij.c:4419-4432.  Returns (iterations, AMG iterations, diagonally scaled iterations, final relative residual norm)."""
     L = B.load_library()
     L.hypre_ParCSRMatrixMigrate(A, DEVICE)
-    Am = A.contents
-    first, nglob = int(Am.row_starts[0]), int(Am.global_num_rows)
-    b, x0 = build_rhs_host(opt, A, rank=rank, allreduce=allreduce)
-    if b is None:
-        ones = B.parvec_from_numpy(np.ones(len(x0)), comm=comm, global_size=nglob, first=first)
-        db = B.parvec_from_numpy(np.zeros(len(x0)), comm=comm, global_size=nglob, first=first)
-        L.hypre_ParCSRMatrixMatvec(1.0, A, ones, 0.0, db)
-        L.hypre_ParVectorDestroy(ones)
-    else:
-        db = B.parvec_from_numpy(b, comm=comm, global_size=nglob, first=first)
-    dx = B.parvec_from_numpy(x0, comm=comm, global_size=nglob, first=first)
+    db, dx = device_vectors(opt, A, comm, rank, allreduce)
     h = create_hybrid(opt)
     L.HYPRE_ParCSRHybridSetup(h, A, db, dx)
     L.HYPRE_ParCSRHybridSolve(h, A, db, dx)
@@ -838,64 +835,6 @@ def run_hybrid(opt, A, comm=0, rank=0, allreduce=None, out=None):
                              "DSCG_Iterations = %d" % dscg_its.value, "Final Relative Residual Norm = %e" % rel.value, ""]) + "\n")
         out.flush()
     return its.value, pcg_its.value, dscg_its.value, rel.value
-
-
-def solve_gmres(opt, amg, A, b, x, comm=0):
-    """test/ij.c:6715-6790, 6919-6925, 7190-7215: AMG-GMRES (solver 3)."""
-    return _solve_gmres_family("GMRES", opt, A, b, x, comm, amg, amg_first=True)
-
-
-def solve_cogmres(opt, A, b, x, comm=0, amg=None):
-    """test/ij.c:8426-8440, 8583-8598, 8710-8722: COGMRES behind BoomerAMG (solver 16, `amg` the set-up hierarchy) or behind the
-    diagonal scaling preconditioner (solver 17)."""
-    return _solve_gmres_family("COGMRES", opt, A, b, x, comm, amg, early=(("Unroll", opt.unroll), ("CGS", opt.cgs)),
-                               late=(("Logging", 3), ("PrintLevel", 3)),            # ioutdat (test/ij.c:686); inert here
-                               amg_max_iter=opt.mg_max_iter)
-
-
-def solve_flexgmres(opt, A, b, x, comm=0, amg=None):
-    """test/ij.c:7565-7578, 7720-7724, 7892-7943: FlexGMRES behind BoomerAMG (solver 61, `amg` the set-up hierarchy) or behind the
-    diagonal scaling preconditioner (solver 60); b and x may be multivectors (-nc N).  modify_pc stays the default, which
-    changes nothing."""
-    return _solve_gmres_family("FlexGMRES", opt, A, b, x, comm, amg, late=(("Logging", 1), ("PrintLevel", 3)),   # ioutdat; inert here
-                               amg_max_iter=opt.mg_max_iter, check_precond=True)
-
-
-def solve_lgmres(opt, A, b, x, comm=0, amg=None):
-    """test/ij.c:7338-7560: LGMRES behind BoomerAMG (the reference's solver 51, `amg` the set-up hierarchy) or behind the diagonal
-    scaling preconditioner (50); b and x may be multivectors (-nc N).  AugDim follows KDim, which it is clamped against."""
-    return _solve_gmres_family("LGMRES", opt, A, b, x, comm, amg, early=(("AugDim", opt.aug_dim),),
-                               late=(("Logging", 1), ("PrintLevel", 3)),            # ioutdat; inert here
-                               amg_max_iter=opt.mg_max_iter, check_precond=True)
-
-
-def solve_bicgstab(opt, A, b, x, comm=0, amg=None):
-    """test/ij.c:8002-8172, 8324-8367: BiCGSTAB behind BoomerAMG (solver 9, `amg` the set-up hierarchy, run as a preconditioner:
-    SetTol 0, SetMaxIter precon_cycles; the iteration limit is then mg_max_iter, test/ij.c:8156) or behind the diagonal
-    scaling preconditioner (solver 10); b and x may be multivectors (-nc N).  The reference driver also asks for the
-    solver's table of norms (ioutdat); this one prints the closing lines alone, as for its other solvers."""
-    L = B.load_library()
-    g = C.c_void_p()
-    L.HYPRE_ParCSRBiCGSTABCreate(comm, C.byref(g))
-    L.HYPRE_BiCGSTABSetMaxIter(g, opt.max_iter)
-    L.HYPRE_BiCGSTABSetTol(g, opt.tol)
-    L.HYPRE_BiCGSTABSetAbsoluteTol(g, 0.0)
-    L.HYPRE_BiCGSTABSetLogging(g, 1)
-    L.HYPRE_BiCGSTABSetPrintLevel(g, 0)
-    if amg is not None:
-        L.HYPRE_BoomerAMGSetTol(amg, 0.0)
-        L.HYPRE_BoomerAMGSetMaxIter(amg, opt.precon_cycles)
-        L.HYPRE_BiCGSTABSetMaxIter(g, opt.mg_max_iter)
-        L.HYPRE_BiCGSTABSetPrecond(g, C.cast(L.HYPRE_BoomerAMGSolve, C.c_void_p), None, amg)
-    else:
-        L.HYPRE_BiCGSTABSetPrecond(g, C.cast(L.HYPRE_ParCSRDiagScale, C.c_void_p), C.cast(L.HYPRE_ParCSRDiagScaleSetup, C.c_void_p), None)
-    L.HYPRE_BiCGSTABSetup(g, A, b, x)
-    L.HYPRE_BiCGSTABSolve(g, A, b, x)
-    its, rel = C.c_int(), C.c_double()
-    L.HYPRE_BiCGSTABGetNumIterations(g, C.byref(its))
-    L.HYPRE_BiCGSTABGetFinalRelativeResidualNorm(g, C.byref(rel))
-    L.HYPRE_ParCSRBiCGSTABDestroy(g)
-    return its.value, rel.value
 
 
 def main(argv=None):
