@@ -123,6 +123,18 @@ struct AmgPrivate
    // relax 15: one unpreconditioned-CG solver per level, created at the first cycle that needs it
    std::vector<HYPRE_Solver> cg_smoothers;
 
+   // ILU as a level smoother (smooth_type 5 | 15; par_amg.c:223-231 and :179-181 for the defaults).  The parameters are
+   // handed to one HYPRE_ILU per level < smooth_num_levels when Setup has built the hierarchy (par_amg_setup.c:3700-3727).
+   int    smooth_type = 6, smooth_num_levels = 0, smooth_num_sweeps = 1;
+   int    ilu_type = 0, ilu_lfil = 0, ilu_max_row_nnz = 20, ilu_max_iter = 1, ilu_tri_solve = 1, ilu_lower_jacobi_iters = 5,
+          ilu_upper_jacobi_iters = 5, ilu_reordering_type = 1, ilu_iter_setup_type = 0;
+   double ilu_droptol = 0.01;
+   std::vector<HYPRE_Solver> ilu_smoothers;   // [min(smooth_num_levels, num_levels)], made by Setup, freed with the hierarchy
+   double *d_cg_scalars = nullptr;            // smooth_type 15: gamma, gammaold, <P, V>, stop flag (ILU_CG_*), device
+   int    smoother_visits = 0, smoother_readbacks = 0;   // of the last cycle: level visits the smoother served, and the
+                                                         // reductions read back to the host inside them
+   bool   ilu_smoothing() const { return smooth_num_levels > 0 && (smooth_type == 5 || smooth_type == 15); }
+
    // coarsest level: factors of the reference's pivot-free elimination
    // (utilities/gselim.h), computed once on the host, applied on the device
    double *d_coarse_lu = nullptr;   // n*n row-major: U on/above the diagonal, multipliers below
@@ -229,6 +241,17 @@ void launch_cheby_start(const double *f, const double *t, const double *ds, doub
                         double *orig, double *r, double *tmp, size_t n, hipStream_t s);
 void launch_cheby_step(const double *r, const double *v, const double *ds, const double *orig, double mult, bool last,
                        double *u, double *tmp, size_t n, hipStream_t s);
+
+// ILU as a level smoother.  The body of HYPRE_ILUSolve for a caller that has checked the fine-level plans itself (the
+// cycle: an AMG solve verifies them once, not at every application); the residual product is skipped when u->all_zeros.
+HYPRE_Int ilu_solve_core(HYPRE_Solver solver, hypre_ParCSRMatrix *A, hypre_ParVector *f, hypre_ParVector *u, bool verify_plans);
+// the conjugate-gradient acceleration of smooth_type 15 (ilu_smoother_kernels.hip): slots of its scalar block in device
+// memory, the two sums left there, the direction and the update that read them
+enum { ILU_CG_GAMMA = 0, ILU_CG_GAMMAOLD = 1, ILU_CG_PV = 2, ILU_CG_STOP = 3, ILU_CG_SCALARS = 4 };
+void launch_ilu_cg_dot(const double *x, const double *y, size_t n, double *sc, int which, hipStream_t s);
+void launch_ilu_cg_direction(const double *sc, int first, const double *z, double *p, size_t n, hipStream_t s);
+void launch_ilu_cg_direction_value(double beta, const double *z, double *p, size_t n, hipStream_t s);
+void launch_ilu_cg_update(const double *sc, const double *p, const double *v, double *u, double *r, double *z, size_t n, hipStream_t s);
 
 void launch_jacobi_update(const double *u_in, const double *r, const double *d, const int *marker, int mval,
                           double *u_out, size_t n, hipStream_t s);

@@ -434,7 +434,7 @@ void launch_mc_small_sweep(int num_colors, int direction, const int *cstart, con
 // one per kernel file: loads its code object (runtime.cpp: ensure_device)
 void preload_cheby_kernels(); void preload_gs_kernels(); void preload_interp_kernels(); void preload_vector_kernels();
 void preload_rap_kernels(); void preload_setup_kernels(); void preload_spmv_kernels(); void preload_mass_kernels();
-void preload_ilu_kernels(); void preload_ilu_iter_kernels();
+void preload_ilu_kernels(); void preload_ilu_iter_kernels(); void preload_ilu_smoother_kernels();
 // setup_kernels.hip: strength of connection, PMIS, coarse numbering and smoother diagonals of a single-rank level
 void device_strength(int n, const int *Ai, const int *Aj, const double *Aa, double theta, double max_row_sum,
                      int **Si_out, int **Sj_out, int *nnz_out, hipStream_t s);
@@ -495,6 +495,7 @@ void launch_pcg_direction(double beta, const double *s, double *p, size_t n, hip
 double global_sum(MPI_Comm comm, double v);     // scalar all-reduce over a communicator (identity on one rank)
 void   dev_allreduce_sum(MPI_Comm comm, double *d_buf, int n);                 // in place, device memory, stream-ordered
 void   dev_global_sums(MPI_Comm comm, double *d_vals, int n, double *h_out);   // n device partials -> global sums on the host
+long  &reduction_readbacks();       // dev_global_sums calls so far: each is a copy to the host and a stream synchronisation
 void launch_scale_copy(double b, const double *x, double *y, size_t n, hipStream_t s);   // y = b*x
 
 }  // namespace hamd

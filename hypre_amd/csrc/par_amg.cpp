@@ -1,6 +1,7 @@
 // hypre_amd — BoomerAMG solver object: creation, parameters, destruction.
 // Reference: parcsr_ls/par_amg.c:28-520 (defaults at :162-316), HYPRE_parcsr_amg.c.
 #include "amg_internal.hpp"
+#include <string>
 
 using namespace hamd;
 
@@ -70,6 +71,8 @@ void amg_free_hierarchy(hypre_ParAMGData *d)
       pv->release_device();
       for (HYPRE_Solver cg : pv->cg_smoothers) { if (cg) { HYPRE_ParCSRPCGDestroy(cg); } }
       pv->cg_smoothers.clear();
+      for (HYPRE_Solver ilu : pv->ilu_smoothers) { if (ilu) { HYPRE_ILUDestroy(ilu); } }
+      pv->ilu_smoothers.clear();
    }
    const int L = d->num_levels;
    if (d->A_array)
@@ -291,10 +294,93 @@ HYPRE_Int HYPRE_BoomerAMGSetRAP2(HYPRE_Solver s, HYPRE_Int v)
 { AMG_DATA(s, d); (void) d; return gate("HYPRE_BoomerAMGSetRAP2: the coarse operator is the Galerkin triple product (0 only)", v == 0); }
 HYPRE_Int HYPRE_BoomerAMGSetRestriction(HYPRE_Solver s, HYPRE_Int v)
 { AMG_DATA(s, d); (void) d; return gate("HYPRE_BoomerAMGSetRestriction: R = P^T (0 only)", v == 0); }
+// ---- ILU as a level smoother (smooth_type 5, and 15 with the conjugate-gradient acceleration around it) -----------------
+// Of the reference's complex smoothers ILU is the one built.  A positive level count is accepted only while the stored
+// type is 5 or 15 (so the type is set first), and a type other than these is refused while the count is positive; a
+// fresh solver (type 6) refuses a positive count with the message it always gave.
+namespace {
+const char *const SMOOTH_REFUSAL = "HYPRE_BoomerAMGSetSmoothNumLevels: Schwarz / ILU / FSAI / ParaSails smoothers are not built (0 only)";
+AmgPrivate *priv(hypre_ParAMGData *d) { return (AmgPrivate *) d->amd_private; }
+}  // namespace
 HYPRE_Int HYPRE_BoomerAMGSetSmoothNumLevels(HYPRE_Solver s, HYPRE_Int v)
-{ AMG_DATA(s, d); (void) d; return gate("HYPRE_BoomerAMGSetSmoothNumLevels: Schwarz / ILU / FSAI / ParaSails smoothers are not built (0 only)", v == 0); }
-HYPRE_Int HYPRE_BoomerAMGSetSmoothType(HYPRE_Solver s, HYPRE_Int v) { AMG_DATA(s, d); (void) d; (void) v; return hypre_error_flag; }    // inert while SmoothNumLevels is 0
-HYPRE_Int HYPRE_BoomerAMGSetSmoothNumSweeps(HYPRE_Solver s, HYPRE_Int v) { AMG_DATA(s, d); (void) d; (void) v; return hypre_error_flag; }
+{
+   AMG_DATA(s, d);
+   AmgPrivate *pv = priv(d);
+   if (v < 0 || (v > 0 && pv->smooth_type != 5 && pv->smooth_type != 15)) { return gate(SMOOTH_REFUSAL, false); }
+   pv->smooth_num_levels = v;
+   return hypre_error_flag;
+}
+HYPRE_Int HYPRE_BoomerAMGSetSmoothType(HYPRE_Solver s, HYPRE_Int v)
+{
+   AMG_DATA(s, d);
+   AmgPrivate *pv = priv(d);
+   if (pv->smooth_num_levels > 0 && v != 5 && v != 15) { return gate(SMOOTH_REFUSAL, false); }
+   pv->smooth_type = v;
+   return hypre_error_flag;
+}
+HYPRE_Int HYPRE_BoomerAMGSetSmoothNumSweeps(HYPRE_Solver s, HYPRE_Int v)
+{ AMG_DATA(s, d); if (v < 1) { hypre_error_in_arg(2); return hypre_error_flag; } priv(d)->smooth_num_sweeps = v; return hypre_error_flag; }
+// parameters of the level smoothers (par_amg.c:4231-4420), handed on by Setup as par_amg_setup.c:3710-3726 hands them on
+HYPRE_Int HYPRE_BoomerAMGSetILUType(HYPRE_Solver s, HYPRE_Int v)
+{
+   AMG_DATA(s, d);
+   if (v != 0)
+   {
+      hypre_error_in_arg(2);
+      hypre_error_w_msg(HYPRE_ERROR_GENERIC, ("HYPRE_BoomerAMGSetILUType: ilu_type " + std::to_string(v) + " is outside the scope of this library "
+                                              "(0: block Jacobi with ILU(k); ILUT and the Schur, NSH, RAS, ddPQ and RAP types are not served)").c_str());
+      return hypre_error_flag;
+   }
+   priv(d)->ilu_type = v;
+   return hypre_error_flag;
+}
+HYPRE_Int HYPRE_BoomerAMGSetILULevel(HYPRE_Solver s, HYPRE_Int v)
+{ AMG_DATA(s, d); if (v < 0) { hypre_error_in_arg(2); return hypre_error_flag; } priv(d)->ilu_lfil = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_BoomerAMGSetILULocalReordering(HYPRE_Solver s, HYPRE_Int v)
+{ AMG_DATA(s, d); if (v != 0 && v != 1) { hypre_error_in_arg(2); return hypre_error_flag; } priv(d)->ilu_reordering_type = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_BoomerAMGSetILUMaxIter(HYPRE_Solver s, HYPRE_Int v)
+{ AMG_DATA(s, d); if (v < 0) { hypre_error_in_arg(2); return hypre_error_flag; } priv(d)->ilu_max_iter = v; return hypre_error_flag; }
+// 1: direct triangular solves; 0: Jacobi sweeps, the reference's meaning (HYPRE_ILUSetTriSolve itself keeps refusing 0)
+HYPRE_Int HYPRE_BoomerAMGSetILUTriSolve(HYPRE_Solver s, HYPRE_Int v)
+{ AMG_DATA(s, d); if (v != 0 && v != 1) { hypre_error_in_arg(2); return hypre_error_flag; } priv(d)->ilu_tri_solve = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_BoomerAMGSetILULowerJacobiIters(HYPRE_Solver s, HYPRE_Int v)
+{ AMG_DATA(s, d); if (v < 0) { hypre_error_in_arg(2); return hypre_error_flag; } priv(d)->ilu_lower_jacobi_iters = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_BoomerAMGSetILUUpperJacobiIters(HYPRE_Solver s, HYPRE_Int v)
+{ AMG_DATA(s, d); if (v < 0) { hypre_error_in_arg(2); return hypre_error_flag; } priv(d)->ilu_upper_jacobi_iters = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_BoomerAMGSetILUDroptol(HYPRE_Solver s, HYPRE_Real v)      // stored; ILU(k) drops by level, not by size
+{ AMG_DATA(s, d); priv(d)->ilu_droptol = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_BoomerAMGSetILUMaxRowNnz(HYPRE_Solver s, HYPRE_Int v)     // stored; read by ILUT only
+{ AMG_DATA(s, d); priv(d)->ilu_max_row_nnz = v; return hypre_error_flag; }
+HYPRE_Int HYPRE_BoomerAMGSetILUIterSetupType(HYPRE_Solver s, HYPRE_Int v)
+{
+   AMG_DATA(s, d);
+   if (v != 0) { return gate("HYPRE_BoomerAMGSetILUIterSetupType: the iterative ILU setup is not built (0 only)", false); }
+   priv(d)->ilu_iter_setup_type = v;
+   return hypre_error_flag;
+}
+// the ILU object of a level (NULL where the level has none, or before Setup): launch statistics and parameters for tests
+HYPRE_Int hypre_amd_BoomerAMGGetSmoother(HYPRE_Solver s, HYPRE_Int level, HYPRE_Solver *ilu)
+{
+   AMG_DATA(s, d);
+   if (!ilu) { hypre_error_in_arg(3); return hypre_error_flag; }
+   const AmgPrivate *pv = priv(d);
+   *ilu = (level >= 0 && level < (HYPRE_Int) pv->ilu_smoothers.size()) ? pv->ilu_smoothers[(size_t) level] : nullptr;
+   return hypre_error_flag;
+}
+// the smoother settings as they stand, and of the last cycle: the level visits the smoother served and the reductions that
+// were read back to the host inside them (0 with the fused acceleration); any pointer may be NULL
+HYPRE_Int hypre_amd_BoomerAMGGetSmootherStats(HYPRE_Solver s, HYPRE_Int *smooth_type, HYPRE_Int *smooth_num_levels, HYPRE_Int *smooth_num_sweeps,
+                                              HYPRE_Int *visits, HYPRE_Int *readbacks)
+{
+   AMG_DATA(s, d);
+   const AmgPrivate *pv = priv(d);
+   if (smooth_type) { *smooth_type = pv->smooth_type; }
+   if (smooth_num_levels) { *smooth_num_levels = pv->smooth_num_levels; }
+   if (smooth_num_sweeps) { *smooth_num_sweeps = pv->smooth_num_sweeps; }
+   if (visits) { *visits = pv->smoother_visits; }
+   if (readbacks) { *readbacks = pv->smoother_readbacks; }
+   return hypre_error_flag;
+}
 HYPRE_Int HYPRE_BoomerAMGSetAdditive(HYPRE_Solver s, HYPRE_Int v)
 { AMG_DATA(s, d); (void) d; return gate("HYPRE_BoomerAMGSetAdditive: additive cycles are not built (-1 only)", v == -1); }
 HYPRE_Int HYPRE_BoomerAMGSetMultAdditive(HYPRE_Solver s, HYPRE_Int v)

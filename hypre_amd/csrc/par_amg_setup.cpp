@@ -1822,6 +1822,22 @@ HYPRE_Int hypre_BoomerAMGSetup(void *amg_vdata, hypre_ParCSRMatrix *A, hypre_Par
       return hypre_error_flag;
    }
    AmgPrivate *pv = (AmgPrivate *) d->amd_private;
+   if (pv->ilu_smoothing())
+   {
+      // ILU as a level smoother (smooth_type 5 | 15): what it does not serve is refused before anything is built
+      const char *why = nullptr;
+      if (comm_size(A->comm) > 1) { why = "hypre_BoomerAMGSetup: ILU smoothing (smooth_type 5 | 15) on more than one rank is not built"; }
+      else if ((f && f->local_vector && f->local_vector->num_vectors > 1) || (u && u->local_vector && u->local_vector->num_vectors > 1))
+      {
+         why = "ILU smoothing doesn't support multicomponent vectors";          // par_amg_setup.c:3703-3708
+      }
+      else if (pv->mixed_precision) { why = "hypre_BoomerAMGSetup: ILU smoothing (smooth_type 5 | 15) doesn't support the mixed-precision hierarchy"; }
+      if (why)
+      {
+         hypre_error_w_msg(HYPRE_ERROR_GENERIC, why);
+         return hypre_error_flag;
+      }
+   }
    amg_free_hierarchy(d);
    // A (re-)setup is the caller telling the library that the matrix is what it is NOW: whatever earlier products cached for
    // its two blocks — tile tables, staged column pattern, value codes and slice form, triangles, colour classes, level
@@ -2198,7 +2214,7 @@ HYPRE_Int hypre_BoomerAMGSetup(void *amg_vdata, hypre_ParCSRMatrix *A, hypre_Par
    d->Vtemp = new_vec(comm, A->global_num_rows, A->row_starts, target);
    d->Ztemp = new_vec(comm, A->global_num_rows, A->row_starts, target);
    d->Rtemp = nullptr; d->Ptemp = nullptr;
-   if (uses_cheby)
+   if (uses_cheby || (pv->ilu_smoothing() && pv->smooth_type == 15))
    {
       d->Ptemp = new_vec(comm, A->global_num_rows, A->row_starts, target);
       d->Rtemp = new_vec(comm, A->global_num_rows, A->row_starts, target);
@@ -2297,6 +2313,31 @@ HYPRE_Int hypre_BoomerAMGSetup(void *amg_vdata, hypre_ParCSRMatrix *A, hypre_Par
    else
    {
       for (int l = 0; l < num_levels - 1; l++) { hypre_amd_ParCSRMatrixKeepTranspose(d->P_array[l]); }
+   }
+   // ILU as a level smoother: one HYPRE_ILU per level j < smooth_num_levels, the coarsest included when the count reaches it
+   // (par_amg_setup.c:3484, 3700-3727), on the level's operator where the hierarchy lives.  Setup factors on the host and
+   // uploads the factors of a device operator; the finest level's, when the caller migrates A after this call, go up at
+   // the first cycle.
+   if (pv->ilu_smoothing())
+   {
+      const int ns = std::min<int>(pv->smooth_num_levels, num_levels);
+      pv->ilu_smoothers.assign((size_t) ns, nullptr);
+      for (int j = 0; j < ns && !hypre_error_flag; j++)
+      {
+         HYPRE_Solver &sm = pv->ilu_smoothers[(size_t) j];
+         HYPRE_ILUCreate(&sm);
+         HYPRE_ILUSetType(sm, pv->ilu_type);
+         HYPRE_ILUSetLocalReordering(sm, pv->ilu_reordering_type);
+         HYPRE_ILUSetMaxIter(sm, pv->ilu_max_iter);
+         hypre_amd_ILUSetIterativeTriSolve(sm, pv->ilu_tri_solve == 0 ? 1 : 0);
+         HYPRE_ILUSetLowerJacobiIters(sm, pv->ilu_lower_jacobi_iters);
+         HYPRE_ILUSetUpperJacobiIters(sm, pv->ilu_upper_jacobi_iters);
+         HYPRE_ILUSetTol(sm, 0.);
+         HYPRE_ILUSetLogging(sm, 0);
+         HYPRE_ILUSetPrintLevel(sm, 0);
+         HYPRE_ILUSetLevelOfFill(sm, pv->ilu_lfil);
+         HYPRE_ILUSetup(sm, d->A_array[j], d->F_array[j], d->U_array[j]);
+      }
    }
    if (own_host_A0) { hypre_ParCSRMatrixDestroy(hostA[0]); }
    return hypre_error_flag;

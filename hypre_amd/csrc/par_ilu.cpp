@@ -312,9 +312,15 @@ struct Ops
       return device ? std::sqrt(hypre_ParVectorInnerProd(d->ftemp, d->ftemp)) : norm_of(d->h_ftemp.data());
    }
    double rhs_norm() const { return device ? std::sqrt(hypre_ParVectorInnerProd(f, f)) : norm_of(f->local_vector->data); }
-   // hypre_ILUSolveLU: u += (L D^-1 U)^-1 (f - A u)
+   // hypre_ILUSolveLU: u += (L D^-1 U)^-1 (f - A u).  An iterate known to be zero (all_zeros: hypre_ParVectorSetZeros, the
+   // cycle on the way down) needs no product: f - A 0 is f, the same number, so f itself is the right-hand side.
    void apply()
    {
+      if (u->all_zeros && f->local_vector->data != u->local_vector->data)
+      {
+         apply_factors(f->local_vector->data);
+         return;
+      }
       residual();
       apply_factors(device ? d->ftemp->local_vector->data : d->h_ftemp.data());
    }
@@ -582,6 +588,13 @@ HYPRE_Int HYPRE_ILUSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVec
 // 1) no norm is computed: max_iter applications, each one product with A and the two triangular solves.
 HYPRE_Int HYPRE_ILUSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector f, HYPRE_ParVector u)
 {
+   return hamd::ilu_solve_core(solver, A, f, u, true);
+}
+
+}  // extern "C"
+
+HYPRE_Int hamd::ilu_solve_core(HYPRE_Solver solver, hypre_ParCSRMatrix *A, hypre_ParVector *f, hypre_ParVector *u, bool verify_plans)
+{
    if (refuse_null(solver)) { return hypre_error_flag; }
    hypre_amd_ILUData *d = D(solver);
    if (!d->is_setup)
@@ -631,7 +644,7 @@ HYPRE_Int HYPRE_ILUSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVec
 
    QuietSync quiet;
    struct Finish { QuietSync &q; ~Finish() { q.restore(); maybe_sync(); } } finish{quiet};
-   if (device) { verify_par_plans(A); }
+   if (device && verify_plans) { verify_par_plans(A); }
    d->num_iterations = 0;
    d->norms.clear();
    if (print)
@@ -707,6 +720,8 @@ HYPRE_Int HYPRE_ILUSolve(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVec
    }
    return hypre_error_flag;
 }
+
+extern "C" {
 
 // The two triangular solves alone, without the product with A: u += (L D^-1 U)^-1 f, on the device or on the host as f and
 // u lie.  For tests that compare the kernels with the host solve bit for bit (the residual product of a Solve has another

@@ -60,6 +60,7 @@ void AmgPrivate::release_device()
    if (mp_r) { hypre_ParVectorDestroy(mp_r); mp_r = nullptr; }
    if (mp_e) { hypre_ParVectorDestroy(mp_e); mp_e = nullptr; }
    if (mv_resid) { hypre_ParVectorDestroy(mv_resid); mv_resid = nullptr; }
+   if (d_cg_scalars) { hypre_Free(d_cg_scalars, HYPRE_MEMORY_DEVICE); d_cg_scalars = nullptr; }
 }
 
 double *AmgPrivate::level_diag(int level, int n)
@@ -181,7 +182,7 @@ static double *diag_scratch(size_t n)
    return buf;
 }
 
-namespace { int &cycle_fusion(); int &small_tail_on(); int &small_tail_forced_form(); }     // (defined with the cycle below)
+namespace { int &cycle_fusion(); int &smoother_fusion(); int &small_tail_on(); int &small_tail_forced_form(); }    // (defined with the cycle below)
 
 extern "C" {
 
@@ -544,6 +545,12 @@ int &cycle_fusion()
    return on;
 }
 // the smallest levels of a Jacobi V(1,1) cycle in one kernel of one workgroup (tail_kernels.hip; hypre_amd_SetSmallTail)
+int &smoother_fusion()
+{
+   static int on = [] { const char *e = getenv("HYPRE_AMD_SMOOTHER_FUSION"); return e ? atoi(e) : 1; }();
+   return on;
+}
+
 int &small_tail_on()
 {
    static int on = [] { const char *e = getenv("HYPRE_AMD_SMALL_TAIL"); return e ? atoi(e) : 1; }();
@@ -723,6 +730,48 @@ HYPRE_Int hypre_amd_SetSmallTailForm(HYPRE_Int form)
    return hypre_error_flag;
 }
 
+// The conjugate-gradient acceleration around the ILU level smoother (smooth_type 15) with its two inner products left on the
+// device from now on (default 1; ilu_smoother_kernels.hip): no read-back inside a level visit.  0: the reference's call
+// sequence on the library's vector routines, two read-backs per sweep.  Same bits either way.  on < 0: unchanged; returns
+// the setting.
+HYPRE_Int hypre_amd_SetSmootherFusion(HYPRE_Int on)
+{
+   if (on >= 0) { smoother_fusion() = on != 0; }
+   return smoother_fusion();
+}
+
+// Test hook: one pass of the fused acceleration's vector kernels through their launchers, on host arrays of n entries
+// (V is only read) and the four scalars: [the sum <R, Z>,] the direction, [the sum <P, V>,] the update.
+HYPRE_Int hypre_amd_ILUSmootherKernelTest(HYPRE_Int n, HYPRE_Real *scalars, HYPRE_Int first, HYPRE_Int zero_z, HYPRE_Int with_dots,
+                                          HYPRE_Real *U, HYPRE_Real *R, HYPRE_Real *P, HYPRE_Real *Z, const HYPRE_Real *V)
+{
+   if (n < 1) { hypre_error_in_arg(1); return hypre_error_flag; }
+   if (!scalars || !U || !R || !P || !Z || !V) { hypre_error_in_arg(2); return hypre_error_flag; }
+   if (!ensure_device())
+   {
+      hypre_error_w_msg(HYPRE_ERROR_GENERIC, "hypre_amd_ILUSmootherKernelTest: no HIP device is available");
+      return hypre_error_flag;
+   }
+   hipStream_t s = stream();
+   const size_t m = (size_t) n;
+   const size_t ld = (m + 1) & ~(size_t) 1;          // every vector starts on 16 bytes, as the library's own do
+   double *buf = hypre_TAlloc(double, 5 * ld + ILU_CG_SCALARS, HYPRE_MEMORY_DEVICE);
+   double *dU = buf, *dR = buf + ld, *dP = buf + 2 * ld, *dZ = buf + 3 * ld, *dV = buf + 4 * ld, *sc = buf + 5 * ld;
+   HYPRE_Real *host[4] = {U, R, P, Z};
+   for (int k = 0; k < 4; k++) { hypre_TMemcpy(buf + (size_t) k * ld, host[k], double, m, HYPRE_MEMORY_DEVICE, HYPRE_MEMORY_HOST); }
+   hypre_TMemcpy(dV, V, double, m, HYPRE_MEMORY_DEVICE, HYPRE_MEMORY_HOST);
+   hypre_TMemcpy(sc, scalars, double, (size_t) ILU_CG_SCALARS, HYPRE_MEMORY_DEVICE, HYPRE_MEMORY_HOST);
+   if (with_dots) { launch_ilu_cg_dot(dR, dZ, m, sc, 0, s); }
+   launch_ilu_cg_direction(sc, first != 0, dZ, dP, m, s);
+   if (with_dots) { launch_ilu_cg_dot(dP, dV, m, sc, 1, s); }
+   launch_ilu_cg_update(sc, dP, dV, dU, dR, zero_z ? dZ : nullptr, m, s);
+   HIP_CHECK(hipStreamSynchronize(s));
+   for (int k = 0; k < 4; k++) { hypre_TMemcpy(host[k], buf + (size_t) k * ld, double, m, HYPRE_MEMORY_HOST, HYPRE_MEMORY_DEVICE); }
+   hypre_TMemcpy(scalars, sc, double, (size_t) ILU_CG_SCALARS, HYPRE_MEMORY_HOST, HYPRE_MEMORY_DEVICE);
+   hypre_TFree(buf, HYPRE_MEMORY_DEVICE);
+   return hypre_error_flag;
+}
+
 // The cycle from level `first` down and back up to it (0: the whole cycle).  first > 0 is the entry of the multi-column driver
 // below: the levels above were cycled for all columns at once, F_array[first] holds the restricted residual of one column
 // and, with first_presmoothed, U_array[first] the sweep from zero the restriction's epilogue wrote; the result is left in
@@ -780,6 +829,18 @@ static HYPRE_Int amg_cycle_from(void *amg_vdata, hypre_ParVector **F_array, hypr
 
    HYPRE_Int cycle_nprocs = 1;
    hypre_MPI_Comm_size(A[0]->comm, &cycle_nprocs);
+   // ILU as a level smoother: on the levels below snl it replaces the relaxation, the coarsest level's direct solve included
+   // (par_cycle.c:477 stands before :491); the one-workgroup tail, the recorded graph and the restriction's fused first
+   // sweep start at a level >= snl or not at all
+   const int snl = pv->ilu_smoothing() ? std::min<int>(pv->smooth_num_levels, (int) pv->ilu_smoothers.size()) : 0;
+   pv->smoother_visits = pv->smoother_readbacks = 0;
+   if (snl > 0 && (pv->mixed_precision || cycle_nprocs > 1))
+   {
+      hypre_error_w_msg(HYPRE_ERROR_GENERIC, "hypre_BoomerAMGCycle: ILU smoothing (smooth_type 5 | 15) serves neither the mixed-precision hierarchy nor several ranks");
+      handle().fp32_values = saved_fp32;
+      handle().gs_threads = saved_gs_threads;
+      return 1;
+   }
    // ---- the smallest levels in one kernel of one workgroup (tail_kernels.hip): one rank, a plain V(1,1) cycle, Jacobi or
    // l1-Jacobi over all points with the smoother diagonals at hand, a direct solve on the coarsest level ----
    int st = -1;
@@ -798,6 +859,7 @@ static HYPRE_Int amg_cycle_from(void *amg_vdata, hypre_ParVector **F_array, hypr
             pv->small_tail_level = (first <= L - 2) ? first : -1;
          }
          st = pv->small_tail_level;
+         if (st >= 0 && st < snl) { st = snl <= L - 2 ? snl : -1; }
          for (int l = st; st >= 0 && l < L; l++)
          {
             const bool last = l == L - 1;
@@ -846,9 +908,10 @@ static HYPRE_Int amg_cycle_from(void *amg_vdata, hypre_ParVector **F_array, hypr
       {
          if (pv->graph_level < 0)
          {
-            for (int l = 1; l < L - 1; l++) { if (A[l]->global_num_rows <= (HYPRE_BigInt) pv->graph_rows) { pv->graph_level = l; break; } }
+            for (int l = std::max(1, snl); l < L - 1; l++) { if (A[l]->global_num_rows <= (HYPRE_BigInt) pv->graph_rows) { pv->graph_level = l; break; } }
          }
          gl = pv->graph_level;
+         if (gl >= 0 && gl < snl) { gl = pv->graph_level = snl; }
          if (gl >= L - 1) { gl = -1; }
       }
       if (gl < 0 && pv->graph_state) { pv->drop_graph(); }
@@ -940,7 +1003,90 @@ static HYPRE_Int amg_cycle_from(void *amg_vdata, hypre_ParVector **F_array, hypr
          zeros[(size_t) level] = 0;
          if (err) { break; }
       }
-      for (int j = 0; j < ((tail_here || replayed) ? 0 : num_sweep); j++)
+      // ---- ILU as the level's smoother (par_cycle.c:293-326, 388-393, 477-483, 614-636) ----
+      const bool smooth_here = level < snl && !tail_here && !replayed;
+      if (smooth_here)
+      {
+         const long readbacks_before = reduction_readbacks();
+         pv->smoother_visits++;
+         HYPRE_Solver sm = pv->ilu_smoothers[(size_t) level];
+         const double level_ops = A[level]->d_num_nonzeros;
+         hypre_Vector uv; hypre_ParVector up;
+         wrap(&uv, u.cur, n);
+         wrap_par(&up, &uv, A[level]->comm, A[level]->global_num_rows);
+         up.all_zeros = zeros[(size_t) level];
+         if (pv->smooth_type == 5 || L == 1)
+         {
+            // smooth_num_sweeps applications on (F, U); a hierarchy of one level takes num_grid_sweeps[0] of them, with
+            // either type (the reference's acceleration there works on vectors it never filled)
+            const int sweeps = L > 1 ? pv->smooth_num_sweeps : num_sweep;
+            for (int j = 0; j < sweeps && !err; j++)
+            {
+               cycle_op_count += level_ops;
+               ilu_solve_core(sm, A[level], F_array[level], &up, false);
+               if (hypre_error_flag) { err = 1; }
+            }
+         }
+         else if (!d->Rtemp || !d->Ptemp)
+         {
+            hypre_error_w_msg(HYPRE_ERROR_GENERIC, "hypre_BoomerAMGCycle: smooth_type 15 on a hierarchy the setup did not prepare for it");
+            err = 1;
+         }
+         else
+         {
+            // conjugate gradients on A with num_sweep ILU applications from zero as the preconditioner, smooth_num_sweeps steps
+            hypre_ParVectorSetLocalSize(d->Vtemp, n); hypre_ParVectorSetLocalSize(d->Ztemp, n);
+            hypre_ParVectorSetLocalSize(d->Rtemp, n); hypre_ParVectorSetLocalSize(d->Ptemp, n);
+            double *R = d->Rtemp->local_vector->data, *Pd = d->Ptemp->local_vector->data, *Z = d->Ztemp->local_vector->data, *V = vtemp;
+            const int cg_sweeps = pv->smooth_num_sweeps;
+            const bool fused = smoother_fusion() != 0;
+            if (!pv->d_cg_scalars) { pv->d_cg_scalars = hypre_TAlloc(double, ILU_CG_SCALARS, HYPRE_MEMORY_DEVICE); }
+            double *sc = pv->d_cg_scalars;
+            if (zeros[(size_t) level]) { launch_copy(R, fd, (size_t) n, s); }        // F - A 0
+            else { dev_par_matvec(-1.0, A[level], u.cur, 1.0, fd, R); }
+            if (fused) { launch_set(sc, 0.0, (size_t) ILU_CG_SCALARS, s); }
+            launch_set(Z, 0.0, (size_t) n, s);
+            double gamma = 0.0, gammaold = 0.0;
+            for (int jj = 0; jj < cg_sweeps && !err; jj++)
+            {
+               // Z = 0: by the set above, then by the update kernel of the sweep before (fused) or by a set of its own
+               if (jj > 0 && !fused) { hypre_ParVectorSetConstantValues(d->Ztemp, 0.0); }
+               d->Ztemp->all_zeros = 1;
+               for (int j = 0; j < num_sweep && !err; j++)
+               {
+                  cycle_op_count += level_ops;
+                  ilu_solve_core(sm, A[level], d->Rtemp, d->Ztemp, false);
+                  if (hypre_error_flag) { err = 1; }
+               }
+               if (err) { break; }
+               if (fused)
+               {
+                  launch_ilu_cg_dot(R, Z, (size_t) n, sc, 0, s);
+                  launch_ilu_cg_direction(sc, jj == 0, Z, Pd, (size_t) n, s);
+                  dev_par_matvec(1.0, A[level], Pd, 0.0, nullptr, V);
+                  launch_ilu_cg_dot(Pd, V, (size_t) n, sc, 1, s);
+                  launch_ilu_cg_update(sc, Pd, V, u.cur, R, jj + 1 < cg_sweeps ? Z : nullptr, (size_t) n, s);
+               }
+               else
+               {
+                  gammaold = gamma;
+                  gamma = hypre_ParVectorInnerProd(d->Rtemp, d->Ztemp);
+                  if (gamma == 0.0) { break; }       // a zero right-hand side: U stays (the reference divides 0 by 0)
+                  if (jj == 0) { hypre_ParVectorCopy(d->Ztemp, d->Ptemp); }
+                  else { launch_ilu_cg_direction_value(gamma / gammaold, Z, Pd, (size_t) n, s); }
+                  dev_par_matvec(1.0, A[level], Pd, 0.0, nullptr, V);
+                  const double alfa = gamma / hypre_ParVectorInnerProd(d->Ptemp, d->Vtemp);
+                  hypre_ParVectorAxpy(alfa, d->Ptemp, &up);
+                  hypre_ParVectorAxpy(-alfa, d->Vtemp, d->Rtemp);
+               }
+            }
+            d->Ztemp->all_zeros = 0;
+         }
+         zeros[(size_t) level] = 0;
+         pv->smoother_readbacks += (int) (reduction_readbacks() - readbacks_before);
+         if (err) { break; }
+      }
+      for (int j = 0; j < ((tail_here || replayed || smooth_here) ? 0 : num_sweep); j++)
       {
          int relax_points = 0, relax_local = d->relax_order;
          if (L == 1 && d->max_levels > 1) { relax_points = 0; relax_local = 0; }
@@ -1087,8 +1233,10 @@ static HYPRE_Int amg_cycle_from(void *amg_vdata, hypre_ParVector **F_array, hypr
          // read as zero, so the vector is cleared unless the first coarse
          // operation is known to overwrite all of it
          const int ctype = d->grid_relax_type[coarse == L - 1 ? 3 : 1];
-         const bool overwrites_all = (is_jacobi_type(ctype) && ctype != 0 && !(d->relax_order == 1 && coarse != L - 1) &&
-                                      !old_version && d->num_grid_sweeps[coarse == L - 1 ? 3 : 1] > 0) || is_ge_type(ctype);
+         // (an ILU level smoother adds its correction to the iterate: the zeros have to be there)
+         const bool overwrites_all = coarse >= snl &&
+                                     ((is_jacobi_type(ctype) && ctype != 0 && !(d->relax_order == 1 && coarse != L - 1) &&
+                                       !old_version && d->num_grid_sweeps[coarse == L - 1 ? 3 : 1] > 0) || is_ge_type(ctype));
          if (!overwrites_all) { launch_set(uc.cur, 0.0, (size_t) nc, s); }
          zeros[(size_t) coarse] = 1;
          dev_par_matvec(-1.0, A[fine], u.cur, 1.0, fd, vtemp);
@@ -1146,7 +1294,7 @@ static HYPRE_Int amg_cycle_from(void *amg_vdata, hypre_ParVector **F_array, hypr
          int flips = 0;
          {
             const int t = d->grid_relax_type[2];
-            if (is_jacobi_type(t))
+            if (is_jacobi_type(t) && fine >= snl)        // (an ILU level smoother works in place)
             {
                const int passes = (!old_version && d->relax_order == 1) ? 2 : 1;
                flips = d->num_grid_sweeps[2] * passes;
@@ -1205,6 +1353,7 @@ static HYPRE_Int amg_cycle_from(void *amg_vdata, hypre_ParVector **F_array, hypr
 static std::string multivector_refusal(const hypre_ParAMGData *d)
 {
    const AmgPrivate *pv = (const AmgPrivate *) d->amd_private;
+   if (pv && pv->ilu_smoothing()) { return "ILU smoothing doesn't support multicomponent vectors"; }
    if (pv && pv->mixed_precision) { return "hypre_BoomerAMGSolve: mixed precision doesn't support multicomponent vectors"; }
    if (d->grid_relax_points) { return "hypre_BoomerAMGSolve: grid_relax_points don't support multicomponent vectors"; }
    if (d->relax_order != 0) { return "hypre_BoomerAMGSolve: C/F-ordered relaxation doesn't support multicomponent vectors"; }

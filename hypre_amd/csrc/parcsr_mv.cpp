@@ -189,8 +189,14 @@ void dev_allreduce_sum(MPI_Comm comm, double *d_buf, int n)
 
 // Sum over the ranks of n doubles that sit in device memory, returned on the host: one device all-reduce and
 // one read-back when the transport takes device buffers (otherwise read back, then reduce on the host).
+long &reduction_readbacks()
+{
+   static long count = 0;
+   return count;
+}
 void dev_global_sums(MPI_Comm comm, double *d_vals, int n, double *h_out)
 {
+   reduction_readbacks()++;
    const hypre_amd_CommOps *o = comm_ops(comm);
    Handle &hd = handle();
    double *h = reduce_host((size_t) n);

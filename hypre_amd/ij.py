@@ -111,7 +111,12 @@ class IJOptions:
         self.ilu_iterative = 0        # 1: triangular solves as Jacobi sweeps (hypre_amd_ILUSetIterativeTriSolve); no command-line flag
         self.ilu_ljac_iters = 5       # sweeps of the lower solve (HYPRE_ILUSetLowerJacobiIters; test/ij.c default 5)
         self.ilu_ujac_iters = 5       # sweeps of the upper solve (HYPRE_ILUSetUpperJacobiIters)
-        self.ilu_sm_max_iter = 1      # -ilu_sm_max_iter: sweeps of ILU as a BoomerAMG smoother (-smtype 5, refused): accepted, no effect
+        self.ilu_sm_max_iter = 1      # -ilu_sm_max_iter: applications per call of ILU as a BoomerAMG smoother (HYPRE_BoomerAMGSetILUMaxIter)
+        # ILU as a level smoother of BoomerAMG (solvers 0, 1, 3), with the ilu_* fields above as its parameters; options only: the
+        # command line keeps refusing -smtype / -smlv
+        self.smooth_type = 6          # 5: ILU; 15: ILU inside conjugate-gradient steps; anything else has no effect
+        self.smooth_num_levels = 0    # levels, from the finest, the smoother replaces the relaxation on
+        self.smooth_num_sweeps = 1    # type 5: applications per level visit; type 15: conjugate-gradient steps
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise TypeError("unknown ij option %r" % k)
@@ -332,6 +337,18 @@ def create_amg(opt, memory_location=DEVICE):
     L.HYPRE_BoomerAMGSetChebyEigEst(s, opt.cheby_eig_est)
     L.HYPRE_BoomerAMGSetChebyVariant(s, opt.cheby_variant)
     L.HYPRE_BoomerAMGSetChebyScale(s, opt.cheby_scale)
+    if opt.smooth_num_levels > 0:
+        # test/ij.c:4590-4640: the type before the level count (the count is refused while the type is not 5 | 15)
+        L.HYPRE_BoomerAMGSetSmoothType(s, opt.smooth_type)
+        L.HYPRE_BoomerAMGSetSmoothNumLevels(s, opt.smooth_num_levels)
+        L.HYPRE_BoomerAMGSetSmoothNumSweeps(s, opt.smooth_num_sweeps)
+        L.HYPRE_BoomerAMGSetILUType(s, opt.ilu_type)
+        L.HYPRE_BoomerAMGSetILULevel(s, opt.ilu_lfil)
+        L.HYPRE_BoomerAMGSetILULocalReordering(s, opt.ilu_reordering)
+        L.HYPRE_BoomerAMGSetILUMaxIter(s, opt.ilu_sm_max_iter)
+        L.HYPRE_BoomerAMGSetILUTriSolve(s, 0 if opt.ilu_iterative else 1)
+        L.HYPRE_BoomerAMGSetILULowerJacobiIters(s, opt.ilu_ljac_iters)
+        L.HYPRE_BoomerAMGSetILUUpperJacobiIters(s, opt.ilu_ujac_iters)
     B.check()
     return s
 
@@ -434,6 +451,20 @@ def check_options(opt):
         raise SystemExit("ij: ilu_iterative is 0 (direct triangular solves) or 1 (Jacobi sweeps), ilu_ljac_iters and ilu_ujac_iters are >= 0")
     if opt.ilu_lfil < 0 or opt.ilu_reordering not in (0, 1):
         raise SystemExit("ij: -ilu_lfil takes a level of fill >= 0, -ilu_reordering 0 (none) or 1 (reverse Cuthill-McKee)")
+    if opt.smooth_num_levels < 0 or opt.smooth_num_sweeps < 1 or opt.ilu_sm_max_iter < 0:
+        raise SystemExit("ij: smooth_num_levels is >= 0, smooth_num_sweeps >= 1, -ilu_sm_max_iter >= 0")
+    if opt.smooth_num_levels > 0:
+        if opt.smooth_type not in (5, 15):
+            raise SystemExit("ij: smooth_num_levels %d with smooth_type %d: the level smoothers served are 5 (ILU) and 15 (ILU inside "
+                             "conjugate-gradient steps)" % (opt.smooth_num_levels, opt.smooth_type))
+        if opt.num_components > 1:
+            raise SystemExit("ij: -nc %d: ILU smoothing doesn't support multicomponent vectors" % opt.num_components)
+        if opt.P is not None and int(np.prod(opt.P)) > 1:
+            raise SystemExit("ij: ILU smoothing (smooth_type 5 | 15) on more than one rank is outside the scope of this driver")
+        if opt.mixed:
+            raise SystemExit("ij: ILU smoothing (smooth_type 5 | 15) doesn't support the mixed-precision hierarchy")
+        if spec.precond != "amg" or opt.hybrid:
+            raise SystemExit("ij: smooth_num_levels is read by BoomerAMG alone or behind PCG or GMRES (-solver 0 | 1 | 3 and their kin)")
     if spec.precond == "ilu" and (opt.num_components > 1 or opt.lgmres or opt.hybrid):
         raise SystemExit("ij: -solver %d (ILU) takes one component, and neither LGMRES nor the hybrid solver" % opt.solver)
     if opt.hybrid not in (0, 1) or (opt.hybrid and opt.solver != 0):
@@ -541,6 +572,8 @@ def run(opt, comm=0, rank=0, nprocs=1, allreduce=None, out=None):
     import sys
     out = out or sys.stdout
     L = B.load_library()
+    if nprocs > 1 and opt.smooth_num_levels > 0:
+        raise SystemExit("ij: ILU smoothing (smooth_type 5 | 15) on more than one rank is outside the scope of this driver")
     A = build_matrix(opt, comm=comm, rank=rank, nprocs=nprocs)
     if opt.hybrid:
         return run_hybrid(opt, A, comm=comm, rank=rank, allreduce=allreduce, out=out)

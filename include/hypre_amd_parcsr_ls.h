@@ -217,8 +217,7 @@ HYPRE_Int HYPRE_BoomerAMGSetPrintLevel(HYPRE_Solver solver, HYPRE_Int print_leve
 HYPRE_Int HYPRE_BoomerAMGSetLogging(HYPRE_Solver solver, HYPRE_Int logging);
 /* Option gates (HYPRE_parcsr_amg.c): setters an application written against hypre calls routinely, for options whose
  * other branches are outside this library.  The value that selects what is implemented here is accepted (named in each
- * comment); any other value raises HYPRE_ERROR_ARG(2) with a message.  SetDebugFlag / SetNumPaths / SetSmoothType /
- * SetSmoothNumSweeps are accepted and inert. */
+ * comment); any other value raises HYPRE_ERROR_ARG(2) with a message.  SetDebugFlag / SetNumPaths are accepted and inert. */
 HYPRE_Int HYPRE_BoomerAMGSetMeasureType(HYPRE_Solver solver, HYPRE_Int measure_type);          /* 0 local, 1 global */
 HYPRE_Int HYPRE_BoomerAMGSetDebugFlag(HYPRE_Solver solver, HYPRE_Int debug_flag);
 HYPRE_Int HYPRE_BoomerAMGSetNumPaths(HYPRE_Solver solver, HYPRE_Int num_paths);
@@ -228,9 +227,47 @@ HYPRE_Int HYPRE_BoomerAMGSetSeqThreshold(HYPRE_Solver solver, HYPRE_Int seq_thre
 HYPRE_Int HYPRE_BoomerAMGSetRedundant(HYPRE_Solver solver, HYPRE_Int redundant);               /* 0 */
 HYPRE_Int HYPRE_BoomerAMGSetRAP2(HYPRE_Solver solver, HYPRE_Int rap2);                         /* 0 */
 HYPRE_Int HYPRE_BoomerAMGSetRestriction(HYPRE_Solver solver, HYPRE_Int restr_par);             /* 0 */
-HYPRE_Int HYPRE_BoomerAMGSetSmoothNumLevels(HYPRE_Solver solver, HYPRE_Int smooth_num_levels); /* 0 */
+/* ILU as a level smoother (par_cycle.c:293-326, 477-483, 614-636; defaults smooth_type 6, smooth_num_levels 0,
+ * smooth_num_sweeps 1).  Of the reference's complex smoothers only ILU is built: smooth_type 5 applies HYPRE_ILUSolve
+ * smooth_num_sweeps times on every level < smooth_num_levels in place of the relaxation (the coarsest level's direct solve
+ * included when the count reaches it); 15 wraps smooth_num_sweeps conjugate-gradient steps around num_grid_sweeps ILU
+ * applications from zero.  ORDER: SetSmoothType comes before SetSmoothNumLevels — a positive level count is accepted only
+ * while the stored type is 5 or 15, and a type other than these is refused while the count is positive (HYPRE_ERROR_ARG(2)
+ * with a message); every type is accepted while the count is 0 and has no effect then.  One rank, one column, fp64
+ * hierarchy: anything else is refused by Setup with a message.  Deviation: where the reference's acceleration divides
+ * 0 by 0 (gamma = <R, Z> exactly 0: a zero right-hand side) and fills U with NaN, the visit ends and U stays. */
+HYPRE_Int HYPRE_BoomerAMGSetSmoothNumLevels(HYPRE_Solver solver, HYPRE_Int smooth_num_levels); /* 0; > 0 with type 5 | 15 */
 HYPRE_Int HYPRE_BoomerAMGSetSmoothType(HYPRE_Solver solver, HYPRE_Int smooth_type);
-HYPRE_Int HYPRE_BoomerAMGSetSmoothNumSweeps(HYPRE_Solver solver, HYPRE_Int smooth_num_sweeps);
+HYPRE_Int HYPRE_BoomerAMGSetSmoothNumSweeps(HYPRE_Solver solver, HYPRE_Int smooth_num_sweeps); /* >= 1 */
+/* Parameters of the level smoothers (par_amg.c:223-231: type 0, level 0, max_row_nnz 20, max_iter 1, droptol 0.01,
+ * tri_solve 1, 5 and 5 Jacobi iterations, reordering 1), handed on by Setup as par_amg_setup.c:3710-3726 hands them on. */
+HYPRE_Int HYPRE_BoomerAMGSetILUType(HYPRE_Solver solver, HYPRE_Int ilu_type);                  /* 0 */
+HYPRE_Int HYPRE_BoomerAMGSetILULevel(HYPRE_Solver solver, HYPRE_Int ilu_lfil);                 /* >= 0 */
+HYPRE_Int HYPRE_BoomerAMGSetILULocalReordering(HYPRE_Solver solver, HYPRE_Int ilu_reordering_type);   /* 0 none, 1 RCM */
+HYPRE_Int HYPRE_BoomerAMGSetILUMaxIter(HYPRE_Solver solver, HYPRE_Int ilu_max_iter);           /* applications per HYPRE_ILUSolve */
+/* 1 direct, 0 Jacobi sweeps: the reference's meaning (hypre_amd_ILUSetIterativeTriSolve(.., 1) on the level smoothers;
+ * HYPRE_ILUSetTriSolve(.., 0) itself stays refused) */
+HYPRE_Int HYPRE_BoomerAMGSetILUTriSolve(HYPRE_Solver solver, HYPRE_Int ilu_tri_solve);
+HYPRE_Int HYPRE_BoomerAMGSetILULowerJacobiIters(HYPRE_Solver solver, HYPRE_Int ilu_lower_jacobi_iters);   /* >= 0 */
+HYPRE_Int HYPRE_BoomerAMGSetILUUpperJacobiIters(HYPRE_Solver solver, HYPRE_Int ilu_upper_jacobi_iters);   /* >= 0 */
+HYPRE_Int HYPRE_BoomerAMGSetILUDroptol(HYPRE_Solver solver, HYPRE_Real ilu_droptol);           /* stored; no effect for type 0 */
+HYPRE_Int HYPRE_BoomerAMGSetILUMaxRowNnz(HYPRE_Solver solver, HYPRE_Int ilu_max_row_nnz);      /* stored; no effect for type 0 */
+HYPRE_Int HYPRE_BoomerAMGSetILUIterSetupType(HYPRE_Solver solver, HYPRE_Int ilu_iter_setup_type);   /* 0 */
+/* the HYPRE_ILU object of a level (NULL where the level has none): parameters and launch statistics through hypre_amd_ILUGet* */
+HYPRE_Int hypre_amd_BoomerAMGGetSmoother(HYPRE_Solver solver, HYPRE_Int level, HYPRE_Solver *ilu);
+/* the settings as they stand; of the last cycle, the level visits the smoother served and the reductions read back to the
+ * host inside them (0 with hypre_amd_SetSmootherFusion on); any pointer may be NULL */
+HYPRE_Int hypre_amd_BoomerAMGGetSmootherStats(HYPRE_Solver solver, HYPRE_Int *smooth_type, HYPRE_Int *smooth_num_levels,
+                                              HYPRE_Int *smooth_num_sweeps, HYPRE_Int *visits, HYPRE_Int *readbacks);
+/* smooth_type 15 with both inner products left on the device (default 1) or as the reference's call sequence with two
+ * read-backs per sweep (0); same bits.  on < 0: unchanged; returns the setting. */
+HYPRE_Int hypre_amd_SetSmootherFusion(HYPRE_Int on);
+/* the vector kernels of the fused acceleration on their own (tests): `scalars` holds gamma, gammaold, <P, V>, stop flag.
+ * Direction: P = Z (first) or Z + (gamma / gammaold) P; update: U += alfa P, R -= alfa V with alfa = gamma / <P, V>, and
+ * Z = 0 when zero_z; both leave everything as it is when the stop flag is not 0.  Dot: scalars[which ? 2 : 0] = <x, y>
+ * (which 0 moves gamma to gammaold first and raises the stop flag at a sum of exactly 0).  Host arrays in and out. */
+HYPRE_Int hypre_amd_ILUSmootherKernelTest(HYPRE_Int n, HYPRE_Real *scalars, HYPRE_Int first, HYPRE_Int zero_z, HYPRE_Int with_dots,
+                                          HYPRE_Real *U, HYPRE_Real *R, HYPRE_Real *P, HYPRE_Real *Z, const HYPRE_Real *V);
 HYPRE_Int HYPRE_BoomerAMGSetAdditive(HYPRE_Solver solver, HYPRE_Int addlvl);                   /* -1 */
 HYPRE_Int HYPRE_BoomerAMGSetMultAdditive(HYPRE_Solver solver, HYPRE_Int addlvl);               /* -1 */
 HYPRE_Int HYPRE_BoomerAMGSetSimple(HYPRE_Solver solver, HYPRE_Int addlvl);                     /* -1 */
@@ -869,7 +906,8 @@ HYPRE_Int hypre_amd_ParCSRHybridGetKrylovSolver(HYPRE_Solver solver, HYPRE_Solve
  * the device the factors then lie in row slices of 64 rows as well and an application is at most lower + upper launches
  * beside the product with A, whatever the number of dependency levels; the host path is reproduced bit for bit.
  * Outside the scope, refused by the setter: ilu_type other than 0 (ILUT, Schur-GMRES, NSH, RAS, ddPQ, RAP).  Iterative
- * setup and ILU as a BoomerAMG smoother have no entry point. */
+ * setup has no entry point.  As a BoomerAMG level smoother: HYPRE_BoomerAMGSetSmoothType 5 | 15 above.  HYPRE_ILUSolve skips
+ * the residual product when u->all_zeros is set (hypre_ParVectorSetZeros) and takes f as it is: f - A 0 is f. */
 HYPRE_Int HYPRE_ILUCreate(HYPRE_Solver *solver);
 HYPRE_Int HYPRE_ILUDestroy(HYPRE_Solver solver);
 HYPRE_Int HYPRE_ILUSetup(HYPRE_Solver solver, HYPRE_ParCSRMatrix A, HYPRE_ParVector b, HYPRE_ParVector x);

@@ -13,7 +13,12 @@ With `--iterative` the triangular solves are `--ljac` / `--ujac` Jacobi sweeps o
 the slice form beside the stored ones, and the bytes are those of the sweeps (per product with a factor 12 bytes a padded
 entry, per row the slot tables and the vectors the pass reads and writes: DESIGN.md section 6, ILU).  With `--gmres` the
 same object then preconditions GMRES (`ij -solver 81`, restart `--kdim`) on a right-hand side of ones to 1e-8: iterations and
-seconds of the solve."""
+seconds of the solve.
+
+`--amg-smoother 5|15` times something else: one V-cycle of BoomerAMG (PMIS, ext+i) on the same operator with ILU as the smoother
+of ALL levels (smooth_num_levels 25, `--sm-sweeps` sweeps, iterative triangular solves of `--ljac` / `--ujac` sweeps), the
+accelerated smoother fused (hypre_amd_SetSmootherFusion 1) and unfused (0), and beside them the l1-Jacobi V(1,1) cycle of the
+same hierarchy settings.  One JSON line: milliseconds per cycle of the three, smoother visits and read-backs per cycle."""
 import argparse
 import ctypes as C
 import json
@@ -26,8 +31,57 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def amg_smoother_cycles(a, L, B, ij):
+    """one V-cycle with ILU on all levels, fused and unfused, and the l1-Jacobi cycle: median milliseconds of each"""
+    n = a.n ** 3
+    f = np.ones(n)
+
+    def cycle_ms(opt, fusion):
+        A = ij.build_matrix(opt)
+        s = ij.create_amg(ij.check_options(opt), memory_location=B.HYPRE_MEMORY_DEVICE)
+        L.HYPRE_BoomerAMGSetup(s, A, None, None)
+        B.check()
+        L.hypre_ParCSRMatrixMigrate(A, B.HYPRE_MEMORY_DEVICE)
+        L.HYPRE_BoomerAMGSetTol(s, 0.0)
+        L.HYPRE_BoomerAMGSetMaxIter(s, 1)
+        L.hypre_amd_SetSmootherFusion(fusion)
+        df, du = B.parvec_from_numpy(f), B.parvec_from_numpy(np.zeros(n))
+        times = []
+        for k in range(a.warmup + a.reps):
+            L.hypre_ParVectorSetZeros(du)
+            t0 = time.perf_counter()
+            L.HYPRE_BoomerAMGSolve(s, A, df, du)         # ends in a synchronisation of the compute stream
+            if k >= a.warmup:
+                times.append(time.perf_counter() - t0)
+        B.check()
+        st = [C.c_int() for _ in range(5)]
+        L.hypre_amd_BoomerAMGGetSmootherStats(s, *[C.byref(v) for v in st])
+        levels = L.hypre_amd_BoomerAMGGetNumLevels(s)
+        L.hypre_amd_SetSmootherFusion(1)
+        L.HYPRE_BoomerAMGDestroy(s)
+        for v in (df, du):
+            L.hypre_ParVectorDestroy(v)
+        L.hypre_ParCSRMatrixDestroy(A)
+        return 1e3 * float(np.median(times)), 1e3 * min(times), levels, st[3].value, st[4].value
+
+    base = dict(n=(a.n, a.n, a.n), coarsen_type=8, relax_type=18)
+    smooth = dict(base, smooth_type=a.amg_smoother, smooth_num_levels=25, smooth_num_sweeps=a.sm_sweeps, ilu_lfil=a.lfil, ilu_reordering=a.reordering,
+                  ilu_iterative=1, ilu_ljac_iters=a.ljac, ilu_ujac_iters=a.ujac)
+    out = dict(tool="bench_ilu", mode="amg-smoother", n=a.n, rows=n, smooth_type=a.amg_smoother, smooth_num_sweeps=a.sm_sweeps, lfil=a.lfil,
+               ljac=a.ljac, ujac=a.ujac)
+    for name, opt, fusion in (("fused", smooth, 1), ("unfused", smooth, 0), ("l1_jacobi", base, 1)):
+        ms, ms_min, levels, visits, readbacks = cycle_ms(ij.IJOptions(**opt), fusion)
+        out.update({"ms_per_cycle_" + name: round(ms, 4), "ms_min_" + name: round(ms_min, 4), "levels": levels})
+        if name != "l1_jacobi":
+            out.update({"visits_" + name: visits, "readbacks_" + name: readbacks})
+    print(json.dumps(out))
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--amg-smoother", type=int, choices=(5, 15), default=0, help="time a V-cycle with ILU smoothing on all levels instead")
+    ap.add_argument("--sm-sweeps", type=int, default=1, help="smooth_num_sweeps of --amg-smoother")
     ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--lfil", type=int, default=0)
     ap.add_argument("--reordering", type=int, default=1)
@@ -43,6 +97,8 @@ def main():
     L = B.load_library(build_if_missing=True)
     if not L.hypre_amd_DeviceAvailable():
         raise SystemExit("bench_ilu: no HIP device")
+    if a.amg_smoother:
+        return amg_smoother_cycles(a, L, B, ij)
     opt = ij.IJOptions(n=(a.n, a.n, a.n))
     A = ij.build_matrix(opt)
     n = a.n ** 3
